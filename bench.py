@@ -9,16 +9,19 @@ A "step" (default ``--mode cycle``) is the north_star unit of work: one G_A->B +
 forward/backward/Adam step (4 generator passes, 4 discriminator passes, LSGAN + cycle-L1 + gradient-sensitive
 losses; ``sggan._train_step_cycle``) over one synthetic (A,B) batch already resident in HBM; one *image* = one
 A sample (a B sample is consumed with it).  ``--mode reference`` times the literal ``model.py:169-200`` step
-(1 G + 1 D, paired losses) instead; at N=1 it is also reported beside the headline as ``reference_mode_step``.
+(1 G + 1 D, paired losses) instead; with --full at N=1 it is also reported beside the headline as ``reference_mode_step``.
 Workload = BASELINE.json configs[2]: 512x256 (W x H) images, batch 8 per GPU, bf16 storage / f32 accumulate,
 9-block ResNet generators; weak scaling (8 images per GPU), one RCCL all-reduce per network bucket.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying two extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets up,
+warms up, times the --steps steps (all replayed from HIP graphs) and prints that line; ``--dump-outputs DIR`` also writes
+what the last timed step computed as DIR/<name>.npy (see dump_outputs).  ``--full`` adds what takes runs or steps of its own:
   roofline     -- the dominant kernel (3x3 C=256 residual-block conv forward, implicit GEMM M=N*64*128, N=256,
                   K=2304): algorithmic FLOPs per launch / its average duration measured with HIP events on the
                   launch stream inside the timed region, vs the 2.5 PFLOP/s dense bf16 MFMA peak.
   cpu_baseline -- the PyTorch-CPU float32 restatement of the same step (oracle/torch_restatement.py; "port":
                   the reference's TF2 path cannot run here) timed on the host cores, N=1 image, bounded sample.
+  f32_step, reference_mode_step -- short runs of the same step in float32 and of the reference's literal 1G+1D step.
 """
 import argparse
 import json
@@ -266,6 +269,37 @@ def cpu_baseline(H, W, seed, mode):
             "reference_mode_256x256": ref_small, f"reference_mode_{W}x{H}": ref_full}
 
 
+DUMP_PARAM_SAMPLE = 1 << 20        # entries kept per network's parameter vector
+DUMP_IMAGE_SAMPLE = 1 << 22        # entries kept per image batch (the default 8x256x512x3 batch is written whole)
+
+
+def _seeded_sample(x, n):
+    """x flattened, or a fixed, seeded sample of n of its entries (in index order) when it has more."""
+    x = x.reshape(-1)
+    if x.size <= n:
+        return x
+    return x[np.sort(np.random.default_rng(0).choice(x.size, n, replace=False))]
+
+
+def dump_outputs(model, out_dir):
+    """What a caller of the timed step receives after its last step, as float32 arrays DIR/<name>.npy (at most 48 MB):
+    gen_loss, disc_loss (shape (1,)); fake_A (+ fake_B in cycle mode) in the reference's (N,H,W,3) layout, or a seeded
+    sample of DUMP_IMAGE_SAMPLE entries for larger batches; params_<net> -- a seeded sample of DUMP_PARAM_SAMPLE entries of
+    each network's updated f32 parameter vector (G, D, and G_BA, D_B in cycle mode).  Inputs and initial weights are seeded,
+    so two runs with the same arguments can be compared array by array."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"gen_loss": model.gen_loss.cpu().numpy(), "disc_loss": model.disc_loss.cpu().numpy()}
+    fakes = ("fake_A", "fake_B") if model.cycle else ("fake_A",)
+    for name in fakes:
+        x = getattr(model, name).numpy()
+        arrays[name] = x if x.size <= DUMP_IMAGE_SAMPLE else _seeded_sample(x, DUMP_IMAGE_SAMPLE)
+    keys = ("G", "D", "G_BA", "D_B") if model.cycle else ("G", "D")
+    for key, net in zip(keys, model.networks()):
+        arrays[f"params_{key}"] = _seeded_sample(net.P.flat.cpu().numpy(), DUMP_PARAM_SAMPLE)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
 class _StdoutToStderr:
     """RCCL prints a version banner on stdout when its communicator is created; the bench contract is ONE JSON line
     on stdout, so file descriptor 1 is pointed at stderr while the process group / first collective come up."""
@@ -301,6 +335,8 @@ def main():
     ap.add_argument("--d-quad", type=int, default=1, help="0: reals and fakes go through the discriminators as two stacked passes instead of one (A/B)")
     ap.add_argument("--checkpoint-blocks", type=int, default=0, help="1: activation checkpointing of the generators' residual blocks (BASELINE configs[4]): each block is re-run in backward")
     ap.add_argument("--lib", default=None, help="A/B timing: bind this build of the library instead of the in-tree libsggan.so")
+    ap.add_argument("--full", action="store_true", help="also time kernels (roofline), the CPU baseline, the f32 leg and the reference-mode leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -335,11 +371,12 @@ def main():
     model = make_model(a.mode)
 
     prof = EventProfiler((a.height // 4, a.width // 4))
-    K.PROFILE = prof
-    timing = (rank == 0) and not a.no_kernel_timing
-    # graph mode: the last `eager_tail` steps of the timed region are dispatched eagerly so that their launches can be timed
-    # with events (EventProfiler); every rank does the same (the steps all-reduce)
-    eager_tail = 0 if (a.no_kernel_timing or not a.graph) else max(2, a.steps // 5)
+    kernel_timing = a.full and not a.no_kernel_timing
+    K.PROFILE = prof if kernel_timing else None
+    timing = (rank == 0) and kernel_timing
+    # --full, graph mode: the last `eager_tail` steps of the timed region are dispatched eagerly so that their launches can be
+    # timed with events (EventProfiler); every rank does the same (the steps all-reduce)
+    eager_tail = 0 if (not kernel_timing or not a.graph) else max(2, a.steps // 5)
     eager_tail = min(eager_tail, a.steps)
 
     def barrier():
@@ -376,6 +413,8 @@ def main():
     gl, dl = model.losses()
     if not (np.isfinite(gl) and np.isfinite(dl)):
         raise SystemExit(f"non-finite losses after the timed region: gen {gl} disc {dl}")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(model, a.dump_outputs)
 
     if rank == 0:
         images = a.batch * world * a.steps
@@ -394,6 +433,8 @@ def main():
                        "gflop_per_image": gflop_img, "mixed_gradient_chain": bool(a.mixed),
                        "dispatch": (f"HIP-graph replay of the recorded step (sggan_amd/graph.py) for {a.steps - eager_tail} of the {a.steps} timed "
                                     f"steps, eager launches for the last {eager_tail} (the ones whose kernels are timed with events)"
+                                    if a.graph and eager_tail else
+                                    f"HIP-graph replay of the recorded step (sggan_amd/graph.py) for all {a.steps} timed steps"
                                     if a.graph else "eager launches from Python")},
             "graph_steps_images_per_sec": (a.batch * world * (a.steps - eager_tail) / (t_switch - t0)) if t_switch else None,
             "eager_tail_images_per_sec": (a.batch * world * eager_tail / (elapsed - (t_switch - t0))) if t_switch else None,
@@ -461,11 +502,11 @@ def main():
                                                  "(finalize launch not in the span); traffic = FETCH_SIZE (doubled) + WRITE_SIZE of the kernel's read+write "
                                                  "form per tensor byte (profiles/r02_in_traffic.json), scaled to the timed mix"}
         line["kernels"] = kt
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.height, a.width, 19, a.mode)
         else:
             line["cpu_baseline"] = None
-        if world == 1 and a.dtype != "f32" and not a.no_f32_leg:
+        if world == 1 and a.full and a.dtype != "f32" and not a.no_f32_leg:
             # the same step at the reference's own precision (Keras float32 end to end; module.py layers are default-dtype):
             # f32 storage, v_mfma_f32_16x16x4_f32 (1/16 of the bf16 matrix rate), same kernels otherwise; short run
             K.PROFILE = None
@@ -489,7 +530,7 @@ def main():
                                 "what": f"the same {a.mode}-mode step, same shapes, f32 storage and f32 MFMA (the reference trains in float32): "
                                         "the same-precision-as-the-reference number beside the bf16 headline"}
             model = m32
-        if world == 1 and a.mode == "cycle" and not a.no_reference_leg:
+        if world == 1 and a.full and a.mode == "cycle" and not a.no_reference_leg:
             # the literal reference step (1 G + 1 D) beside the headline, same shapes, short run
             K.PROFILE = None
             model._program = None

@@ -1768,17 +1768,15 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
 #define S2_PITCH 40                                    // halo row pitch in pixels (34 used)
 #define S2_HALO_BYTES ((S2_TI + 2) * S2_PITCH * 128)   // 51200
 #define S2_WSTAGE (3 * 64 * 128)                       // one kernel row of taps x 64 output channels x 128 B
-#define S2_STATS_BYTES (8 * 64 * 2 * 4)                // per-wave (sum, sumsq) rows of a tile's 64 channels (forward with the norm-statistics epilogue)
-#define S2_LDS (2 * S2_HALO_BYTES + 2 * S2_WSTAGE + S2_STATS_BYTES)     // 155648
+#define S2_LDS (2 * S2_HALO_BYTES + 2 * S2_WSTAGE)    // 151552
 
-// STATS: the Conv2DTranspose-forward build with the norm-statistics epilogue -- its own instantiation, because the kernel sits at 251 VGPRs and
-// the 32 running sums tipped the common build into 192 spilled registers (-4.5 % on the whole step) when they shared it.
-template <int PT, int PL, bool STATS = false>          // pad_t, pad_l (0 or 1): compile-time so that each tap's class is static
+// (the norm statistics of a Conv2DTranspose forward are a launch of their own, deconv_s2_stats_kernel: the kernel sits at 251 VGPRs and
+// every form of a statistics epilogue inside it spilled)
+template <int PT, int PL>                              // pad_t, pad_l (0 or 1): compile-time so that each tap's class is static
 __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int total_tiles, int tiles_per_block) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sH = smem;                                   // 2 x halo [10][40][128 B]
     char* sW = smem + 2 * S2_HALO_BYTES;               // 2 x [3 taps][64 c][128 B]
-    float* sS = reinterpret_cast<float*>(smem + 2 * S2_HALO_BYTES + 2 * S2_WSTAGE);   // [8 waves][64 channels][2]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int SC = a.K, DC = a.C;                      // dy channels (reduction), dx channels
     const int wrow = 9 * SC, nchunk = SC >> 6;
@@ -1914,9 +1912,8 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
                 for (int e = 0; e < 4; ++e) bv[i][e] = bias_t ? bias_t[cur.n0 + i * 16 + fq * 4 + e] : 0.f;
             auto epilogue = [&](auto act_c) {
                 constexpr int ACT = decltype(act_c)::value;
-                auto store_tile = [&](auto add_c, auto st_c) {
+                auto store_tile = [&](auto add_c) {
                     constexpr bool ADD = decltype(add_c)::value;
-                    constexpr bool ST = STATS && decltype(st_c)::value && !ADD && S2_WIDE;      // Conv2DTranspose forward + the following norm's sums
                     if constexpr (S2_WIDE) {
                         // 16-byte stores: the two pixel fragments of a class trade halves between lane rows (row_swap16, see the
                         // 3x3 halo GEMM's epilogue) -- 16 store instructions per wave and tile instead of 32; the layers this
@@ -1953,53 +1950,6 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
                                 st16(reinterpret_cast<bf16*>(a.dst) + dpix * DC + dc, pk);
                             }
                         }
-                        if constexpr (ST) {
-                            // Statistics of the STORED values (channel 16 i + 4 fq + e of this lane), as a SECOND pass over the accumulators,
-                            // one channel group at a time: 8 running sums instead of 32 next to 128 accumulators (the kernel has no
-                            // registers to spare; the re-evaluation is a few hundred VALU instructions per tile).  Wave: 16-lane butterfly
-                            // (fixed order) -> one (sum, sumsq) per channel; block: the eight waves' rows through LDS, summed in wave
-                            // order by 128 threads -> ONE partial row per (image, pixel tile), channels n0 .. n0 + 63
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                                        for (int e = 0; e < 4; ++e) {
-                                            const float r = (float)(bf16)act_apply_c<ACT>(acc[c][j][i][e] + bv[i][e], a.leak);
-                                            s1[e] += r; s2[e] += r * r;
-                                        }
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                                    for (int off = 1; off < 16; off <<= 1) {
-                                        s1[e] += __shfl_xor(s1[e], off);
-                                        s2[e] += __shfl_xor(s2[e], off);
-                                    }
-                                }
-                                if (frow == 0) {
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) {
-                                        float* o = sS + ((wave * 64) + i * 16 + fq * 4 + e) * 2;
-                                        o[0] = s1[e]; o[1] = s2[e];
-                                    }
-                                }
-                            }
-                            SGG_WAIT_LGKM0();
-                            __builtin_amdgcn_s_barrier();
-                            if (tid < 128) {
-                                const int ch = tid >> 1, which = tid & 1;
-                                float t = 0.f;
-#pragma unroll
-                                for (int w8 = 0; w8 < 8; ++w8) t += sS[(w8 * 64 + ch) * 2 + which];
-                                const int chunks = tilesI * tilesJ;
-                                const int chunk = (cur.i0 / S2_TI) * tilesJ + cur.j0 / S2_TJ;
-                                a.stats[(((size_t)cur.img * chunks + chunk) * DC + cur.n0 + ch) * 2 + which] = t;
-                            }
-                            // (the next tile's rows are written at least a main-loop barrier later)
-                        }
                         return;
                     }
 #pragma unroll
@@ -2026,14 +1976,74 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
                         }
                     }
                 };
-                if constexpr (STATS) store_tile(std::false_type{}, std::true_type{});
-                else if (a.addend) store_tile(std::true_type{}, std::false_type{});
-                else store_tile(std::false_type{}, std::false_type{});
+                if (a.addend) store_tile(std::true_type{});
+                else store_tile(std::false_type{});
             };
-            // (the statistics build serves a layer followed by a norm: no activation, and no tanh code next to its second pass)
-            if constexpr (STATS) epilogue(std::integral_constant<int, SGG_ACT_NONE>{}); else act_dispatch(a.act, epilogue);
+            act_dispatch(a.act, epilogue);
             cur = nxt; ++tcur; chunk = 0;
         } else ++chunk;
+    }
+}
+
+// Instance-norm statistics of a Conv2DTranspose forward's STORED bf16 output (sgg_deconv2d_fwd_stats): one block per (image, 16 x 64
+// output-pixel tile of deconv_s2_halo_kernel, 64 channels) writes that tile's (sum, sumsq) row of channels n0 .. n0 + 63.  The sums are
+// formed in the order the tile's own epilogue formed them when it carried them: wave w reads output rows 2w, 2w+1 of the tile; lane
+// (frow, fq) adds parity classes c = 0..3 x pixel fragments j = 0..1 of channels 16 i + 4 fq + e, a 16-lane butterfly (fixed order) gives
+// one (sum, sumsq) per channel and wave, and 128 threads add the eight waves' rows in wave order.
+__global__ __launch_bounds__(512) void deconv_s2_stats_kernel(ConvArgs a) {
+    __shared__ float sS[8 * 64 * 2];                   // [wave][channel][sum, sumsq]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int DC = a.C;
+    const int tilesN = DC >> 6, tilesJ = a.Wo / S2_TJ, tilesI = a.Ho / S2_TI;
+    int t = (int)blockIdx.x;
+    const int n0 = (t % tilesN) * 64; t /= tilesN;
+    const int j0 = (t % tilesJ) * S2_TJ; t /= tilesJ;
+    const int i0 = (t % tilesI) * S2_TI;
+    const int img = t / tilesI;
+    const bf16* y = reinterpret_cast<const bf16*>(a.dst);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+        const int dc = n0 + i * 16 + fq * 4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int h = 2 * (i0 + wave) + (c >> 1);
+                const int w = 2 * (j0 + j * 16 + frow) + (c & 1);
+                const bf16x4 v = *reinterpret_cast<const bf16x4*>(y + (((size_t)img * a.H + h) * a.W + w) * DC + dc);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float r = (float)v[e];
+                    s1[e] += r; s2[e] += r * r;
+                }
+            }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) {
+                s1[e] += __shfl_xor(s1[e], off);
+                s2[e] += __shfl_xor(s2[e], off);
+            }
+        }
+        if (frow == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float* o = sS + ((wave * 64) + i * 16 + fq * 4 + e) * 2;
+                o[0] = s1[e]; o[1] = s2[e];
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < 128) {
+        const int ch = tid >> 1, which = tid & 1;
+        float acc = 0.f;
+#pragma unroll
+        for (int w8 = 0; w8 < 8; ++w8) acc += sS[(w8 * 64 + ch) * 2 + which];
+        const int chunks = tilesI * tilesJ;
+        const int chunk = (i0 / S2_TI) * tilesJ + j0 / S2_TJ;
+        a.stats[(((size_t)img * chunks + chunk) * DC + n0 + ch) * 2 + which] = acc;
     }
 }
 
@@ -2045,9 +2055,9 @@ static bool s2halo_ok(const ConvArgs& a, bool is_bf16) {
     return a.K % 64 == 0 && a.C % 64 == 0 && a.Wo % S2_TJ == 0 && a.Ho % S2_TI == 0;
 }
 
-template <int PT, int PL, bool STATS = false>
+template <int PT, int PL>
 static int launch_s2halo_p(const ConvArgs& a, hipStream_t s) {
-    auto kern = deconv_s2_halo_kernel<PT, PL, STATS>;
+    auto kern = deconv_s2_halo_kernel<PT, PL>;
     SGG_LDS_ATTR(kern, S2_LDS);
     const int total = (int)((int64_t)a.N * (a.Ho / S2_TI) * (a.Wo / S2_TJ) * (a.C / 64));
     const int tpb = (total + 255) / 256;               // one persistent block per CU
@@ -2056,8 +2066,13 @@ static int launch_s2halo_p(const ConvArgs& a, hipStream_t s) {
     return sgg_check_launch();
 }
 static int launch_s2halo(const ConvArgs& a, hipStream_t s) {
-    if (a.stats) return a.addend ? SGG_EUNSUPPORTED : launch_s2halo_p<0, 0, true>(a, s);
-    return launch_s2halo_p<0, 0>(a, s);
+    if (!a.stats) return launch_s2halo_p<0, 0>(a, s);
+    if (a.addend || a.act != SGG_ACT_NONE) return SGG_EUNSUPPORTED;      // the statistics serve a layer followed by a norm
+    const int rc = launch_s2halo_p<0, 0>(a, s);
+    if (rc != SGG_OK) return rc;
+    const int blocks = a.N * (a.Ho / S2_TI) * (a.Wo / S2_TJ) * (a.C / 64);
+    hipLaunchKernelGGL(deconv_s2_stats_kernel, dim3((unsigned)blocks), dim3(512), 0, s, a);
+    return sgg_check_launch();
 }
 
 // shapes the halo-resident kernel takes: 3x3, stride 1, pad 1 on a same-size output, bf16, 64 | source channels,
@@ -5209,7 +5224,7 @@ int sgg_deconv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const
 }
 
 // Conv2DTranspose forward that also emits the per-chunk (sum, sumsq) rows of its stored output for the instance norm behind it
-// (module.py:254-260): one row per (image, 16 x 64 output-pixel tile) from the stride-2 halo kernel's epilogue.
+// (module.py:254-260): one row per (image, 16 x 64 output-pixel tile) of the stride-2 halo kernel, from deconv_s2_stats_kernel.
 size_t sgg_deconv2d_fwd_stats_chunks(const sgg_conv_desc* d) {
     if (!desc_ok(d) || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_ZERO || !S2_WIDE) return 0;
     ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);

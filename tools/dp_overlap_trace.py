@@ -1,7 +1,7 @@
 """Where the data-parallel step's all-reduce kernels land relative to the backward kernels, from a rocprofv3 --kernel-trace CSV of
 
     RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 rocprofv3 --kernel-trace --output-format csv -d <dir> -- \
-        python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-reference-leg --no-f32-leg
+        python3 bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-reference-leg --no-f32-leg
 
 (one rank: RCCL moves nothing, but every bucket's all-reduce is a real kernel on RCCL's stream, launched by the same host actions
 between the same graph segments as on 8 ranks).  For each step of the timed region: every RCCL kernel's start offset from the

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/ktrace; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/raw -- python3 $R/bench.py --steps 6 --warmup 2 --graph 0 --no-cpu-baseline --no-f32-leg --no-reference-leg > $O/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/raw -- python3 $R/bench.py --full --steps 6 --warmup 2 --graph 0 --no-cpu-baseline --no-f32-leg --no-reference-leg > $O/run.log 2>&1
 python3 - "$1" <<PY
 import csv, glob, sys, collections
 pat = sys.argv[1]

@@ -5,6 +5,6 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/trace_$1; shift
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/raw -- python3 $R/bench.py --no-cpu-baseline "$@" > $O/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/raw -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $O/run.log 2>&1
 python3 $R/tools/trace_gaps.py $(ls $O/raw/*/*kernel_trace.csv | head -1) > $O/gaps.txt 2>&1
 rm -rf $O/raw
