@@ -258,6 +258,20 @@ int sgg_instnorm_bwd_partial(const void* dy, const void* x, const float* gamma, 
                              float* dgamma, float* dbeta, const float* partial, int chunks, int N, int64_t HW, int C, int C_real,
                              int accumulate, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* Skip added BEFORE the activation (generator_unet d3 / d7, module.py:181-184,199-202): y = act(gamma*xhat + beta + skip),
+ * act RELU / LRELU / NONE.  Same stats layout and workspace as sgg_instnorm_fwd; the _partial form takes the conv epilogue's
+ * partial sums like sgg_instnorm_fwd_partial.
+ * Backward: given dy and the stored output y, dskip = dy * act'(y) (the skip path's gradient: written once, by the statistics
+ * pass; it may alias dy), dx = the norm's input gradient for dskip, dgamma/dbeta as sgg_instnorm_bwd.  Deterministic. */
+int sgg_instnorm_fwd_skip(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                          int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream);
+int sgg_instnorm_fwd_skip_partial(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                                  const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
+                                  void* stream);
+int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
+                          void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
+                          int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream);
+
 /* Two networks of the same shape in lockstep on ONE stacked batch (the cycle step's G_A->B / G_B->A and D_A / D_B pairs,
  * model.py:114-133 applied to both translation directions): images 0..nsplit-1 belong to the first network (gamma, beta,
  * dgamma, dbeta), images nsplit..N-1 to the second (gamma2, ...).  Instance norm is per image, so one launch over the 2x larger

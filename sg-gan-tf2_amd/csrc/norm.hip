@@ -418,6 +418,145 @@ __global__ __launch_bounds__(256) void in_fused_small_kernel(const char* x, cons
 
 __global__ void in_param_grad_kernel(InParamGrad g, int C, InSplit sp) { in_param_grad(g, C, sp); }
 
+
+// -------------------------------------------------------------------------------------------------
+// Skip added BEFORE the activation: y = act(gamma*xhat + beta + skip) -- generator_unet's d3 / d7 (module.py:181-184,
+// 199-202: IN, add([., e5]), Activation('relu')).  The forward is the statistics pass / finalize above plus its own apply
+// kernel; the backward takes the stored OUTPUT y: dz = dy * act'(y) (relu / lrelu keep the sign, so act'(y) == act'(z)) is
+// computed once, in the statistics pass, and stored -- it is the skip path's gradient and the input of the unchanged
+// act-NONE apply pass (in_apply_kernel<T, true>), which then reads dz and x only.
+// -------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void in_apply_skip_kernel(const char* x, const char* skip, const float* gamma, const float* beta,
+                                                            const float* stats, char* out, int64_t HW, int C, int rows_per_block,
+                                                            int act, float leak) {
+    constexpr int VEC = ET<T>::VEC;
+    const int CV = C / VEC;
+    const int n = blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t p1 = p0 + rows_per_block < HW ? p0 + rows_per_block : HW;
+    for (int cvb = 0; cvb < CV; cvb += 256) {
+        const int lanes = CV - cvb < 256 ? CV - cvb : 256;
+        const int rows = 256 / lanes;
+        const int cv = cvb + (int)(threadIdx.x % lanes), prow = threadIdx.x / lanes;
+        if (prow >= rows) continue;
+        float A[VEC], B[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const int c = cv * VEC + e;
+            const float mu = stats[((size_t)n * C + c) * 2], rs = stats[((size_t)n * C + c) * 2 + 1];
+            A[e] = gamma[c] * rs; B[e] = beta[c] - mu * A[e];
+        }
+        act_dispatch(act, [&](auto act_c) {
+            constexpr int ACT = decltype(act_c)::value;
+            auto one = [&](const u32x4& xr, const u32x4& sr, size_t off) {
+                float xv[VEC], sv[VEC], o[VEC];
+                ET<T>::unpack(xr, xv);
+                ET<T>::unpack(sr, sv);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) o[e] = act_apply_c<ACT>(xv[e] * A[e] + B[e] + sv[e], leak);
+                st16(out + off, ET<T>::pack(o));
+            };
+            const size_t base = ((size_t)n * HW * C + (size_t)cv * VEC) * sizeof(T), pstep = (size_t)C * sizeof(T);
+            int64_t p = p0 + prow;
+            for (; p + 3 * rows < p1; p += 4 * rows) {               // 4 pixels per trip, all loads first (see in_partial_kernel)
+                u32x4 xr[4], sr[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const size_t off = base + (size_t)(p + u * rows) * pstep;
+                    xr[u] = ld16_nt(x + off);
+                    sr[u] = ld16_nt(skip + off);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) one(xr[u], sr[u], base + (size_t)(p + u * rows) * pstep);
+            }
+            for (; p < p1; p += rows) {
+                const size_t off = base + (size_t)p * pstep;
+                one(ld16_nt(x + off), ld16_nt(skip + off), off);
+            }
+        });
+    }
+}
+
+// Backward statistics pass of the skip form: dz = dy * act'(y) is stored to dz_out, and the per-chunk (sum dz, sum dz*xhat)
+// rows are written in the layout of in_partial_kernel (fixed per-thread pixel order, fixed combine order -> deterministic).
+template <typename T>
+__global__ __launch_bounds__(256) void in_skip_bwd_partial_kernel(const char* x, const char* dy, const char* y, const float* stats,
+                                                                  char* dz_out, float* partial, int64_t HW, int C, int chunks, int rpc,
+                                                                  int act, float leak) {
+    constexpr int VEC = ET<T>::VEC;
+    const int CV = C / VEC;
+    const int n = blockIdx.y, chunk = blockIdx.x;
+    const int64_t p0 = (int64_t)chunk * rpc;
+    const int64_t p1 = p0 + rpc < HW ? p0 + rpc : HW;
+    using AccT = InAcc<T>;
+    __shared__ AccT red[256][2 * VEC + 1];
+    for (int cvb = 0; cvb < CV; cvb += 256) {
+        const int lanes = CV - cvb < 256 ? CV - cvb : 256;
+        const int rows = 256 / lanes;
+        const int cv = cvb + (int)(threadIdx.x % lanes), prow = threadIdx.x / lanes;
+        AccT s1[VEC], s2[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s1[e] = s2[e] = (AccT)0;
+        if (prow < rows) {
+            float mu[VEC], rs[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const int c = cv * VEC + e;
+                mu[e] = stats[((size_t)n * C + c) * 2]; rs[e] = stats[((size_t)n * C + c) * 2 + 1];
+            }
+            act_dispatch(act, [&](auto act_c) {
+                constexpr int ACT = decltype(act_c)::value;
+                auto one = [&](const u32x4& xr, const u32x4& gr, const u32x4& yr, size_t off) {
+                    float xv[VEC], gv[VEC], yv[VEC], dz[VEC];
+                    ET<T>::unpack(xr, xv);
+                    ET<T>::unpack(gr, gv);
+                    ET<T>::unpack(yr, yv);
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) dz[e] = gv[e] * act_grad_c<ACT>(yv[e], leak);
+                    const u32x4 dzr = ET<T>::pack(dz);
+                    st16(dz_out + off, dzr);
+                    // the sums are taken over the STORED dz (what the apply pass reads back), so both passes see the same values
+                    ET<T>::unpack(dzr, dz);
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) {
+                        const float xh = (xv[e] - mu[e]) * rs[e];
+                        s1[e] += (AccT)dz[e]; s2[e] += (AccT)dz[e] * (AccT)xh;
+                    }
+                };
+                const size_t base = ((size_t)n * HW * C + (size_t)cv * VEC) * sizeof(T), pstep = (size_t)C * sizeof(T);
+                int64_t p = p0 + prow;
+                for (; p + rows < p1; p += 2 * rows) {                 // 2 pixels per trip (three tensors read), loads first
+                    u32x4 xr[2], gr[2], yr[2];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const size_t off = base + (size_t)(p + u * rows) * pstep;
+                        xr[u] = ld16(x + off); gr[u] = ld16_nt(dy + off); yr[u] = ld16_nt(y + off);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) one(xr[u], gr[u], yr[u], base + (size_t)(p + u * rows) * pstep);
+                }
+                for (; p < p1; p += rows) {
+                    const size_t off = base + (size_t)p * pstep;
+                    one(ld16(x + off), ld16_nt(dy + off), ld16_nt(y + off), off);
+                }
+            });
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { red[threadIdx.x][e] = s1[e]; red[threadIdx.x][VEC + e] = s2[e]; }
+        __syncthreads();
+        for (int item = threadIdx.x; item < lanes * VEC; item += 256) {
+            const int l = item / VEC, e = item % VEC;
+            AccT a = (AccT)0, b = (AccT)0;
+            for (int r = 0; r < rows; ++r) { a += red[r * lanes + l][e]; b += red[r * lanes + l][VEC + e]; }
+            const int c = (cvb + l) * VEC + e;
+            const size_t o = (((size_t)n * chunks + chunk) * C + c) * 2;
+            partial[o] = (float)a; partial[o + 1] = (float)b;
+        }
+        __syncthreads();
+    }
+}
+
 static bool in_use_fused(int64_t HW) {
     const int mx = sgg_config().in_fused_maxhw;
     return HW <= (mx >= 0 ? mx : IN_FUSED_MAXHW);
@@ -616,6 +755,71 @@ int sgg_instnorm_bwd_pair(const void* dy, const void* x, const float* gamma, con
     if (!in_pair_ok(gamma2, beta2, nsplit, N) || !dgamma2 || !dbeta2) return SGG_EINVAL;
     InSplit sp; sp.gamma2 = gamma2; sp.beta2 = beta2; sp.dgamma2 = dgamma2; sp.dbeta2 = dbeta2; sp.nsplit = nsplit;
     return instnorm_bwd_impl(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream, sp);
+}
+
+// ---- skip added before the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip)
+static int instnorm_fwd_skip_apply(const void* x, const float* gamma, const float* beta, const void* skip, void* y, const float* stats,
+                                   int N, int64_t HW, int C, int act, float leak, int dtype, hipStream_t s) {
+    const int rpb = in_rows_per_block(N, HW, C, 0);
+    const dim3 ga((unsigned)((HW + rpb - 1) / rpb), N);
+    if (dtype == SGG_BF16) hipLaunchKernelGGL(in_apply_skip_kernel<bf16>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak);
+    else hipLaunchKernelGGL(in_apply_skip_kernel<float>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak);
+    return sgg_check_launch();
+}
+int sgg_instnorm_fwd_skip(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                          int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !gamma || !beta || !skip || !y || !stats || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
+    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
+    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
+    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = in_chunks(HW);
+    float* partial = (float*)ws;
+    const dim3 gp(chunks, N);
+    const InSplit sp = in_nosplit();
+    if (dtype == SGG_BF16) hipLaunchKernelGGL((in_partial_kernel<bf16, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
+    else hipLaunchKernelGGL((in_partial_kernel<float, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
+    hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
+    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s);
+}
+int sgg_instnorm_fwd_skip_partial(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                                  const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
+                                  void* stream) {
+    if (!x || !gamma || !beta || !skip || !y || !stats || !partial || chunks <= 0 || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
+    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
+    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
+    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s);
+}
+int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
+                          void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
+                          int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    if (!dy || !y || !x || !gamma || !beta || !stats || !dx || !dskip || !dgamma || !dbeta || N <= 0 || HW <= 0 || C <= 0 ||
+        C % SGG_CPAD || C_real <= 0 || C_real > C) return SGG_EINVAL;
+    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
+    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
+    if (dx == dskip || dx == dy || dx == x) return SGG_EINVAL;
+    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = in_chunks(HW);
+    float* partial = (float*)ws;
+    float* sums = partial + (size_t)N * chunks * C * 2;
+    float* tot = sums + (size_t)N * C * 2;
+    const int rpb = in_rows_per_block(N, HW, C, 0);
+    const dim3 gp(chunks, N), ga((unsigned)((HW + rpb - 1) / rpb), N);
+    const InParamGrad pg{tot, dgamma, dbeta, N, C_real, accumulate};
+    const InSplit sp = in_nosplit();
+    if (dtype == SGG_BF16) {
+        hipLaunchKernelGGL(in_skip_bwd_partial_kernel<bf16>, gp, dim3(256), 0, s, (const char*)x, (const char*)dy, (const char*)y, stats, (char*)dskip, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak);
+        hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
+        hipLaunchKernelGGL((in_apply_kernel<bf16, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dskip, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, (int)SGG_ACT_NONE, 0.f, pg, sp);
+    } else {
+        hipLaunchKernelGGL(in_skip_bwd_partial_kernel<float>, gp, dim3(256), 0, s, (const char*)x, (const char*)dy, (const char*)y, stats, (char*)dskip, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak);
+        hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
+        hipLaunchKernelGGL((in_apply_kernel<float, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dskip, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, (int)SGG_ACT_NONE, 0.f, pg, sp);
+    }
+    return sgg_check_launch();
 }
 
 }  // extern "C"

@@ -539,6 +539,42 @@ def instnorm_bwd_partial(dy, x, partial, gamma, beta, stats, dgamma, dbeta, accu
     return dx
 
 
+# ---- the skip added BEFORE the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip)
+def instnorm_fwd_skip(x, gamma, beta, skip, eps=1e-3, act=A.ACT_NONE, leak=0.0, partial=None):
+    """partial: the producing conv's (sum, sumsq) rows (conv_fwd_stats / deconv_fwd_stats) -- the norm skips its statistics pass."""
+    N, H, W, Cp = x.shape
+    assert gamma.numel() == Cp and beta.numel() == Cp and tuple(skip.shape) == tuple(x.shape) and skip.dtype == x.dtype
+    y = torch.empty_like(x)
+    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
+    pr = _prof("instnorm_fwd_skip", (tuple(x.shape), partial is not None))
+    if pr: pr.start()
+    if partial is not None:
+        assert partial.shape[0] == N and partial.shape[2] == Cp
+        A.check(A.lib().sgg_instnorm_fwd_skip_partial(_p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats), _p(partial), partial.shape[1],
+                                                      N, H * W, Cp, eps, act, leak, dt(x), _s()), "instnorm_fwd_skip_partial")
+    else:
+        ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
+        A.check(A.lib().sgg_instnorm_fwd_skip(_p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats), N, H * W, Cp, eps, act, leak,
+                                              dt(x), _p(ws), ws.numel(), _s()), "instnorm_fwd_skip")
+    if pr: pr.stop()
+    return y, stats
+
+
+def instnorm_bwd_skip(dy, y, x, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
+    """Backward of instnorm_fwd_skip from its stored output y: returns (dx, dskip), dskip = dy * act'(y)."""
+    N, H, W, Cp = x.shape
+    assert dy.dtype == x.dtype and y.dtype == x.dtype and tuple(dy.shape) == tuple(x.shape) == tuple(y.shape)
+    dx, dskip = torch.empty_like(x), torch.empty_like(x)
+    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
+    pr = _prof("instnorm_bwd_skip", tuple(x.shape))
+    if pr: pr.start()
+    A.check(A.lib().sgg_instnorm_bwd_skip(_p(dy), _p(y), _p(x), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dskip), _p(dgamma), _p(dbeta),
+                                          N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak, dt(x), _p(ws), ws.numel(), _s()),
+            "instnorm_bwd_skip")
+    if pr: pr.stop()
+    return dx, dskip
+
+
 # ---- two networks of the same shape on one stacked batch (images 0..nsplit-1: first network; the rest: second)
 def instnorm_fwd_pair(x, gamma, beta, gamma2, beta2, nsplit, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
     N, H, W, Cp = x.shape

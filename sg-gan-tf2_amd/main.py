@@ -41,6 +41,9 @@ def build_parser():
     a("--max_size", dest="max_size", type=int, default=50)
     a("--segment_class", dest="segment_class", type=int, default=34)
     # build-specific knobs (not in the reference)
+    a("--generator", dest="generator", choices=("resnet", "unet"), default="resnet",
+      help="generator network: resnet (generator_resnet, this build's default) or unet (generator_unet: the reference's "
+           "default, i.e. its flag-less --use_resnet False)")
     a("--cycle", dest="cycle", action="store_true", help="2G+2D cycle-mode step (north_star unit)")
     a("--dtype", dest="dtype", default="bf16")
     a("--steps_per_epoch", dest="steps_per_epoch", type=int, default=4)
@@ -90,12 +93,19 @@ def synthetic_test_samples(args, count=2):
     return gen
 
 
+def parse_args(argv=None):
+    """build_parser().parse_args with --generator applied: it decides use_resnet (the reference's type=bool --use_resnet
+    cannot be set to False from the command line; its flag-less default is the U-Net, ``--generator unet`` here)."""
+    args = build_parser().parse_args(argv)
+    args.use_resnet = args.generator == "resnet"
+    return args
+
+
 def main(argv=None):
     """main.py:45-60: ``--phase train`` runs the epoch loop (with the epoch-end test pass and scalar summaries of
     model.py:263-268), ``--phase test`` the test pass of model.py:535-567 -- here on synthetic data (dataset files and their
     decoding are host-side I/O outside the hot path)."""
-    args = build_parser().parse_args(argv)
-    args.use_resnet = True            # the only generator on the hot path (SURVEY.md 2.1)
+    args = parse_args(argv)
     from .model import sggan
     from .utils import SummarySink
     model = sggan(args)

@@ -16,7 +16,7 @@ import torch
 from . import _abi as A
 from . import kernels as K
 from .graph import StepProgram
-from .module import Adam, Discriminator, DiscriminatorPair, Generator, GeneratorPair
+from .module import Adam, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet
 from .utils import ImagePool, StaticImagePool
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32,
@@ -50,20 +50,29 @@ class sggan(object):
         self.input_c_dim, self.output_c_dim = g("input_nc", 3), g("output_nc", 3)
         self.segment_class = g("segment_class", 34)
         self.use_pix2pix = bool(g("use_pix2pix", False))
-        if self.use_pix2pix or not g("use_resnet", True):
-            raise NotImplementedError("only the ResNet generator / mask discriminator path is built "
-                                      "(generator_unet / *_pix2pix are out of scope, SURVEY.md 2.1)")
+        if self.use_pix2pix:
+            raise NotImplementedError("use_pix2pix: generator_pix2pix / discriminator_pix2pix (BatchNorm, 4x4 stride-2 U-Net) are "
+                                      "not built (SURVEY.md 2.1); use_pix2pix=False selects the mask discriminator")
+        # model.py:55-62: --use_resnet picks generator_resnet(), otherwise generator_unet() (the reference's flag-less default)
+        self.arch = "resnet" if g("use_resnet", True) else "unet"
+        self.cycle = bool(g("cycle", False))
+        if self.cycle and self.arch == "unet":
+            raise NotImplementedError("cycle=True with the U-Net generator: the paired cycle step is built on the ResNet "
+                                      "generator's layer layout (GeneratorPair); use use_resnet=True")
         self.dtype = _DTYPES[g("dtype", "bf16")]
         self.device = torch.device(g("device", "cuda"))
         seed = g("seed", 19)
         self.discriminator = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
                                            dtype=self.dtype, device=self.device, seed=seed + 1)          # model.py:54
-        self.generator = Generator(gf_dim=g("ngf", 64), in_c=self.input_c_dim, out_c=self.output_c_dim,
-                                   n_blocks=g("n_blocks", 9), dtype=self.dtype, device=self.device, seed=seed)  # :56
+        if self.arch == "resnet":
+            self.generator = Generator(gf_dim=g("ngf", 64), in_c=self.input_c_dim, out_c=self.output_c_dim,
+                                       n_blocks=g("n_blocks", 9), dtype=self.dtype, device=self.device, seed=seed)  # :56
+        else:
+            self.generator = GeneratorUNet(gf_dim=g("ngf", 64), in_c=self.input_c_dim, out_c=self.output_c_dim,
+                                           dtype=self.dtype, device=self.device, seed=seed)                   # :58
         self.beta1 = g("beta1", 0.5)
         self.lr = self.LR
         # cycle mode (north_star unit, deviation D5): G_A->B = self.generator, D_A = self.discriminator, plus G_B->A and D_B
-        self.cycle = bool(g("cycle", False))
         self.L1_lambda, self.Lg_lambda = float(g("L1_lambda", 10.0)), float(g("Lg_lambda", 5.0))
         self.use_lsgan = bool(g("use_lsgan", True))
         self.cycle_lr = float(g("lr", 0.0002))
@@ -584,10 +593,15 @@ class sggan(object):
         for key, net in zip(names, self.networks()):
             P = net.P
             sd[key] = {"flat": P.flat.cpu(), "m": P.m.cpu(), "v": P.v.cpu(), "t": P.step_count}
+        sd["G"]["arch"] = self.arch             # generator architecture tag (a checkpoint without one is a ResNet checkpoint)
         return sd
 
     def load_state_dict(self, sd):
         names = ("G", "D", "G_BA", "D_B") if self.cycle else ("G", "D")
+        arch = sd["G"].get("arch", "resnet")
+        if arch != self.arch:
+            raise ValueError(f"checkpoint holds a {arch} generator, this model is built with a {self.arch} generator "
+                             f"(--generator {self.arch}); load it into a model built with --generator {arch}")
         for key, net in zip(names, self.networks()):
             P = net.P
             P.flat.copy_(sd[key]["flat"]); P.m.copy_(sd[key]["m"]); P.v.copy_(sd[key]["v"])

@@ -171,6 +171,30 @@ def generator_param_specs(gf_dim=64, in_c=3, out_c=3, n_blocks=9):
     return L
 
 
+def unet_param_specs(gf_dim=64, in_c=3, out_c=3):
+    """(name, shape) in Keras ``trainable_variables`` creation order of generator_unet (module.py:125-206): per layer, in code
+    order, kernel, bias, then the instance norm's gamma, beta.  e1..e8 are Conv2D (HWIO), d1..d8 Conv2DTranspose ((kh,kw,out,in))."""
+    L = []
+
+    def conv(name, shape, out_ch, norm=True):
+        L.append((name + "_w", shape))
+        L.append((name + "_b", (out_ch,)))
+        if norm:
+            L.append((name + "_g", (out_ch,)))
+            L.append((name + "_beta", (out_ch,)))
+
+    enc = [gf_dim, gf_dim * 2, gf_dim * 4] + [gf_dim * 8] * 5
+    cin = in_c
+    for i, c in enumerate(enc, 1):                                  # :139-170
+        conv(f"e{i}", (3, 3, cin, c), c)
+        cin = c
+    for i, c in enumerate([gf_dim * 8] * 4 + [gf_dim * 4, gf_dim * 2, gf_dim], 1):   # :172-202
+        conv(f"d{i}", (3, 3, c, cin), c)
+        cin = c
+    conv("d8", (3, 3, out_c, cin), out_c, norm=False)               # :204-205
+    return L
+
+
 def discriminator_param_specs(df_dim=64, in_c=3, segment_class=34):
     """Creation order of discriminator (module.py:272-318)."""
     L = []
@@ -384,6 +408,46 @@ class _ConvUnit:
         return (dx, None) if next_norm is not None else dx
 
 
+class _SkipActUnit(_ConvUnit):
+    """A Conv2D / Conv2DTranspose + InstanceNorm whose skip tensor is added BEFORE the activation: y = act(IN(conv(x)) + skip)
+    (generator_unet d3 / d7, module.py:181-184,199-202).  The forward record keeps y as well: the backward derives act'
+    from it (sgg_instnorm_bwd_skip) and returns (dx, dskip), dskip being the skip path's gradient."""
+
+    def forward(self, x, residual=None, record_only=False, out=None):
+        assert residual is not None and out is None and not record_only and self.norm
+        P, n = self.net.P, self.name
+        g = self.geom(x)
+        wf, wd = self.packed(x.dtype)
+        part = None
+        if self.kind == "conv":
+            if g.stats_chunks and self.net.fuse_in_stats:
+                xc, part = K.conv_fwd_stats(g, x, wf, P.p(n + "_b"))
+            else:
+                xc = K.conv_fwd(g, x, wf, P.p(n + "_b"))
+        elif g.stats_chunks and self.net.fuse_in_stats and self.net.fuse_in_stats_deconv:
+            xc, part = K.deconv_fwd_stats(g, x, wd, P.p(n + "_b"))
+        else:
+            xc = K.deconv_fwd(g, x, wd, P.p(n + "_b"))
+        y, stats = K.instnorm_fwd_skip(xc, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak, partial=part)
+        return y, (g, x, xc, stats, y)
+
+    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
+        assert addend is None and dy_partial is None and next_norm is None
+        P, n = self.net.P, self.name
+        g, x, xc, stats, y = rec
+        wf, wd = self.packed(x.dtype)
+        if param_grads:
+            dg, db = P.g(n + "_g", buf=gbuf), P.g(n + "_beta", buf=gbuf)
+        else:
+            dg = db = self.net.scratch_vec(K.cpad(self.cout))
+        dxc, dskip = K.instnorm_bwd_skip(dy, y, xc, P.p(n + "_g"), P.p(n + "_beta"), stats, dg, db, param_grads, self.act, self.leak)
+        if param_grads:
+            self.weight_grad(g, x, dxc, gbuf)
+        if not want_dx:
+            return None, dskip
+        return (K.conv_dgrad(g, dxc, wd) if self.kind == "conv" else K.deconv_dgrad(g, dxc, wf)), dskip
+
+
 class _Net:
     def __init__(self, specs, dtype, device, eps, seed):
         self.dtype = dtype
@@ -567,6 +631,73 @@ class Generator(_Net):
         dy = K.pad_channels(dy_real.contiguous(), K.cpad(self.out_c), self.dtype)
         dx = self.backward(tape, dy, want_dx, True, gbuf)
         return None if dx is None else K.unpad_channels(dx, self.in_c)
+
+
+class GeneratorUNet(_Net):
+    """generator_unet (module.py:125-206), the reference's default generator (--use_resnet False): eight 3x3 stride-1 SAME
+    Conv2D + IN + LeakyReLU (e8: ReLU), seven 3x3 stride-1 SAME Conv2DTranspose + IN + additive skip from the mirrored
+    encoder layer (d3 / d7: ReLU after the add), and a Conv2DTranspose to the output channels + tanh.  Dropout (d1-d3) is the
+    identity: the reference calls the generator without ``training=`` (model.py:173-178, 347, 561), so Keras runs it in inference mode."""
+
+    LEAK = 0.3           # tf.keras.layers.LeakyReLU() default alpha
+
+    def __init__(self, gf_dim=64, in_c=3, out_c=3, dtype=torch.bfloat16, device="cuda", eps=1e-3, seed=19):
+        super().__init__(unet_param_specs(gf_dim, in_c, out_c), dtype, device, eps, seed)
+        self.in_c, self.out_c = in_c, out_c
+        U = lambda *a, **k: _ConvUnit(self, *a, padding="SAME", **k)
+        self.enc = [U(f"e{i}", "conv", act=A.ACT_LRELU, leak=self.LEAK) for i in range(1, 8)] + [U("e8", "conv", act=A.ACT_RELU)]
+        self.dec = [(_SkipActUnit(self, f"d{i}", "deconv", stride=1, act=A.ACT_RELU) if i in (3, 7) else
+                     U(f"d{i}", "deconv", stride=1, act=A.ACT_NONE)) for i in range(1, 8)]
+        self.d8 = U("d8", "deconv", stride=1, norm=False, act=A.ACT_TANH)
+
+    def conv_units(self):
+        return self.enc + self.dec + [self.d8]
+
+    def forward(self, x, out=None):
+        """x: internal (N,H,W,8).  Returns (fake internal (N,H,W,8), tape); out: buffer for the result.  tape = the 16 layers'
+        forward records in layer order."""
+        tape, enc_out = [], []
+        h = x
+        for u in self.enc:
+            h, r = u.forward(h)
+            tape.append(r)
+            enc_out.append(h)
+        for j, u in enumerate(self.dec):                       # d(j+1) + e(7-j)
+            h, r = u.forward(h, residual=enc_out[6 - j])
+            tape.append(r)
+        h, r = self.d8.forward(h, out=out)
+        tape.append(r)
+        return h, tape
+
+    def backward(self, tape, dy, want_dx=False, param_grads=True, gbuf=None, on_unit_done=None, addend=None):
+        """As Generator.backward.  The decoder produces the seven skip gradients (d1, d2, d4-d6: the gradient of the layer's
+        output itself; d3, d7: dy * relu'(y) from the norm backward); each is held until the encoder's backward reaches its
+        layer and joins that layer's gradient in the data-gradient store of the conv behind it (addend)."""
+        done = on_unit_done if on_unit_done is not None else (lambda name: None)
+        d = self.d8.backward(tape[15], dy, True, param_grads, gbuf)
+        done("d8")
+        dskip = [None] * 7                                     # dskip[i]: gradient reaching e(i+1)'s output through the skip
+        for j in range(6, -1, -1):
+            u = self.dec[j]
+            if isinstance(u, _SkipActUnit):
+                d, dskip[6 - j] = u.backward(tape[8 + j], d, True, param_grads, gbuf)
+            else:
+                dskip[6 - j] = d
+                d = u.backward(tape[8 + j], d, True, param_grads, gbuf)
+            done(u.name)
+        for k in range(7, -1, -1):
+            u = self.enc[k]
+            if k:
+                d = u.backward(tape[k], d, True, param_grads, gbuf, addend=dskip[k - 1])   # + skip gradient (fused store)
+                dskip[k - 1] = None
+            else:
+                d = u.backward(tape[0], d, want_dx, param_grads, gbuf, addend=addend)
+            done(u.name)
+        return d
+
+    __call__ = Generator.__call__
+    _run = Generator._run
+    _run_backward = Generator._run_backward
 
 
 class Discriminator(_Net):
@@ -913,6 +1044,11 @@ def _apply_net(net, x, mask=None):
 def generator_resnet(**kw) -> Generator:
     """module.py:219 -- returns a callable ``G(x)``; keyword dims default to the reference constants."""
     return Generator(**kw)
+
+
+def generator_unet(**kw) -> GeneratorUNet:
+    """module.py:125 -- the U-Net generator; keyword dims default to the reference constants (gf_dim 64, 3 -> 3 channels)."""
+    return GeneratorUNet(**kw)
 
 
 def discriminator(**kw) -> Discriminator:
