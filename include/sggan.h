@@ -350,6 +350,22 @@ int sgg_seg_class_table(uint32_t* keys_host, uint8_t* vals_host, int capacity);
 /* utils.py:158-165 + :197-199 (deviation D1): one-hot of the align-corners nearest resample of the
  * class-index map:  mask[n,i,j,c] = (idx[n, round(i*(H-1)/(oh-1)), round(j*(W-1)/(ow-1))] == c). */
 int sgg_onehot_resample(const uint8_t* idx, float* mask, int N, int H, int W, int oh, int ow, int n_classes, void* stream);
+/* ---- input pipeline: utils.load_train_data / load_test_data's imread -> resize (-> resize) -> fliplr (utils.py:116-233) over
+ * device-resident uint8 sources.  The skimage resize chain is linear and separable; the caller folds it into one banded
+ * matrix per axis (sggan_amd/data.py) and this applies
+ *   out[n,i,j,c] = ( sum_kr row_w[i][kr] * ( sum_kc col_w[j'][kc] * src[index[n]][row_start[i]+kr][col_start[j']+kc][c] ) ) / 255,
+ *   j' = flip[n] ? W-1-j : j,   c < C   (channels C..SGG_CPAD-1 of out are written as zeros),
+ * f32 accumulation in that order (kc ascending, then kr ascending), independent of the launch geometry.
+ *   src (M,H0,W0,Cs) uint8, Cs = 3 or 4;  index, flip: int32[N] on the DEVICE (the launch is the same every step: graph safe);
+ *   row_w f32 [H][row_taps], row_start int32 [H] with 0 <= row_start[i] <= H0 - row_taps; col_* likewise over W / W0;
+ *   col_step = the largest col_start[j+1] - col_start[j] (sizes the LDS window; coordinates are clamped inside the kernel,
+ *   so tables that break these rules give wrong pixels, not out-of-range accesses);
+ *   out (N,H,W,SGG_CPAD) in dtype -- the layout the networks read, so the step passes it through untouched.
+ * No workspace.  SGG_EUNSUPPORTED: a tile's column window plus its weights exceed 64 KB of LDS. */
+int sgg_resample_u8(const uint8_t* src, int M, int H0, int W0, int Cs, const int32_t* index, const int32_t* flip,
+                    const float* row_w, const int32_t* row_start, int row_taps,
+                    const float* col_w, const int32_t* col_start, int col_taps, int col_step,
+                    void* out, int N, int H, int W, int C, int dtype, void* stream);
 /* ---- evaluation (next-row SURVEY 8(f)4): metric._fast_hist (metric.py:18-24) and scores_seg_fake (metric.py:71-77), bit exact
  * hist[n_class*t + p] += 1 for pixels with 0 <= t,p < n_class (uint64 counts, caller zeroes);
  * labels[i] = argmax_c uint8(255*x[i][c]) over the first C_real channels (first maximum wins). */

@@ -718,6 +718,21 @@ def onehot_resample(idx_u8, oh, ow, n_classes):
     return mask
 
 
+def resample_u8(src_u8, index, flip, rows, cols, out, C):
+    """Band-table resample of device-resident uint8 sources straight into a batch in the internal layout (sgg_resample_u8).
+    src_u8 (M,H0,W0,3|4) uint8; index / flip int32 (N,) device tensors; rows / cols: (weights f32 (n_out,taps), starts int32
+    (n_out,), step) device band tables (data.band_table); out (N,H,W,cpad(C)) bf16 / f32, written in full."""
+    M, H0, W0, Cs = src_u8.shape
+    N, H, W, Cp = out.shape
+    (rw, rs, _), (cw, cs, cstep) = rows, cols
+    assert src_u8.dtype == torch.uint8 and index.dtype == flip.dtype == rs.dtype == cs.dtype == torch.int32
+    assert rw.dtype == cw.dtype == torch.float32 and Cp == A.CPAD and index.numel() == flip.numel() == N
+    assert tuple(rw.shape) == (H, rw.shape[1]) and tuple(cw.shape) == (W, cw.shape[1]) and rs.numel() == H and cs.numel() == W
+    A.check(A.lib().sgg_resample_u8(_p(src_u8), M, H0, W0, Cs, _p(index), _p(flip), _p(rw), _p(rs), rw.shape[1],
+                                    _p(cw), _p(cs), cw.shape[1], int(cstep), _p(out), N, H, W, int(C), dt(out), _s()), "resample_u8")
+    return out
+
+
 def pad_channels(x_f32, Cd, dtype, out=None):
     Cs = x_f32.shape[-1]
     out = _out(out, tuple(x_f32.shape[:-1]) + (Cd,), dtype, x_f32.device)

@@ -1,10 +1,11 @@
 """Flag surface of the reference's ``main.py`` (main.py:14-43: same names, types and defaults -- SURVEY.md 8(f)3)
-driving ``sggan`` on synthetic batches.  The reference's quirks are kept as data, not behaviour: --lr, --L1_lambda
+driving ``sggan`` on a dataset directory (data.py) or, where ``--dataset_dir`` names none, on synthetic batches.  The reference's quirks are kept as data, not behaviour: --lr, --L1_lambda
 and friends are parsed but the live (reference-mode) step hard-codes lr=1e-3 and LAMBDA=100 (model.py:151,205);
 they take effect in --cycle mode, which uses the criteria those flags were written for."""
 from __future__ import annotations
 
 import argparse
+import os
 
 
 def build_parser():
@@ -52,6 +53,8 @@ def build_parser():
     a("--graph", dest="graph", action="store_true", help="replay the step from captured HIP graphs")
     a("--checkpoint_blocks", dest="checkpoint_blocks", action="store_true",
       help="activation checkpointing: re-run each residual block in backward instead of keeping its activations")
+    a("--dataset_dir_B", dest="dataset_dir_B", default=None,
+      help="cycle mode: dataset root of domain B (its trainB* folders, else its trainA*); default: trainB* of --dataset_dir")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 
@@ -101,18 +104,55 @@ def parse_args(argv=None):
     return args
 
 
+def directory_sources(model, args, log=print):
+    """(batches, test_samples) from the dataset directory ``--dataset_dir`` names (as given, else ./datasets/<dataset_dir>:
+    model.py:220), or None where it has no ``trainA`` folder (the caller then keeps the synthetic sources)."""
+    from . import data as D
+    root = D.resolve_root(args.dataset_dir)
+    if root is None:
+        return None
+    if args.use_augmentation:
+        log(" [*] --use_augmentation: the imgaug crop / affine branch (utils.py:55-103) is not built; "
+            "the loader's random flip is (DESIGN.md 11)")
+    dev = model.device
+    cache_A = D.DatasetCache(root, "trainA", device=dev, max_files=args.train_size)
+    cache_B = None
+    if args.cycle:
+        root_B = root
+        if args.dataset_dir_B:
+            root_B = D.resolve_root(args.dataset_dir_B, "trainB") or D.resolve_root(args.dataset_dir_B, "trainA")
+        split_B = "trainB" if root_B and os.path.isdir(os.path.join(root_B, "trainB")) else "trainA"
+        if root_B is None or (not args.dataset_dir_B and split_B == "trainA"):
+            raise FileNotFoundError("--cycle needs a second domain: trainB* under --dataset_dir, or --dataset_dir_B")
+        cache_B = D.DatasetCache(root_B, split_B, device=dev, max_files=args.train_size)
+    batches = D.DirectoryBatches(model, args, cache_A, cache_B)
+    tests = None
+    if os.path.isdir(os.path.join(root, "testA")):
+        tests = D.directory_test_samples(args, D.DatasetCache(root, "testA", device=dev, with_class=False))
+    return batches, tests
+
+
 def main(argv=None):
     """main.py:45-60: ``--phase train`` runs the epoch loop (with the epoch-end test pass and scalar summaries of
-    model.py:263-268), ``--phase test`` the test pass of model.py:535-567 -- here on synthetic data (dataset files and their
-    decoding are host-side I/O outside the hot path)."""
+    model.py:263-268), ``--phase test`` the test pass of model.py:535-567 -- on the dataset directory ``--dataset_dir``
+    names, or on synthetic data where it names none."""
     args = parse_args(argv)
+    from . import data as D
     from .model import sggan
     from .utils import SummarySink
     model = sggan(args)
+    if D.resolve_root(args.dataset_dir) or D.resolve_root(args.dataset_dir, "testA"):
+        # a dataset given as a path: checkpoints go under <checkpoint_dir>/<its folder name>, as they do for a bare name
+        model.dataset_dir = os.path.basename(os.path.normpath(args.dataset_dir)) or args.dataset_dir
     if args.phase == "test":          # main.py:58-60
+        root = D.resolve_root(args.dataset_dir, "testA")
+        if root is not None:
+            return model.test(args, D.directory_test_samples(args, D.DatasetCache(root, "testA", device=model.device, with_class=False))())
         return model.test(args, synthetic_test_samples(args)())
-    import os
     sink = SummarySink(os.path.join(getattr(args, "log_dir", "./logs"), "train", "scalars.jsonl"))
+    src = directory_sources(model, args)
+    if src is not None:
+        return model.train(args, src[0], test_samples=src[1], sink=sink)
     return model.train(args, synthetic_batches(model, args), test_samples=synthetic_test_samples(args), sink=sink)
 
 

@@ -229,6 +229,22 @@ class sggan(object):
             setattr(self, n, self._static_in[n])
         return fresh
 
+    def adopt_inputs(self, **buffers):
+        """Make caller-owned device tensors the recorded step's static inputs (``real_A=..., seg_A=..., mask_A=...``): a
+        loader that refills them in place (data.DirectoryBatches) then feeds a replayed step with no staging copy.  Images
+        must already be in the internal layout (channel-padded, network dtype), masks float32."""
+        names = self._INPUTS_CYCLE if self.cycle else self._INPUTS_REF
+        for n, t in buffers.items():
+            if n not in names:
+                raise KeyError(f"{n}: not an input of this step ({', '.join(names)})")
+            want = torch.float32 if n.startswith("mask") else self.dtype
+            if not (isinstance(t, torch.Tensor) and t.device.type == self.device.type and t.is_contiguous() and t.dtype == want
+                    and (n.startswith("mask") or t.shape[-1] % A.CPAD == 0)):
+                raise ValueError(f"{n}: a contiguous {want} device tensor in the step's internal layout is required")
+            self._static_in[n] = t
+        self._program = None
+        return self
+
     def _graph_step(self):
         if self.use_pool and not self.pool_static:
             raise NotImplementedError("graph replay with the dynamic image pool: its random swaps change the step's launch "
@@ -690,7 +706,7 @@ class sggan(object):
     def train(self, args, batches, log=print, test_samples=None, sink=None):
         """The reference's epoch loop (model.py:202-275) around ``train_step`` for a caller-supplied batch source:
         ``batches(epoch)`` yields dicts with real_A / seg_A / mask_A (+ real_B / seg_B / mask_B in cycle mode) --
-        disk loading and augmentation (utils.py:167-233) stay on the caller's side; ``test_samples`` / ``sink`` add the epoch-end
+        data.DirectoryBatches loads them from a dataset directory (utils.py:167-233), any other source is the caller's; ``test_samples`` / ``sink`` add the epoch-end
         test pass and the scalar summaries of model.py:263-268.  Prints the reference's line
         (model.py:260), keeps its running-mean loss metrics (model.py:23-24,193-194,270-271), honours
         --continue_train (model.py:210-215) and saves in ``finally`` like model.py:272-275."""
@@ -706,7 +722,9 @@ class sggan(object):
             for epoch in range(args.epoch):
                 self.gen_loss_metric = self.disc_loss_metric = 0.0
                 self._metric_n = 0
-                data = list(batches(epoch))
+                data = batches(epoch)
+                if not hasattr(data, "__len__"):       # a sized source (data.DirectoryBatches) refills its buffers per step: keep it lazy
+                    data = list(data)
                 for idx, b in enumerate(data):
                     for k, v in b.items():
                         setattr(self, k, v)
