@@ -366,6 +366,28 @@ int sgg_resample_u8(const uint8_t* src, int M, int H0, int W0, int Cs, const int
                     const float* row_w, const int32_t* row_start, int row_taps,
                     const float* col_w, const int32_t* col_start, int col_taps, int col_step,
                     void* out, int N, int H, int W, int C, int dtype, void* stream);
+/* ---- augmented training copy (utils.py:80-103,180-182; deviation D6): Fliplr, Crop and Affine in a drawn order on
+ * the squared image A = resize(src, (S, S)), S = H0, folded by the caller (sggan_amd/data.py: augment_matrices) into two 2x3
+ * float64 maps per sample, row major, 12 doubles: `fill` (output point -> the affine's input frame) then `full` (-> A):
+ *   p = (x + 0.5, y + 0.5);  out[n][y][x] = 0 where fill.p lies outside [0,S]x[0,S], else the bilinear sample (edge clamp) of
+ *   A at full.p - 0.5, with A[y][x][c] = ( sum_k col_w[x][k] * src[index[n]][y][col_start[x] + k][c] ) / 255, c < 3.
+ * Coordinates float64, each (m0*px + m1*py) + m2; f32 sums: taps ascending, then neighbours (y0,x0) (y0,x1) (y1,x0) (y1,x1).
+ *   src (M,S,W0,Cs) uint8, Cs = 3 or 4 (the 4th source channel is not read); index int32[N], matrices double[N][12],
+ *   col_w f32 [S][col_taps], col_start int32 [S] (band_table((W0, S))): all on the DEVICE, so the launch is the same every step;
+ *   win_rows x win_cols: the pixels of A one 16 x 64 output tile can touch (data.warp_window), staged in LDS; coordinates are
+ *   clamped to the window and the source, so wrong parameters give wrong pixels, not out-of-range accesses;
+ *   out (N,S,S,4) f32, channel 3 = 0.  No workspace, no atomics.  SGG_EUNSUPPORTED: the window exceeds 64 KB of LDS. */
+int sgg_warp_affine_u8(const uint8_t* src, int M, int S, int W0, int Cs, const int32_t* index, const double* matrices,
+                       const float* col_w, const int32_t* col_start, int col_taps, int win_rows, int win_cols,
+                       float* out, int N, void* stream);
+/* sgg_resample_u8's band resample over an f32 source (N,H0,W0,4) (the warp's output): sample n -> output sample n, values
+ * taken as they are (no / 255), the same summation order; c < C <= 4, channels C..SGG_CPAD-1 written as zeros.  Output sample
+ * n starts out_stride elements after sample n-1 (>= H*W*SGG_CPAD, a multiple of SGG_CPAD): the copies of a doubled batch are
+ * written between its plain samples.  SGG_EUNSUPPORTED: a tile's column window plus its weights exceed 64 KB of LDS. */
+int sgg_resample_f32(const float* src, int N, int H0, int W0, const int32_t* flip,
+                     const float* row_w, const int32_t* row_start, int row_taps,
+                     const float* col_w, const int32_t* col_start, int col_taps, int col_step,
+                     void* out, int64_t out_stride, int H, int W, int C, int dtype, void* stream);
 /* ---- evaluation (next-row SURVEY 8(f)4): metric._fast_hist (metric.py:18-24) and scores_seg_fake (metric.py:71-77), bit exact
  * hist[n_class*t + p] += 1 for pixels with 0 <= t,p < n_class (uint64 counts, caller zeroes);
  * labels[i] = argmax_c uint8(255*x[i][c]) over the first C_real channels (first maximum wins). */

@@ -172,6 +172,109 @@ __global__ __launch_bounds__(RS_CB) void resample_u8_kernel(const ResampleArgs a
     }
 }
 
+// The same band resample over an f32 source (N, H0, W0, 4) -- the warp's intermediate (warp.hip) -- for the augmented copy:
+// sample n of the source becomes sample n of the output, values are taken as they are (no / 255), and consecutive output
+// samples lie out_stride elements apart so that the copies can be written between the plain samples of a doubled batch.
+// Same tiling and the same summation order as resample_u8_kernel; a staged row is span float4 pixels, always aligned.
+struct ResampleF32Args {
+    const float4* src; int H0, W0;
+    const int32_t* flip;
+    const float* rw; const int32_t* rs; int TR;
+    const float* cw; const int32_t* cs; int TC;
+    void* out; int64_t out_stride; int N, H, W, C;
+    int rq;            // source rows per chunk
+    int span_cap;      // source pixels per staged row the LDS window holds
+    int wstride;       // columns per row of the LDS weight tile
+};
+
+template <typename T>
+__global__ __launch_bounds__(RS_CB) void resample_f32_kernel(const ResampleF32Args a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int t = threadIdx.x;
+    const int n = blockIdx.z;
+    const int i0 = blockIdx.y * RS_RB;
+    const int jt0 = blockIdx.x * RS_CB;
+    const int ncol = min(RS_CB, a.W - jt0);
+    const int nrow = min(RS_RB, a.H - i0);
+    const int TR = a.TR, TC = a.TC;
+    const bool flip = a.flip[n] != 0;
+
+    const bool active = t < ncol;
+    float* wl = reinterpret_cast<float*>(lds);                                                    // [TC][wstride]
+    float4* stage = reinterpret_cast<float4*>(lds + (size_t)TC * a.wstride * sizeof(float));      // [rq][span_cap]
+
+    const int x_lo = min(max(a.cs[jt0], 0), a.W0 - 1);
+    const int x_hi = min(a.cs[jt0 + ncol - 1] + TC, a.W0);
+    const int span = min(max(x_hi - x_lo, 1), a.span_cap);
+    const int jt = jt0 + min(t, ncol - 1);
+    const int px0 = min(max(a.cs[jt] - x_lo, 0), span - 1);
+    if (active)
+        for (int kc = 0; kc < TC; ++kc) wl[kc * a.wstride + t] = a.cw[(size_t)jt * TC + kc];
+
+    const int r_lo = min(max(a.rs[i0], 0), a.H0 - 1);
+    const int r_hi = min(a.rs[i0 + nrow - 1] + TR, a.H0);
+    int rs_i[RS_RB];
+#pragma unroll
+    for (int i = 0; i < RS_RB; ++i) rs_i[i] = a.rs[min(i0 + i, a.H - 1)];
+
+    float acc[RS_RB][4];
+#pragma unroll
+    for (int i = 0; i < RS_RB; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
+
+    const int64_t img_base = (int64_t)n * a.H0;
+    for (int rb = r_lo; rb < r_hi; rb += a.rq) {
+        const int nq = min(a.rq, r_hi - rb);
+        __syncthreads();
+        for (int e = t; e < nq * span; e += RS_CB) {
+            const int q = e / span, px = e - q * span;
+            stage[q * a.span_cap + px] = a.src[(img_base + rb + q) * a.W0 + x_lo + px];
+        }
+        __syncthreads();
+        float h[RS_RQ][4];
+#pragma unroll
+        for (int q = 0; q < RS_RQ; ++q)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) h[q][c] = 0.f;
+        for (int kc = 0; active && kc < TC; ++kc) {
+            const float w = wl[kc * a.wstride + t];
+            const int pb = min(px0 + kc, span - 1);
+#pragma unroll
+            for (int q = 0; q < RS_RQ; ++q) {
+                if (q < nq) {
+                    const float4 v = stage[q * a.span_cap + pb];
+                    h[q][0] = fmaf(w, v.x, h[q][0]);
+                    h[q][1] = fmaf(w, v.y, h[q][1]);
+                    h[q][2] = fmaf(w, v.z, h[q][2]);
+                    h[q][3] = fmaf(w, v.w, h[q][3]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RS_RQ; ++q) {
+            if (active && q < nq) {
+#pragma unroll
+                for (int i = 0; i < RS_RB; ++i) {
+                    const int k = rb + q - rs_i[i];
+                    if (i < nrow && k >= 0 && k < TR) {
+                        const float w = a.rw[(size_t)(i0 + i) * TR + k];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) acc[i][c] = fmaf(w, h[q][c], acc[i][c]);
+                    }
+                }
+            }
+        }
+    }
+    if (active) {
+        const int j = flip ? a.W - 1 - (jt0 + t) : jt0 + t;
+#pragma unroll
+        for (int i = 0; i < RS_RB; ++i)
+            if (i < nrow)
+                store_pixel<T>(reinterpret_cast<T*>(a.out) + (int64_t)n * a.out_stride + ((int64_t)(i0 + i) * a.W + j) * SGG_CPAD, acc[i], a.C);
+    }
+}
+
 }  // namespace
 
 extern "C" int sgg_resample_u8(const uint8_t* src, int M, int H0, int W0, int Cs, const int32_t* index, const int32_t* flip,
@@ -205,5 +308,35 @@ extern "C" int sgg_resample_u8(const uint8_t* src, int M, int H0, int W0, int Cs
         if (Cs == 3) hipLaunchKernelGGL((resample_u8_kernel<3, float>), grid, dim3(RS_CB), lds, s, a);
         else hipLaunchKernelGGL((resample_u8_kernel<4, float>), grid, dim3(RS_CB), lds, s, a);
     }
+    return sgg_check_launch();
+}
+
+extern "C" int sgg_resample_f32(const float* src, int N, int H0, int W0, const int32_t* flip,
+                                const float* row_w, const int32_t* row_start, int row_taps,
+                                const float* col_w, const int32_t* col_start, int col_taps, int col_step,
+                                void* out, int64_t out_stride, int H, int W, int C, int dtype, void* stream) {
+    if (!src || !flip || !row_w || !row_start || !col_w || !col_start || !out) return SGG_EINVAL;
+    if (N <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0 || C <= 0 || C > 4) return SGG_EINVAL;
+    if (row_taps <= 0 || row_taps > H0 || col_taps <= 0 || col_taps > W0 || col_step < 0) return SGG_EINVAL;
+    if (dtype != SGG_F32 && dtype != SGG_BF16) return SGG_EINVAL;
+    if (out_stride < (int64_t)H * W * SGG_CPAD || (out_stride % SGG_CPAD) != 0) return SGG_EINVAL;
+    if (((uintptr_t)out & 15) != 0 || ((uintptr_t)src & 15) != 0) return SGG_EINVAL;
+    if (N > 65535 || (H + RS_RB - 1) / RS_RB > 65535) return SGG_EUNSUPPORTED;
+    ResampleF32Args a;
+    a.src = reinterpret_cast<const float4*>(src); a.H0 = H0; a.W0 = W0; a.flip = flip;
+    a.rw = row_w; a.rs = row_start; a.TR = row_taps; a.cw = col_w; a.cs = col_start; a.TC = col_taps;
+    a.out = out; a.out_stride = out_stride; a.N = N; a.H = H; a.W = W; a.C = C;
+    const int64_t span = (int64_t)(std::min(W, RS_CB) - 1) * col_step + col_taps;
+    a.span_cap = (int)std::min<int64_t>(span, W0);
+    const int64_t seg = (int64_t)a.span_cap * (int64_t)sizeof(float4);
+    a.wstride = (std::min(W, RS_CB) + 63) / 64 * 64;
+    const int64_t wbytes = (int64_t)col_taps * a.wstride * sizeof(float);
+    if (wbytes + seg > RS_LDS) return SGG_EUNSUPPORTED;
+    a.rq = (int)std::min<int64_t>(RS_RQ, (RS_LDS - wbytes) / seg);
+    const size_t lds = (size_t)wbytes + (size_t)a.rq * seg;
+    dim3 grid((W + RS_CB - 1) / RS_CB, (H + RS_RB - 1) / RS_RB, N);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SGG_BF16) hipLaunchKernelGGL((resample_f32_kernel<bf16>), grid, dim3(RS_CB), lds, s, a);
+    else hipLaunchKernelGGL((resample_f32_kernel<float>), grid, dim3(RS_CB), lds, s, a);
     return sgg_check_launch();
 }

@@ -130,6 +130,142 @@ def apply_tables(x, rows, cols):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ augmented copy (host, NumPy)
+# The reference trains on every file twice: as loaded, and through DataAugmentation.augmentation_func (utils.py:80-103,
+# 180-182): iaa.Sequential([Fliplr(0.5), Crop(percent=(0.2, 0.4)), Affine(translate_percent +-0.1, rotate +-1 deg)],
+# random_order=True) on the squared image A = resize(src, (H0, H0)), S = H0.  imgaug is not a dependency and its RNG cannot
+# be reproduced, so the rule is restated (deviation D6).  Coordinates are continuous, pixel centres at +0.5;
+# every operation is its OUTPUT -> INPUT map g:
+#   op 0  Fliplr : coin set: (x, y) -> (S - x, y)
+#   op 1  Crop   : fractions top, right, bottom, left in [0.2, 0.4) -> whole pixels t, r, b, l = rint(f * S) (size is kept):
+#                  (x, y) -> (l + x * (S - l - r) / S, t + y * (S - t - b) / S)
+#   op 2  Affine : forward = rotate by `angle` about (S/2, S/2) (x' = c x - s y, y' = s x + c y), then translate by
+#                  (tx * S, ty * S); g is its inverse.  cval = 0: where g's result lies outside [0, S] x [0, S] the pixel is 0
+#                  on every channel (tested in the affine's own input frame).
+# `perm` lists the operations in the order they are applied to the image, so an output pixel p samples A at
+# g_perm[0](g_perm[1](g_perm[2](p))) -- with ONE bilinear interpolation (edge clamp) where imgaug interpolates per operation.
+AUG_FLIP, AUG_CROP, AUG_AFFINE = 0, 1, 2
+AUG_CROP_RANGE, AUG_TRANSLATE_RANGE, AUG_ROTATE_RANGE = (0.2, 0.4), (-0.1, 0.1), (-1.0, 1.0)
+
+
+def draw_augment_params(rng, n):
+    """The draws of n augmented copies from ``rng`` (a np.random.RandomState), per copy in this order: the permutation of the
+    three operations, the flip coin (random_sample() < 0.5), the crop fractions top, right, bottom, left, the translation
+    tx, ty, the angle in degrees, and the loader's own flip (random_sample() > 0.5, utils.py:201) -- 11 scalar draws after
+    the permutation.  -> dict of arrays with leading dimension n."""
+    p = {"perm": np.zeros((n, 3), np.int64), "flip": np.zeros(n, bool), "crop": np.zeros((n, 4)), "translate": np.zeros((n, 2)),
+         "angle": np.zeros(n), "loader_flip": np.zeros(n, bool)}
+    for i in range(n):
+        p["perm"][i] = rng.permutation(3)
+        p["flip"][i] = rng.random_sample() < 0.5
+        p["crop"][i] = [rng.uniform(*AUG_CROP_RANGE) for _ in range(4)]
+        p["translate"][i] = [rng.uniform(*AUG_TRANSLATE_RANGE) for _ in range(2)]
+        p["angle"][i] = rng.uniform(*AUG_ROTATE_RANGE)
+        p["loader_flip"][i] = rng.random_sample() > 0.5
+    return p
+
+
+def identity_augment_params(n):
+    """Parameters under which every operation is the identity map (tests, and the documentation of the dict's layout)."""
+    return {"perm": np.tile(np.arange(3), (n, 1)), "flip": np.zeros(n, bool), "crop": np.zeros((n, 4)),
+            "translate": np.zeros((n, 2)), "angle": np.zeros(n), "loader_flip": np.zeros(n, bool)}
+
+
+def _op_matrix(op, S, flip, crop, translate, angle):
+    """One operation's output -> input map as a 3x3 homogeneous float64 matrix."""
+    S = float(S)
+    if op == AUG_FLIP:
+        return np.array([[-1.0, 0.0, S], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]) if flip else np.eye(3)
+    if op == AUG_CROP:
+        t, r, b, l = (float(np.rint(f * S)) for f in crop)
+        return np.array([[(S - l - r) / S, 0.0, l], [0.0, (S - t - b) / S, t], [0.0, 0.0, 1.0]])
+    c, s = np.cos(np.deg2rad(angle)), np.sin(np.deg2rad(angle))
+    Rinv = np.array([[c, s], [-s, c]])                       # inverse of x' = c x - s y, y' = s x + c y
+    ctr = np.array([S / 2.0, S / 2.0])
+    M = np.eye(3)
+    M[:2, :2] = Rinv
+    M[:2, 2] = ctr - Rinv @ (np.array([translate[0] * S, translate[1] * S]) + ctr)
+    return M
+
+
+def augment_matrices(params, S):
+    """-> (n, 2, 2, 3) float64.  [:, 0] maps an output point to the affine operation's input frame (the zero-fill test),
+    [:, 1] maps it to the squared image A (the sample point).  Both are products of the per-operation maps in drawn order."""
+    n = len(params["angle"])
+    out = np.zeros((n, 2, 2, 3))
+    for i in range(n):
+        perm = [int(v) for v in params["perm"][i]]
+        g = [_op_matrix(op, S, params["flip"][i], params["crop"][i], params["translate"][i], params["angle"][i]) for op in perm]
+        k = perm.index(AUG_AFFINE)
+        fill = np.eye(3)
+        for m in g[k:]:
+            fill = fill @ m
+        full = np.eye(3)
+        for m in g:
+            full = full @ m
+        out[i, 0], out[i, 1] = fill[:2], full[:2]
+    return out
+
+
+def _augment_points(matrices, S):
+    """(inside (S, S) bool, sx, sy): the zero-fill decision and the sample point of every output pixel centre, each
+    coordinate as (m0 * px + m1 * py) + m2 in that order -- the arithmetic sgg_warp_affine_u8 repeats."""
+    assert np.shape(matrices) == (2, 2, 3)
+    py, px = np.meshgrid(np.arange(S) + 0.5, np.arange(S) + 0.5, indexing="ij")
+    (fx, fy), (sx, sy) = [[(m[r, 0] * px + m[r, 1] * py) + m[r, 2] for r in range(2)] for m in np.asarray(matrices, np.float64)]
+    return (fx >= 0.0) & (fx <= S) & (fy >= 0.0) & (fy <= S), sx, sy
+
+
+def augment_inside(matrices, S):
+    """(S, S) bool: False where the affine operation's zero fill applies, decided exactly as the kernel decides it."""
+    return _augment_points(matrices, S)[0]
+
+
+def apply_augment(A, matrices):
+    """The warp of ONE sample, float64: A (S, S, C) float, matrices (2, 2, 3) from augment_matrices -> (S, S, C).  Every
+    coordinate is (m0 * px + m1 * py) + m2 in that order with (px, py) = (x + 0.5, y + 0.5), which is what the kernel
+    evaluates (sgg_warp_affine_u8), so both make the same zero-fill and floor decisions."""
+    A = np.asarray(A, dtype=np.float64)
+    S = A.shape[0]
+    assert A.shape[1] == S
+    inside, sx_, sy_ = _augment_points(matrices, S)
+    u, v = sx_ - 0.5, sy_ - 0.5
+    x0, y0 = np.floor(u), np.floor(v)
+    wx, wy = u - x0, v - y0
+    x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+    xa, xb = np.clip(x0, 0, S - 1), np.clip(x0 + 1, 0, S - 1)
+    ya, yb = np.clip(y0, 0, S - 1), np.clip(y0 + 1, 0, S - 1)
+    e = (Ellipsis, None)
+    out = (((1.0 - wy) * (1.0 - wx))[e] * A[ya, xa] + ((1.0 - wy) * wx)[e] * A[ya, xb]
+           + (wy * (1.0 - wx))[e] * A[yb, xa] + (wy * wx)[e] * A[yb, xb])
+    return np.where(inside[e], out, 0.0)
+
+
+def interleave(plain, copies):
+    """Per-sample values of the plain samples and of their copies -> row order of the doubled batch [s0, aug(s0), s1, ...]."""
+    return np.stack([np.asarray(plain), np.asarray(copies)], axis=1).reshape(-1)
+
+
+def warp_window(matrices, tile=(16, 64)):
+    """(rows, cols) of A that one tile of tile = (rows, cols) output pixels can touch under any of the (n, 2, 2, 3) matrices:
+    the maps are affine, so the extent is the same for every tile; + 4: the second bilinear neighbour, the two floors, one pixel of slack."""
+    m = np.abs(np.asarray(matrices, np.float64).reshape(-1, 2, 2, 3)[:, 1])
+    th, tw = tile
+    cols = int(np.ceil((m[:, 0, 0] * (tw - 1) + m[:, 0, 1] * (th - 1)).max())) + 4
+    rows = int(np.ceil((m[:, 1, 0] * (tw - 1) + m[:, 1, 1] * (th - 1)).max())) + 4
+    return rows, cols
+
+
+def warp_window_bound(S, tile=(16, 64)):
+    """warp_window's largest value over the parameter ranges, so that the warp's launch (LDS size included) is the same at
+    every step of every epoch: the linear part of the composed map is a flip, a crop scale and a rotation in some order, every
+    entry at most scale * cos / scale * sin in size, with scale <= 1 - 2 * rint(0.2 S) / S <= 0.6 + 1 / S and |angle| <= 1 deg."""
+    th, tw = tile
+    scale = 1.0 - 2.0 * np.rint(AUG_CROP_RANGE[0] * S) / S
+    c, s = np.cos(np.deg2rad(AUG_ROTATE_RANGE[1])), np.sin(np.deg2rad(AUG_ROTATE_RANGE[1]))
+    return int(np.ceil(scale * (c * (th - 1) + s * (tw - 1)))) + 4, int(np.ceil(scale * (c * (tw - 1) + s * (th - 1)))) + 4
+
+
 # ------------------------------------------------------------------------------------------------ files
 def sibling(path, split, suffix):
     """The reference's rule (utils.py:169-170, 121, 146): ``image_path.replace("trainA", "trainA_seg")`` on the whole path."""
@@ -228,22 +364,29 @@ def mask_grid(model, H, W):
 class _Domain:
     """One domain's cache + the persistent batch buffers it fills."""
 
-    def __init__(self, model, args, cache, tag):
+    def __init__(self, model, args, cache, tag, augment=False):
         import torch
         from . import kernels as K
         from .segment_class import one_hot_mask
-        self.cache, self.tag = cache, tag
-        N, H, W = args.batch_size, args.image_height, args.image_width
+        self.cache, self.tag, self.augment = cache, tag, bool(augment)
+        H, W = args.image_height, args.image_width
+        N = args.batch_size * (2 if self.augment else 1)          # augmented: [s0, aug(s0), s1, aug(s1), ...] (model.py:236-244)
         dev = cache.device
         self.C = args.input_nc
-        self.tables = {}
+        if self.augment and self.C > 3:
+            raise ValueError("augment: the warp carries three channels (the reference's RGB image and colour label)")
+        self.tables, self.aug_tables = {}, {}
         for key in {k for k, _ in cache.image} | {k for k, _ in cache.label}:
             H0, W0 = key[1], key[2]
             if (H0, W0) not in self.tables:
                 self.tables[(H0, W0)] = _device_tables(train_tables(H0, W0, H, W), dev)
+                if self.augment:      # the chain cut at the squared image: columns W0 -> H0 (warp), then (H0, H0) -> (H, W)
+                    self.aug_tables[(H0, W0)] = _device_tables((band_table((W0, H0)), band_table((H0, H)), band_table((H0, W))), dev)
             if key[3] < self.C:
                 raise ValueError(f"{cache.root}: {key[3]}-channel sources cannot fill input_nc={self.C}")
         self.real = torch.zeros((N, H, W, K.cpad(self.C)), dtype=model.dtype, device=dev)
+        # augmented: the plain samples are resampled densely (the same launches as without augmentation) and copied to the even rows
+        self._plain_tmp = torch.empty((args.batch_size, H, W, K.cpad(self.C)), dtype=model.dtype, device=dev) if self.augment else None
         self.seg = torch.zeros_like(self.real)
         mh, mw = mask_grid(model, H, W)
         nc = args.segment_class
@@ -263,15 +406,29 @@ class _Domain:
     def buffers(self):
         return {"real_" + self.tag: self.real, "seg_" + self.tag: self.seg, "mask_" + self.tag: self.mask}
 
-    def plan(self, order):
-        """Host part of an epoch: per-sample stack indices of the chosen files, uploaded once per epoch."""
+    def plan(self, order, aug=None):
+        """Host part of an epoch: per-sample stack indices of the chosen files, uploaded once per epoch.  ``aug``: the
+        parameters of the samples' augmented copies (draw_augment_params) -> their matrices per source, the LDS window of the
+        warp (its bound over the parameter ranges, not the drawn values), and every file twice for the doubled batch's masks."""
         import torch
         c = self.cache
         dev = c.device
         img = np.array([c.image[f][1] for f in order], dtype=np.int32)
         lab = np.array([c.label[f][1] for f in order], dtype=np.int32)
-        return {"order": list(order), "img": torch.as_tensor(img).to(dev), "lab": torch.as_tensor(lab).to(dev),
-                "file": torch.as_tensor(np.asarray(order, dtype=np.int32)).to(dev)}
+        p = {"order": list(order), "img": torch.as_tensor(img).to(dev), "lab": torch.as_tensor(lab).to(dev),
+             "file": torch.as_tensor(np.asarray(order, dtype=np.int32)).to(dev)}
+        if aug is not None:
+            one = lambda i: {k: v[i:i + 1] for k, v in aug.items()}
+            for role, where in (("img", c.image), ("lab", c.label)):       # the squared side S = H0 of each sample's own source
+                m = np.concatenate([augment_matrices(one(i), where[f][0][1]) for i, f in enumerate(order)]) if len(order) else np.zeros((0, 2, 2, 3))
+                p[role + "_mats"] = torch.as_tensor(m).to(dev)
+                win = (1, 1)
+                for S in {where[f][0][1] for f in order}:                  # constant per source height, whatever was drawn
+                    win = tuple(max(a, b) for a, b in zip(win, warp_window_bound(S)))
+                assert not len(order) or all(a <= b for a, b in zip(warp_window(m), win))
+                p[role + "_win"] = win
+            p["file2"] = torch.as_tensor(np.repeat(np.asarray(order, dtype=np.int32), 2)).to(dev)
+        return p
 
     def _resample(self, where, plan_idx, order, lo, hi, flips, out):
         """Runs of consecutive samples that share a source stack -> one launch each (one launch when shapes are uniform)."""
@@ -293,6 +450,32 @@ class _Domain:
         self._resample(c.label, plan["lab"], plan["order"], lo, hi, flips, self.seg)
         torch.index_select(self.mask_table, 0, plan["file"][lo:hi], out=self._mask_tmp)
         torch.where(flips_bool[lo:hi].view(-1, 1, 1, 1), self._mask_tmp.flip(2), self._mask_tmp, out=self.mask)
+
+
+    def fill_augmented(self, plan, lo, hi, flips, aug_flips, flips2_bool, inter):
+        """The doubled batch: plain sample i -> row 2i (fill's own launches into a dense temporary, then one strided copy: the
+        same bits), its copy -> row 2i + 1 through warp + resample_f32; masks are the per-file masks, not warped (the
+        reference augments image and label only), each with its own row's flip."""
+        import torch
+        from . import kernels as K
+        c, order, n = self.cache, plan["order"], hi - lo
+        for where, role, out in ((c.image, "img", self.real), (c.label, "lab", self.seg)):
+            idx, mats, win = plan[role], plan[role + "_mats"], plan[role + "_win"]
+            self._resample(where, idx, order, lo, hi, flips, self._plain_tmp)
+            out[0::2].copy_(self._plain_tmp)
+            a = lo
+            while a < hi:
+                key = where[order[a]][0]
+                b = a + 1
+                while b < hi and where[order[b]][0] == key:
+                    b += 1
+                square, arows, acols = self.aug_tables[(key[1], key[2])]
+                tmp = inter(key[1], n)[:b - a]
+                K.warp_affine_u8(c.stacks[key], idx[a:b], mats[a:b], square, win, tmp)
+                K.resample_f32(tmp, aug_flips[a:b], arows, acols, out[2 * (a - lo) + 1::2][:b - a], self.C)
+                a = b
+        torch.index_select(self.mask_table, 0, plan["file2"][2 * lo:2 * hi], out=self._mask_tmp)
+        torch.where(flips2_bool[2 * lo:2 * hi].view(-1, 1, 1, 1), self._mask_tmp.flip(2), self._mask_tmp, out=self.mask)
 
 
 class _Epoch:
@@ -317,16 +500,27 @@ class DirectoryBatches:
     then domain B), ``min(len, train_size) // batch_size`` batches are cut from its head, and every sample takes one
     ``rng.random_sample() > 0.5`` flip draw in batch order (cycle mode: one draw per A/B pair, applied to both, as upstream
     SG-GAN's paired loader does).  ``rng`` is a ``np.random.RandomState`` (default seed 19; the reference leaves NumPy unseeded).
-    With ``model.use_graph`` the buffers become the recorded step's static inputs, so a replayed step reads them directly."""
+    With ``model.use_graph`` the buffers become the recorded step's static inputs, so a replayed step reads them directly.
 
-    def __init__(self, model, args, cache_A, cache_B=None, rng=None):
+    ``augment=True`` (the reference's default --use_augmentation branch, model.py:234-244): every sample is followed by its
+    augmented copy, so the buffers hold ``2 * batch_size`` samples ``[s0, aug(s0), s1, aug(s1), ...]`` and the number of steps
+    is unchanged.  Everything about the copies is drawn from a SECOND stream ``aug_rng`` (default seed 23) after the epoch's
+    ``rng`` draws -- draw_augment_params for domain A's copies, then for domain B's -- so ``rng`` and with it the plain samples
+    are what they are without augmentation.  A copy's loader flip is its own draw (cycle mode: domain A's draw serves the A/B
+    pair, domain B's is drawn and unused)."""
+
+    def __init__(self, model, args, cache_A, cache_B=None, rng=None, augment=False, aug_rng=None):
         import torch
         self.model, self.args = model, args
         self.rng = rng if rng is not None else np.random.RandomState(19)
+        self.augment = bool(augment)
+        self.aug_rng = aug_rng if aug_rng is not None else np.random.RandomState(23)
         self.cycle = bool(getattr(args, "cycle", False))
         if self.cycle and cache_B is None:
             raise ValueError("cycle mode needs a second domain (cache_B)")
-        self.domains = [_Domain(model, args, cache_A, "A")] + ([_Domain(model, args, cache_B, "B")] if self.cycle else [])
+        self.domains = [_Domain(model, args, cache_A, "A", self.augment)] + \
+                       ([_Domain(model, args, cache_B, "B", self.augment)] if self.cycle else [])
+        self._inter = {}                      # the warp's f32 intermediates (batch_size, S, S, 4), one per source height
         self.batch = {}
         for d in self.domains:
             self.batch.update(d.buffers())
@@ -335,8 +529,17 @@ class DirectoryBatches:
         if getattr(model, "use_graph", False):
             model.adopt_inputs(**self.batch)
 
+    def intermediate(self, S, n):
+        """The warp's output buffer for n samples of side S: allocated once, shared by images, labels and both domains (one
+        stream: a launch is done with it before the next one writes it)."""
+        t = self._inter.get(S)
+        if t is None or t.shape[0] < n:
+            t = self._inter[S] = self._torch.empty((n, S, S, 4), dtype=self._torch.float32, device=self.device)
+        return t
+
     def epoch_plan(self):
-        """The host-side draws of one epoch: ([file order per domain], flips (n_batches * batch_size,) bool, n_batches)."""
+        """The host-side draws of one epoch from ``rng``: ([file order per domain], flips (n_batches * batch_size,) bool,
+        n_batches) -- the same with and without augmentation."""
         a = self.args
         orders = []
         for d in self.domains:
@@ -347,8 +550,21 @@ class DirectoryBatches:
         flips = np.array([self.rng.random_sample() > 0.5 for _ in range(n_batches * a.batch_size)], dtype=bool)
         return [o[:n_batches * a.batch_size] for o in orders], flips, n_batches
 
+    def augment_plan(self, orders):
+        """The copies' draws of one epoch from ``aug_rng``, made after epoch_plan's: [draw_augment_params dict per domain],
+        domain A's first, one set of parameters per sample of ``orders``."""
+        return [draw_augment_params(self.aug_rng, len(o)) for o in orders]
+
     def __call__(self, epoch):
         torch = self._torch
+        if self.augment:
+            orders, flips, n = self.epoch_plan()
+            aug = self.augment_plan(orders)
+            plans = [d.plan(o, g) for d, o, g in zip(self.domains, orders, aug)]
+            aug_flips = aug[0]["loader_flip"]                              # one loader flip per A/B pair
+            both = interleave(flips, aug_flips)
+            up = lambda x: torch.as_tensor(x.astype(np.int32)).to(self.device)
+            return _Epoch(self, plans, (up(flips), up(aug_flips), up(both) != 0), n)
         orders, flips, n = self.epoch_plan()
         plans = [d.plan(o) for d, o in zip(self.domains, orders)]
         f32 = torch.as_tensor(flips.astype(np.int32)).to(self.device)
@@ -357,7 +573,10 @@ class DirectoryBatches:
     def _fill(self, plans, flips, b):
         N = self.args.batch_size
         for d, p in zip(self.domains, plans):
-            d.fill(p, b * N, (b + 1) * N, flips[0], flips[1])
+            if self.augment:
+                d.fill_augmented(p, b * N, (b + 1) * N, flips[0], flips[1], flips[2], self.intermediate)
+            else:
+                d.fill(p, b * N, (b + 1) * N, flips[0], flips[1])
         return self.batch
 
 

@@ -733,6 +733,38 @@ def resample_u8(src_u8, index, flip, rows, cols, out, C):
     return out
 
 
+def warp_affine_u8(src_u8, index, matrices, cols, window, out):
+    """The augmented copy's warp (sgg_warp_affine_u8): src_u8 (M,S,W0,3|4) uint8; index int32 (N,), matrices float64 (N,2,2,3)
+    (data.augment_matrices), cols = device band table of the squaring stage (data.band_table((W0, S))); window = (rows, cols)
+    of data.warp_window; out (N,S,S,4) f32, written in full."""
+    M, S, W0, Cs = src_u8.shape
+    N = out.shape[0]
+    cw, cs, _ = cols
+    assert src_u8.dtype == torch.uint8 and index.dtype == cs.dtype == torch.int32 and index.numel() == N
+    assert matrices.dtype == torch.float64 and tuple(matrices.shape) == (N, 2, 2, 3)
+    assert cw.dtype == out.dtype == torch.float32 and tuple(out.shape) == (N, S, S, 4) and tuple(cw.shape) == (S, cw.shape[1]) and cs.numel() == S
+    A.check(A.lib().sgg_warp_affine_u8(_p(src_u8), M, S, W0, Cs, _p(index), _p(matrices), _p(cw), _p(cs), cw.shape[1],
+                                       int(window[0]), int(window[1]), _p(out), N, _s()), "warp_affine_u8")
+    return out
+
+
+def resample_f32(src, flip, rows, cols, out, C):
+    """resample_u8 over an f32 source (N,H0,W0,4) (sgg_resample_f32): source sample n -> out[n].  ``out`` (N,H,W,cpad) bf16 /
+    f32 may be a view with a sample stride (``buf[1::2]``: the copies' rows of a doubled batch), dense within a sample."""
+    N, H0, W0, c4 = src.shape
+    No, H, W, Cp = out.shape
+    (rw, rs, _), (cw, cs, cstep) = rows, cols
+    assert src.dtype == torch.float32 and c4 == 4 and src.is_contiguous() and flip.dtype == rs.dtype == cs.dtype == torch.int32
+    assert rw.dtype == cw.dtype == torch.float32 and Cp == A.CPAD and No == N and flip.numel() == N and out.is_cuda
+    assert tuple(rw.shape) == (H, rw.shape[1]) and tuple(cw.shape) == (W, cw.shape[1]) and rs.numel() == H and cs.numel() == W
+    assert tuple(out.stride()[1:]) == (W * Cp, Cp, 1) and (N == 1 or out.stride(0) >= H * W * Cp)
+    stride = out.stride(0) if N > 1 else H * W * Cp
+    out_p = _p(out[0])                      # the first sample's address: the view as a whole need not be contiguous
+    A.check(A.lib().sgg_resample_f32(_p(src), N, H0, W0, _p(flip), _p(rw), _p(rs), rw.shape[1], _p(cw), _p(cs), cw.shape[1],
+                                     int(cstep), out_p, stride, H, W, int(C), dt(out), _s()), "resample_f32")
+    return out
+
+
 def pad_channels(x_f32, Cd, dtype, out=None):
     Cs = x_f32.shape[-1]
     out = _out(out, tuple(x_f32.shape[:-1]) + (Cd,), dtype, x_f32.device)

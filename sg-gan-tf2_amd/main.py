@@ -55,6 +55,9 @@ def build_parser():
       help="activation checkpointing: re-run each residual block in backward instead of keeping its activations")
     a("--dataset_dir_B", dest="dataset_dir_B", default=None,
       help="cycle mode: dataset root of domain B (its trainB* folders, else its trainA*); default: trainB* of --dataset_dir")
+    a("--augment", dest="augment", action="store_true",
+      help="train on every sample and its augmented copy (flip / crop / affine, 2 x batch_size images per step): the reference's "
+           "default --use_augmentation branch; that flag is type=bool and cannot be switched off, so it stays inert")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 
@@ -111,9 +114,10 @@ def directory_sources(model, args, log=print):
     root = D.resolve_root(args.dataset_dir)
     if root is None:
         return None
-    if args.use_augmentation:
-        log(" [*] --use_augmentation: the imgaug crop / affine branch (utils.py:55-103) is not built; "
-            "the loader's random flip is (DESIGN.md 11)")
+    augment = bool(getattr(args, "augment", False))
+    if args.use_augmentation and not augment:
+        log(" [*] --use_augmentation is inert here: pass --augment to train on every sample plus its augmented copy "
+            "(flip / crop / affine of utils.py:80-103, 2 x batch_size images per step; DESIGN.md 11)")
     dev = model.device
     cache_A = D.DatasetCache(root, "trainA", device=dev, max_files=args.train_size)
     cache_B = None
@@ -125,7 +129,7 @@ def directory_sources(model, args, log=print):
         if root_B is None or (not args.dataset_dir_B and split_B == "trainA"):
             raise FileNotFoundError("--cycle needs a second domain: trainB* under --dataset_dir, or --dataset_dir_B")
         cache_B = D.DatasetCache(root_B, split_B, device=dev, max_files=args.train_size)
-    batches = D.DirectoryBatches(model, args, cache_A, cache_B)
+    batches = D.DirectoryBatches(model, args, cache_A, cache_B, augment=augment)
     tests = None
     if os.path.isdir(os.path.join(root, "testA")):
         tests = D.directory_test_samples(args, D.DatasetCache(root, "testA", device=dev, with_class=False))
@@ -153,6 +157,8 @@ def main(argv=None):
     src = directory_sources(model, args)
     if src is not None:
         return model.train(args, src[0], test_samples=src[1], sink=sink)
+    if getattr(args, "augment", False):
+        print(" [*] --augment has no effect on the synthetic batches (--dataset_dir names no folder with trainA)")
     return model.train(args, synthetic_batches(model, args), test_samples=synthetic_test_samples(args), sink=sink)
 
 

@@ -8,6 +8,11 @@ clock.  Requires (b) >= 0.98 x (a) (exit status 1 otherwise).  Also times the lo
 
     python tools/bench_data.py [--blocks 6] [--steps 10] [--samples 100] [--out profiles/data_pipeline.txt]
     python tools/bench_data.py --fills 20        # loader only: the run to put under rocprofv3 --kernel-trace --stats
+    python tools/bench_data.py --augment --batch 4 [--out profiles/data_pipeline_augment.txt]
+
+--augment: the loader yields every sample plus its augmented copy (DirectoryBatches(augment=True): sgg_warp_affine_u8 +
+sgg_resample_f32 per copy), so --batch 4 feeds the step the usual 8 images per domain.  The ratio (b) / (a) is reported, not
+required: its yardstick is the plain loader's ratio from a run without --augment in the same session.
 
 The 100-sample cache replicates the Cityscapes fixture crops (tests/golden/city_small, 1024x512) 2 x 2 into full 2048x1024
 sources, so every sample costs the bytes a Cityscapes file does.
@@ -33,6 +38,7 @@ def main():
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--fills", type=int, default=0, help="loader only: this many fills, no training step")
+    ap.add_argument("--augment", action="store_true", help="doubled batches: every sample plus its augmented copy")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
@@ -52,7 +58,8 @@ def main():
     args = sggan_amd.default_args(dtype="bf16", device=dev, image_height=a.height, image_width=a.width, batch_size=a.batch,
                                   cycle=True, graph=True, train_size=10 ** 8)
     model = sggan_amd.sggan(args)
-    batches = D.DirectoryBatches(model, args, cache_A, cache_B)
+    batches = D.DirectoryBatches(model, args, cache_A, cache_B, augment=a.augment)
+    per_step = a.batch * (2 if a.augment else 1)              # images per domain the step sees
 
     def stream():
         ep = 0
@@ -62,10 +69,13 @@ def main():
             ep += 1
     fresh = stream()
     src_bytes = sum(int(np.prod(k[1:])) for d in batches.domains for k in (d.cache.image[0][0], d.cache.label[0][0])) * a.batch
-    out_bytes = 4 * a.batch * a.height * a.width * 8 * 2
+    out_bytes = 4 * per_step * a.height * a.width * 8 * 2
+    if a.augment:       # a copy reads its source again and writes + reads the f32 (S, S, 4) intermediate
+        inter = sum(16 * k[1] * k[1] for d in batches.domains for k in (d.cache.image[0][0], d.cache.label[0][0])) * a.batch
+        src_bytes = 2 * src_bytes + 2 * inter
     lines = []
     say = lambda s: (print(s, flush=True), lines.append(s))
-    say(f"bench_data: cycle step bf16 {a.width}x{a.height} batch {a.batch}, graph replay; cache {a.samples} samples/domain of "
+    say(f"bench_data: cycle step bf16 {a.width}x{a.height} batch {a.batch}{' + augmented copies (step batch %d)' % per_step if a.augment else ''}, graph replay; cache {a.samples} samples/domain of "
         f"{imgs[0].shape[1]}x{imgs[0].shape[0]}; loader reads {src_bytes / 1e6:.1f} MB and writes {out_bytes / 1e6:.1f} MB per step")
 
     # loader alone
@@ -104,13 +114,13 @@ def main():
                 times[mode].append((time.perf_counter() - t0) / a.steps)
         gl, dl = model.losses()
         assert np.isfinite(gl) and np.isfinite(dl)
-        ips = {m: a.batch / statistics.median(v) for m, v in times.items()}
+        ips = {m: per_step / statistics.median(v) for m, v in times.items()}
         for m, what in (("a", "inputs staged once"), ("b", "fresh batch every step")):
             say(f"({m}) {what}: {ips[m]:.1f} images/s  (median of {a.blocks} blocks of {a.steps} steps; ms/step per block: "
                 + " ".join(f"{1e3 * t:.3f}" for t in times[m]) + ")")
         ratio = ips["b"] / ips["a"]
-        say(f"(b) / (a) = {ratio:.4f}  (required >= 0.98)")
-        result.update({"a_images_per_sec": ips["a"], "b_images_per_sec": ips["b"], "ratio": ratio, "pass": ratio >= 0.98})
+        say(f"(b) / (a) = {ratio:.4f}  " + ("(reported; compare with the plain loader's ratio of the same session)" if a.augment else "(required >= 0.98)"))
+        result.update({"a_images_per_sec": ips["a"], "b_images_per_sec": ips["b"], "ratio": ratio, "pass": a.augment or ratio >= 0.98})
     print(json.dumps(result))
     if a.out:
         with open(os.path.join(ROOT, a.out) if not os.path.isabs(a.out) else a.out, "a") as f:
