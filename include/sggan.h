@@ -288,6 +288,21 @@ int sgg_instnorm_bwd_pair(const void* dy, const void* x, const float* gamma, con
                           int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak, int dtype,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* The skip-before-activation norm of two networks in lockstep (the U-Net generators of the cycle step): arguments as
+ * sgg_instnorm_*_skip plus the second network's parameter set, picked by image index as in sgg_instnorm_*_pair.  Workspace and
+ * stats layout are those of the single forms; per image the arithmetic and summation order are theirs too, so each half of
+ * the stacked result is bit for bit what sgg_instnorm_*_skip gives on that half alone. */
+int sgg_instnorm_fwd_skip_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
+                               const void* skip, void* y, float* stats, int N, int64_t HW, int C, float eps, int act, float leak,
+                               int dtype, void* ws, size_t ws_bytes, void* stream);
+int sgg_instnorm_fwd_skip_partial_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
+                                       const void* skip, void* y, float* stats, const float* partial, int chunks, int N, int64_t HW, int C,
+                                       float eps, int act, float leak, int dtype, void* stream);
+int sgg_instnorm_bwd_skip_pair(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* gamma2,
+                               const float* beta2, int nsplit, const float* stats, void* dx, void* dskip, float* dgamma, float* dbeta,
+                               float* dgamma2, float* dbeta2, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
+                               int dtype, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- lrelu / relu / tanh: tf.keras.layers.LeakyReLU / Activation ---- module.py:213,265,285 (ops.py:36-37) */
 int sgg_act_fwd(const void* x, void* y, int64_t n, int act, float leak, int dtype, void* stream);
 /* dx = dy * act'(.) evaluated from the OUTPUT y (relu/lrelu: sign of y; tanh: 1-y^2). */

@@ -93,6 +93,10 @@ SIGNATURES = {
     "sgg_instnorm_fwd_skip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _i, _f, _i, _vp, _sz, _vp]),
     "sgg_instnorm_fwd_skip_partial": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _f, _i, _f, _i, _vp]),
     "sgg_instnorm_bwd_skip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
+    "sgg_instnorm_fwd_skip_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _f, _i, _f, _i, _vp, _sz, _vp]),
+    "sgg_instnorm_fwd_skip_partial_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _f, _i, _f, _i, _vp]),
+    "sgg_instnorm_bwd_skip_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _f, _i,
+                                        _vp, _sz, _vp]),
     "sgg_act_fwd": (_i, [_vp, _vp, _i64, _i, _f, _i, _vp]),
     "sgg_act_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _f, _i, _vp]),
     "sgg_add": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),

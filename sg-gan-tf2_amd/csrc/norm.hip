@@ -429,10 +429,11 @@ __global__ void in_param_grad_kernel(InParamGrad g, int C, InSplit sp) { in_para
 template <typename T>
 __global__ __launch_bounds__(256) void in_apply_skip_kernel(const char* x, const char* skip, const float* gamma, const float* beta,
                                                             const float* stats, char* out, int64_t HW, int C, int rows_per_block,
-                                                            int act, float leak) {
+                                                            int act, float leak, InSplit sp) {
     constexpr int VEC = ET<T>::VEC;
     const int CV = C / VEC;
     const int n = blockIdx.y;
+    if (n >= sp.nsplit) { gamma = sp.gamma2; beta = sp.beta2; }      // the second network's images (block-uniform)
     const int64_t p0 = (int64_t)blockIdx.x * rows_per_block;
     const int64_t p1 = p0 + rows_per_block < HW ? p0 + rows_per_block : HW;
     for (int cvb = 0; cvb < CV; cvb += 256) {
@@ -757,17 +758,20 @@ int sgg_instnorm_bwd_pair(const void* dy, const void* x, const float* gamma, con
     return instnorm_bwd_impl(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream, sp);
 }
 
-// ---- skip added before the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip)
+// ---- skip added before the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip).  One network (in_nosplit())
+// or two in lockstep on a stacked batch (the _pair entry points): the statistics passes and the backward's dz pass never read
+// the affine parameters, so only the two apply kernels and the parameter-gradient sums pick a set by image index.
 static int instnorm_fwd_skip_apply(const void* x, const float* gamma, const float* beta, const void* skip, void* y, const float* stats,
-                                   int N, int64_t HW, int C, int act, float leak, int dtype, hipStream_t s) {
+                                   int N, int64_t HW, int C, int act, float leak, int dtype, hipStream_t s, InSplit sp) {
     const int rpb = in_rows_per_block(N, HW, C, 0);
     const dim3 ga((unsigned)((HW + rpb - 1) / rpb), N);
-    if (dtype == SGG_BF16) hipLaunchKernelGGL(in_apply_skip_kernel<bf16>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak);
-    else hipLaunchKernelGGL(in_apply_skip_kernel<float>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak);
+    if (dtype == SGG_BF16) hipLaunchKernelGGL(in_apply_skip_kernel<bf16>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak, sp);
+    else hipLaunchKernelGGL(in_apply_skip_kernel<float>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak, sp);
     return sgg_check_launch();
 }
-int sgg_instnorm_fwd_skip(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
-                          int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+static int instnorm_fwd_skip_impl(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                                  int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream,
+                                  InSplit sp) {
     if (!x || !gamma || !beta || !skip || !y || !stats || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
     if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
     if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
@@ -776,25 +780,24 @@ int sgg_instnorm_fwd_skip(const void* x, const float* gamma, const float* beta, 
     const int chunks = in_chunks(HW);
     float* partial = (float*)ws;
     const dim3 gp(chunks, N);
-    const InSplit sp = in_nosplit();
     if (dtype == SGG_BF16) hipLaunchKernelGGL((in_partial_kernel<bf16, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
     else hipLaunchKernelGGL((in_partial_kernel<float, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
     hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s);
+    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s, sp);
 }
-int sgg_instnorm_fwd_skip_partial(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
-                                  const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
-                                  void* stream) {
+static int instnorm_fwd_skip_partial_impl(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                                          const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
+                                          void* stream, InSplit sp) {
     if (!x || !gamma || !beta || !skip || !y || !stats || !partial || chunks <= 0 || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
     if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
     if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s);
+    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s, sp);
 }
-int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
-                          void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
-                          int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+static int instnorm_bwd_skip_impl(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
+                                  void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
+                                  int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream, InSplit sp) {
     if (!dy || !y || !x || !gamma || !beta || !stats || !dx || !dskip || !dgamma || !dbeta || N <= 0 || HW <= 0 || C <= 0 ||
         C % SGG_CPAD || C_real <= 0 || C_real > C) return SGG_EINVAL;
     if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
@@ -809,7 +812,6 @@ int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const fl
     const int rpb = in_rows_per_block(N, HW, C, 0);
     const dim3 gp(chunks, N), ga((unsigned)((HW + rpb - 1) / rpb), N);
     const InParamGrad pg{tot, dgamma, dbeta, N, C_real, accumulate};
-    const InSplit sp = in_nosplit();
     if (dtype == SGG_BF16) {
         hipLaunchKernelGGL(in_skip_bwd_partial_kernel<bf16>, gp, dim3(256), 0, s, (const char*)x, (const char*)dy, (const char*)y, stats, (char*)dskip, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak);
         hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
@@ -820,6 +822,45 @@ int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const fl
         hipLaunchKernelGGL((in_apply_kernel<float, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dskip, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, (int)SGG_ACT_NONE, 0.f, pg, sp);
     }
     return sgg_check_launch();
+}
+int sgg_instnorm_fwd_skip(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                          int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    return instnorm_fwd_skip_impl(x, gamma, beta, skip, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream, in_nosplit());
+}
+int sgg_instnorm_fwd_skip_partial(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
+                                  const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
+                                  void* stream) {
+    return instnorm_fwd_skip_partial_impl(x, gamma, beta, skip, y, stats, partial, chunks, N, HW, C, eps, act, leak, dtype, stream, in_nosplit());
+}
+int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
+                          void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
+                          int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    return instnorm_bwd_skip_impl(dy, y, x, gamma, beta, stats, dx, dskip, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype,
+                                  ws, ws_bytes, stream, in_nosplit());
+}
+// the lockstep forms: images 0..nsplit-1 use (gamma, beta) and add into (dgamma, dbeta), the rest the second set
+int sgg_instnorm_fwd_skip_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
+                               const void* skip, void* y, float* stats, int N, int64_t HW, int C, float eps, int act, float leak,
+                               int dtype, void* ws, size_t ws_bytes, void* stream) {
+    if (!in_pair_ok(gamma2, beta2, nsplit, N)) return SGG_EINVAL;
+    InSplit sp = in_nosplit(); sp.gamma2 = gamma2; sp.beta2 = beta2; sp.nsplit = nsplit;
+    return instnorm_fwd_skip_impl(x, gamma, beta, skip, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream, sp);
+}
+int sgg_instnorm_fwd_skip_partial_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
+                                       const void* skip, void* y, float* stats, const float* partial, int chunks, int N, int64_t HW, int C,
+                                       float eps, int act, float leak, int dtype, void* stream) {
+    if (!in_pair_ok(gamma2, beta2, nsplit, N)) return SGG_EINVAL;
+    InSplit sp = in_nosplit(); sp.gamma2 = gamma2; sp.beta2 = beta2; sp.nsplit = nsplit;
+    return instnorm_fwd_skip_partial_impl(x, gamma, beta, skip, y, stats, partial, chunks, N, HW, C, eps, act, leak, dtype, stream, sp);
+}
+int sgg_instnorm_bwd_skip_pair(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* gamma2,
+                               const float* beta2, int nsplit, const float* stats, void* dx, void* dskip, float* dgamma, float* dbeta,
+                               float* dgamma2, float* dbeta2, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
+                               int dtype, void* ws, size_t ws_bytes, void* stream) {
+    if (!in_pair_ok(gamma2, beta2, nsplit, N) || !dgamma2 || !dbeta2) return SGG_EINVAL;
+    InSplit sp; sp.gamma2 = gamma2; sp.beta2 = beta2; sp.dgamma2 = dgamma2; sp.dbeta2 = dbeta2; sp.nsplit = nsplit;
+    return instnorm_bwd_skip_impl(dy, y, x, gamma, beta, stats, dx, dskip, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype,
+                                  ws, ws_bytes, stream, sp);
 }
 
 }  // extern "C"

@@ -401,9 +401,9 @@ def conv_wgrad_group2(g: ConvGeom, x, dy, dw, dw2, accumulate=False):
     if pr: pr.stop()
 
 
-def deconv_fwd_group2(g: ConvGeom, x, w_dgrad, bias, w_dgrad2, bias2, act=A.ACT_NONE, leak=0.0):
+def deconv_fwd_group2(g: ConvGeom, x, w_dgrad, bias, w_dgrad2, bias2, act=A.ACT_NONE, leak=0.0, out=None):
     assert tuple(x.shape) == _stacked(g.x_shape) and g.is_deconv
-    y = torch.empty(_stacked(g.y_shape), dtype=x.dtype, device=x.device)
+    y = _out(out, _stacked(g.y_shape), x.dtype, x.device)
     ws = workspace(2 * g.ws_fwd, x.device) if g.ws_fwd else None
     pr = _prof("deconv2d_fwd_group2", g)
     if pr: pr.start()
@@ -613,6 +613,45 @@ def instnorm_bwd_pair(dy, x, gamma, beta, gamma2, beta2, nsplit, stats, dgamma, 
                                           _p(dgamma2), _p(dbeta2), N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak, dt(x),
                                           _p(ws), ws.numel(), _s()), "instnorm_bwd_pair")
     return dx
+
+
+def instnorm_fwd_skip_pair(x, gamma, beta, gamma2, beta2, nsplit, skip, eps=1e-3, act=A.ACT_NONE, leak=0.0, partial=None):
+    """instnorm_fwd_skip of two networks on one stacked batch: y = act(IN(x) + skip) with the affine set picked by image index."""
+    N, H, W, Cp = x.shape
+    assert gamma.numel() == Cp and gamma2.numel() == Cp and 0 < nsplit < N
+    assert tuple(skip.shape) == tuple(x.shape) and skip.dtype == x.dtype
+    y = torch.empty_like(x)
+    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
+    pr = _prof("instnorm_fwd_skip_pair", (tuple(x.shape), partial is not None))
+    if pr: pr.start()
+    if partial is not None:
+        assert partial.shape[0] == N and partial.shape[2] == Cp
+        A.check(A.lib().sgg_instnorm_fwd_skip_partial_pair(_p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(skip), _p(y), _p(stats),
+                                                           _p(partial), partial.shape[1], N, H * W, Cp, eps, act, leak, dt(x), _s()),
+                "instnorm_fwd_skip_partial_pair")
+    else:
+        ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
+        A.check(A.lib().sgg_instnorm_fwd_skip_pair(_p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(skip), _p(y), _p(stats),
+                                                   N, H * W, Cp, eps, act, leak, dt(x), _p(ws), ws.numel(), _s()), "instnorm_fwd_skip_pair")
+    if pr: pr.stop()
+    return y, stats
+
+
+def instnorm_bwd_skip_pair(dy, y, x, gamma, beta, gamma2, beta2, nsplit, stats, dgamma, dbeta, dgamma2, dbeta2, accumulate=False,
+                           act=A.ACT_NONE, leak=0.0):
+    """Backward of instnorm_fwd_skip_pair from its stored output y: (dx, dskip), both stacked like x."""
+    N, H, W, Cp = x.shape
+    assert dy.dtype == x.dtype and y.dtype == x.dtype and tuple(dy.shape) == tuple(x.shape) == tuple(y.shape)
+    assert dgamma.numel() == dgamma2.numel() and 0 < nsplit < N
+    dx, dskip = torch.empty_like(x), torch.empty_like(x)
+    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
+    pr = _prof("instnorm_bwd_skip_pair", tuple(x.shape))
+    if pr: pr.start()
+    A.check(A.lib().sgg_instnorm_bwd_skip_pair(_p(dy), _p(y), _p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(stats), _p(dx), _p(dskip),
+                                               _p(dgamma), _p(dbeta), _p(dgamma2), _p(dbeta2), N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak,
+                                               dt(x), _p(ws), ws.numel(), _s()), "instnorm_bwd_skip_pair")
+    if pr: pr.stop()
+    return dx, dskip
 
 
 def act_fwd(x, act, leak=0.0):

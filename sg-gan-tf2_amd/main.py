@@ -44,8 +44,12 @@ def build_parser():
     # build-specific knobs (not in the reference)
     a("--generator", dest="generator", choices=("resnet", "unet"), default="resnet",
       help="generator network: resnet (generator_resnet, this build's default) or unet (generator_unet: the reference's "
-           "default, i.e. its flag-less --use_resnet False)")
-    a("--cycle", dest="cycle", action="store_true", help="2G+2D cycle-mode step (north_star unit)")
+           "default, i.e. its flag-less --use_resnet False); either one trains in reference mode and with --cycle")
+    a("--cycle", dest="cycle", action="store_true",
+      help="2G+2D cycle-mode step (north_star unit): both generators are of the --generator kind and run in lockstep")
+    a("--paired", dest="paired", type=int, choices=(0, 1), default=None,
+      help="--cycle: 1 runs the two generators and the two discriminators in lockstep on stacked batches, 0 one network at a time; "
+           "default: 1 for the ResNet, 0 for the U-Net (where lockstep only pays at small sizes, e.g. 128x128)")
     a("--dtype", dest="dtype", default="bf16")
     a("--steps_per_epoch", dest="steps_per_epoch", type=int, default=4)
     a("--use_pool", dest="use_pool", action="store_true",

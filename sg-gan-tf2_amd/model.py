@@ -16,7 +16,7 @@ import torch
 from . import _abi as A
 from . import kernels as K
 from .graph import StepProgram
-from .module import Adam, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet
+from .module import Adam, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet, GeneratorUNetPair
 from .utils import ImagePool, StaticImagePool
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32,
@@ -29,7 +29,7 @@ def default_args(**over):
     a = dict(batch_size=1, image_height=128, image_width=128, input_nc=3, output_nc=3, ngf=64, ndf=64,
              segment_class=34, beta1=0.5, lr=0.0002, L1_lambda=10.0, Lg_lambda=5.0, use_resnet=True, use_pix2pix=False,
              use_lsgan=True, ratio_gan2seg=10, max_size=50, phase="train", dataset_dir="city",
-             dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=True,
+             dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=None,
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False)
     a.update(over)
@@ -56,11 +56,11 @@ class sggan(object):
         # model.py:55-62: --use_resnet picks generator_resnet(), otherwise generator_unet() (the reference's flag-less default)
         self.arch = "resnet" if g("use_resnet", True) else "unet"
         self.cycle = bool(g("cycle", False))
-        if self.cycle and self.arch == "unet":
-            raise NotImplementedError("cycle=True with the U-Net generator: the paired cycle step is built on the ResNet "
-                                      "generator's layer layout (GeneratorPair); use use_resnet=True")
         self.dtype = _DTYPES[g("dtype", "bf16")]
         self.device = torch.device(g("device", "cuda"))
+        if self.device.type != "cuda":       # refused here, before any network (and so any buffer) is built
+            raise NotImplementedError(f"sggan(cycle={self.cycle}, generator={self.arch}) on device '{self.device}': the train step has "
+                                      "no host implementation, it runs on the MI355X HIP path only (device must be a cuda/hip device)")
         seed = g("seed", 19)
         self.discriminator = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
                                            dtype=self.dtype, device=self.device, seed=seed + 1)          # model.py:54
@@ -77,8 +77,12 @@ class sggan(object):
         self.use_lsgan = bool(g("use_lsgan", True))
         self.cycle_lr = float(g("lr", 0.0002))
         if self.cycle:
-            self.generator_BA = Generator(gf_dim=g("ngf", 64), in_c=self.output_c_dim, out_c=self.input_c_dim,
-                                          n_blocks=g("n_blocks", 9), dtype=self.dtype, device=self.device, seed=seed + 2)
+            if self.arch == "resnet":
+                self.generator_BA = Generator(gf_dim=g("ngf", 64), in_c=self.output_c_dim, out_c=self.input_c_dim,
+                                              n_blocks=g("n_blocks", 9), dtype=self.dtype, device=self.device, seed=seed + 2)
+            else:
+                self.generator_BA = GeneratorUNet(gf_dim=g("ngf", 64), in_c=self.output_c_dim, out_c=self.input_c_dim,
+                                                  dtype=self.dtype, device=self.device, seed=seed + 2)
             self.discriminator_B = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
                                                  dtype=self.dtype, device=self.device, seed=seed + 3)
             self.real_B = self.seg_B = self.mask_B = self.fake_B = None
@@ -110,8 +114,12 @@ class sggan(object):
             self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1)
             self.d_optim_B = Adam(self.discriminator_B, lr, self.beta1)
         # cycle step: run the two generators (and the two discriminators) in lockstep on stacked batches (module._PairUnit);
-        # bit-identical to the one-network-at-a-time sequencing, which stays for the image pool and for mixed mode
-        self.paired = bool(g("paired", True))
+        # bit-identical to the one-network-at-a-time sequencing, which stays for the image pool and for mixed mode.  paired=None
+        # picks the default: on for the ResNet (the step bench.py times); off for the U-Net, whose step is bound by
+        # full-resolution 512-channel halo GEMMs that pairing does not touch -- lockstep is 4 % faster at 128x128 batch 8 but
+        # 0.6 % slower (and 8 GB larger) at 256x512 batch 8, more than the run-to-run spread ("cycle mode")
+        paired = g("paired", None)
+        self.paired = bool(paired) if paired is not None else self.arch == "resnet"
         # mixed precision: bf16 storage, but the activation-gradient chain through the generators' residual blocks in f32
         self.mixed = bool(g("mixed", False)) and self.dtype == torch.bfloat16
         for net in self.networks():
@@ -500,7 +508,8 @@ class sggan(object):
         (both forms are held to the float64 restatement at 2e-4 on every gradient tensor, tests/test_gpu_step.py)."""
         Gab, Gba, Da, Db = self.generator, self.generator_BA, self.discriminator, self.discriminator_B
         if getattr(self, "_pairs", None) is None:
-            self._pairs = (GeneratorPair(Gab, Gba), GeneratorPair(Gba, Gab), DiscriminatorPair(Db, Da), DiscriminatorPair(Da, Db))
+            GP = GeneratorPair if self.arch == "resnet" else GeneratorUNetPair
+            self._pairs = (GP(Gab, Gba), GP(Gba, Gab), DiscriminatorPair(Db, Da), DiscriminatorPair(Da, Db))
         Gp1, Gp2, Dpf, Dpr = self._pairs
         # Discriminators.  d_quad: reals AND fakes go through (D_B, D_A) as ONE stacked pass [real_B; fake_B | fake_A; real_A] --
         # half the launches of the two passes it replaces (the discriminators' tails are launch-latency bound) and the weight

@@ -789,7 +789,10 @@ class _PairUnit:
                (ub.kind, ub.stride, ub.padding, ub.reflect, ub.norm, ub.act, ub.leak, ub.R, ub.cin, ub.cout)
         self.ua, self.ub = ua, ub
 
-    def forward(self, x, residual=None, record_only=False, out=None):
+    def _conv(self, x, out=None):
+        """The convolution of both halves into one stacked output: (g, xc, part, one_launch).  part: the per-chunk (sum, sumsq)
+        rows of xc where the launch's epilogue delivers them for the norm behind it, else None; one_launch: they came from the
+        stacked launch of the two networks' 3x3 halo kernel."""
         ua, ub = self.ua, self.ub
         assert out is None or not ua.norm
         n = x.shape[0] // 2
@@ -805,29 +808,21 @@ class _PairUnit:
             wfa, _ = ua.packed(x.dtype)
             wfb, _ = ub.packed(x.dtype)
             xc, part = K.conv_fwd_stats_pair(g2, x, wfa, PA.p(na + "_b"), wfb, PB.p(nb + "_b"), n)
-            if record_only:          # (_ConvUnit.forward: the statistics without the apply pass)
-                return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], ua.net.eps))
-            y, stats = K.instnorm_fwd_partial_pair(xc, part, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
-                                                   residual, ua.net.eps, ua.act, ua.leak)
-            return y, (g, x, xc, stats)
+            return g, xc, part, True
         if ua.kind == "conv" and ua.norm and g.stats_chunks and ua.net.fuse_in_stats and (ua.R != 7 or ua.net.fuse_in_stats_stem):
             xc = torch.empty((2 * n,) + tuple(g.y_shape[1:]), dtype=x.dtype, device=x.device)
             part = torch.empty((2 * n, g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x.device)
             for u, sl in halves:
                 wf, _ = u.packed(x.dtype)
                 K.conv_fwd_stats(g, x[sl], wf, u.net.P.p(u.name + "_b"), out=xc[sl], out_partial=part[sl])
-            y, stats = K.instnorm_fwd_partial_pair(xc, part, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
-                                                   residual, ua.net.eps, ua.act, ua.leak)
-            return y, (g, x, xc, stats)
+            return g, xc, part, False
         if ua.kind == "deconv" and ua.norm and ua.net.fuse_in_stats and ua.net.fuse_in_stats_deconv and ua.net.group2:
             gs = ua.geom(x)                                    # the stacked batch: per-image weights in the stride-2 halo kernel
             if gs.stats_chunks:
                 _, wda = ua.packed(x.dtype)
                 _, wdb = ub.packed(x.dtype)
                 xc, part = K.deconv_fwd_stats(gs, x, wda, PA.p(na + "_b"), pair=(wdb, PB.p(nb + "_b"), n))
-                y, stats = K.instnorm_fwd_partial_pair(xc, part, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
-                                                       residual, ua.net.eps, ua.act, ua.leak)
-                return y, (g, x, xc, stats)
+                return g, xc, part, False
         # every other convolution: ONE grouped launch for both networks (sgg_*_group2: each network's call as its own group of
         # blocks -- bit-identical to two calls; the discriminators' small maps are latency bound, two half-size launches cost twice)
         wfa, wda = ua.packed(x.dtype)
@@ -842,37 +837,62 @@ class _PairUnit:
         elif ua.kind == "conv":
             xc = K.conv_fwd_group2(g, x, wfa, PA.p(na + "_b"), wfb, PB.p(nb + "_b"), fused_act, ua.leak, out=out)
         else:
-            assert out is None
-            xc = K.deconv_fwd_group2(g, x, wda, PA.p(na + "_b"), wdb, PB.p(nb + "_b"), fused_act, ua.leak)
+            xc = K.deconv_fwd_group2(g, x, wda, PA.p(na + "_b"), wdb, PB.p(nb + "_b"), fused_act, ua.leak, out=out)
+        return g, xc, None, False
+
+    def forward(self, x, residual=None, record_only=False, out=None):
+        ua, ub = self.ua, self.ub
+        n = x.shape[0] // 2
+        na, nb = ua.name, ub.name
+        PA, PB = ua.net.P, ub.net.P
+        g, xc, part, one_launch = self._conv(x, out)
         if not ua.norm:
             return xc, (g, x, xc, None)
+        if part is not None:
+            if record_only and one_launch:          # (_ConvUnit.forward: the statistics without the apply pass)
+                return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], ua.net.eps))
+            y, stats = K.instnorm_fwd_partial_pair(xc, part, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
+                                                   residual, ua.net.eps, ua.act, ua.leak)
+            return y, (g, x, xc, stats)
         y, stats = K.instnorm_fwd_pair(xc, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
                                        residual, ua.net.eps, ua.act, ua.leak)
         return y, (g, x, xc, stats)
+
+    def _norm_grads(self, param_grads):
+        """Where the norm backward puts (dgamma, dbeta) of the two networks."""
+        ua, ub = self.ua, self.ub
+        if param_grads:
+            return (ua.net.P.g(ua.name + "_g"), ua.net.P.g(ua.name + "_beta"), ub.net.P.g(ub.name + "_g"), ub.net.P.g(ub.name + "_beta"))
+        # gradients w.r.t. gamma / beta not wanted: send them to scratch
+        sa, sb = ua.net.scratch_vec(K.cpad(ua.cout)), ub.net.scratch_vec(K.cpad(ub.cout))
+        return (sa, sa, sb, sb)
 
     def backward(self, rec, dy, want_dx=True, param_grads=True, addend=None):
         ua, ub = self.ua, self.ub
         g, x, xc, stats = rec
         n = x.shape[0] // 2
-        halves = ((ua, slice(0, n)), (ub, slice(n, 2 * n)))
         na, nb = ua.name, ub.name
         PA, PB = ua.net.P, ub.net.P
         if ua.norm:
-            if param_grads:
-                grads = (PA.g(na + "_g"), PA.g(na + "_beta"), PB.g(nb + "_g"), PB.g(nb + "_beta"))
-            else:                                         # gradients w.r.t. gamma / beta not wanted: send them to scratch
-                sa, sb = ua.net.scratch_vec(K.cpad(ua.cout)), ub.net.scratch_vec(K.cpad(ub.cout))
-                grads = (sa, sa, sb, sb)
             dxc = K.instnorm_bwd_pair(dy, xc, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n, stats,
-                                      *grads, param_grads, ua.act, ua.leak)
+                                      *self._norm_grads(param_grads), param_grads, ua.act, ua.leak)
             # (the conv bias in front of an instance norm has an identically zero gradient: left at 0)
         else:
             dxc = K.act_bwd(dy, xc, ua.act, ua.leak) if ua.act != A.ACT_NONE else dy
             if param_grads and ua.net.group2:
                 K.bias_grad_group2(dxc, PA.g(na + "_b"), PB.g(nb + "_b"), accumulate=True)
             elif param_grads:
-                for u, sl in halves:
+                for u, sl in ((ua, slice(0, n)), (ub, slice(n, 2 * n))):
                     K.bias_grad(dxc[sl], u.net.P.g(u.name + "_b"), accumulate=True)
+        return self._conv_backward(g, x, dxc, want_dx, param_grads, addend)
+
+    def _conv_backward(self, g, x, dxc, want_dx, param_grads, addend):
+        """Weight gradients of both networks, then the stacked data gradient (+ addend)."""
+        ua, ub = self.ua, self.ub
+        n = x.shape[0] // 2
+        halves = ((ua, slice(0, n)), (ub, slice(n, 2 * n)))
+        na, nb = ua.name, ub.name
+        PA, PB = ua.net.P, ub.net.P
         if param_grads:
             # both networks have this layer's first application waiting (pair_wgrads): all four weight gradients in ONE launch
             pa, pb = ua._pending, ub._pending
@@ -906,6 +926,31 @@ class _PairUnit:
             return K.conv_dgrad_group2(g, dxc, wda, wdb, addend)
         dx = K.deconv_dgrad_group2(g, dxc, wfa, wfb)
         return dx if addend is None else K.add(dx, addend)
+
+
+class _PairSkipActUnit(_PairUnit):
+    """_SkipActUnit of two networks in lockstep: y = act(IN(conv(x)) + skip) on the stacked batch (the U-Net generators' d3 / d7
+    in the cycle step).  The convolution takes _PairUnit's paths; the norm is sgg_instnorm_*_skip_pair.  The forward record
+    carries y, and backward returns (dx, dskip), both stacked."""
+
+    def forward(self, x, residual=None, record_only=False, out=None):
+        assert residual is not None and out is None and not record_only and self.ua.norm
+        ua, ub = self.ua, self.ub
+        PA, PB = ua.net.P, ub.net.P
+        g, xc, part, _ = self._conv(x)
+        y, stats = K.instnorm_fwd_skip_pair(xc, PA.p(ua.name + "_g"), PA.p(ua.name + "_beta"), PB.p(ub.name + "_g"), PB.p(ub.name + "_beta"),
+                                            x.shape[0] // 2, residual, ua.net.eps, ua.act, ua.leak, partial=part)
+        return y, (g, x, xc, stats, y)
+
+    def backward(self, rec, dy, want_dx=True, param_grads=True, addend=None):
+        assert addend is None
+        ua, ub = self.ua, self.ub
+        PA, PB = ua.net.P, ub.net.P
+        g, x, xc, stats, y = rec
+        dxc, dskip = K.instnorm_bwd_skip_pair(dy, y, xc, PA.p(ua.name + "_g"), PA.p(ua.name + "_beta"), PB.p(ub.name + "_g"),
+                                              PB.p(ub.name + "_beta"), x.shape[0] // 2, stats, *self._norm_grads(param_grads),
+                                              param_grads, ua.act, ua.leak)
+        return self._conv_backward(g, x, dxc, want_dx, param_grads, None), dskip
 
 
 class GeneratorPair:
@@ -966,6 +1011,57 @@ class GeneratorPair:
         done("c2")
         d = self.head[0].backward(tape[0], d, want_dx, param_grads, addend=addend)
         done("c1")
+        return d
+
+
+class GeneratorUNetPair:
+    """generator_unet (module.py:125-206) of two generators in lockstep: forward([x_a; x_b]) = [G_a(x_a); G_b(x_b)].  Layer for
+    layer GeneratorUNet.forward / backward on stacked tensors: the seven skips and their gradients stay stacked (the gradients
+    ride in the addend of the encoder convs' data-gradient store), every instance norm is one launch for both networks."""
+
+    def __init__(self, ga, gb):
+        self.a, self.b = ga, gb
+        self.enc = [_PairUnit(ua, ub) for ua, ub in zip(ga.enc, gb.enc)]
+        self.dec = [(_PairSkipActUnit if isinstance(ua, _SkipActUnit) else _PairUnit)(ua, ub) for ua, ub in zip(ga.dec, gb.dec)]
+        self.d8 = _PairUnit(ga.d8, gb.d8)
+
+    def forward(self, x, out=None):
+        """out: buffer for the stacked result (the step hands in the middle of the discriminators' stacked input)."""
+        tape, enc_out = [], []
+        h = x
+        for u in self.enc:
+            h, r = u.forward(h)
+            tape.append(r)
+            enc_out.append(h)
+        for j, u in enumerate(self.dec):                       # d(j+1) + e(7-j)
+            h, r = u.forward(h, residual=enc_out[6 - j])
+            tape.append(r)
+        h, r = self.d8.forward(h, out=out)
+        tape.append(r)
+        return h, tape
+
+    def backward(self, tape, dy, want_dx=False, param_grads=True, on_unit_done=None, addend=None):
+        """on_unit_done(name), addend: as GeneratorUNet.backward -- both networks of the pair finish a layer together."""
+        done = on_unit_done if on_unit_done is not None else (lambda name: None)
+        d = self.d8.backward(tape[15], dy, True, param_grads)
+        done("d8")
+        dskip = [None] * 7                                     # dskip[i]: stacked gradient reaching e(i+1)'s output through the skip
+        for j in range(6, -1, -1):
+            u = self.dec[j]
+            if isinstance(u, _PairSkipActUnit):
+                d, dskip[6 - j] = u.backward(tape[8 + j], d, True, param_grads)
+            else:
+                dskip[6 - j] = d
+                d = u.backward(tape[8 + j], d, True, param_grads)
+            done(u.ua.name)
+        for k in range(7, -1, -1):
+            u = self.enc[k]
+            if k:
+                d = u.backward(tape[k], d, True, param_grads, addend=dskip[k - 1])   # + skip gradient (fused store)
+                dskip[k - 1] = None
+            else:
+                d = u.backward(tape[0], d, want_dx, param_grads, addend=addend)
+            done(u.ua.name)
         return d
 
 
