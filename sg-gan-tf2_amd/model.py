@@ -64,12 +64,10 @@ class sggan(object):
         seed = g("seed", 19)
         self.discriminator = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
                                            dtype=self.dtype, device=self.device, seed=seed + 1)          # model.py:54
-        if self.arch == "resnet":
-            self.generator = Generator(gf_dim=g("ngf", 64), in_c=self.input_c_dim, out_c=self.output_c_dim,
-                                       n_blocks=g("n_blocks", 9), dtype=self.dtype, device=self.device, seed=seed)  # :56
-        else:
-            self.generator = GeneratorUNet(gf_dim=g("ngf", 64), in_c=self.input_c_dim, out_c=self.output_c_dim,
-                                           dtype=self.dtype, device=self.device, seed=seed)                   # :58
+        def make_generator(in_c, out_c, seed):                  # :56 generator_resnet / :58 generator_unet
+            kw = dict(gf_dim=g("ngf", 64), in_c=in_c, out_c=out_c, dtype=self.dtype, device=self.device, seed=seed)
+            return Generator(n_blocks=g("n_blocks", 9), **kw) if self.arch == "resnet" else GeneratorUNet(**kw)
+        self.generator = make_generator(self.input_c_dim, self.output_c_dim, seed)
         self.beta1 = g("beta1", 0.5)
         self.lr = self.LR
         # cycle mode (north_star unit, deviation D5): G_A->B = self.generator, D_A = self.discriminator, plus G_B->A and D_B
@@ -77,12 +75,7 @@ class sggan(object):
         self.use_lsgan = bool(g("use_lsgan", True))
         self.cycle_lr = float(g("lr", 0.0002))
         if self.cycle:
-            if self.arch == "resnet":
-                self.generator_BA = Generator(gf_dim=g("ngf", 64), in_c=self.output_c_dim, out_c=self.input_c_dim,
-                                              n_blocks=g("n_blocks", 9), dtype=self.dtype, device=self.device, seed=seed + 2)
-            else:
-                self.generator_BA = GeneratorUNet(gf_dim=g("ngf", 64), in_c=self.output_c_dim, out_c=self.input_c_dim,
-                                                  dtype=self.dtype, device=self.device, seed=seed + 2)
+            self.generator_BA = make_generator(self.output_c_dim, self.input_c_dim, seed + 2)
             self.discriminator_B = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
                                                  dtype=self.dtype, device=self.device, seed=seed + 3)
             self.real_B = self.seg_B = self.mask_B = self.fake_B = None
@@ -377,19 +370,22 @@ class sggan(object):
         hook, (hG,) = self._bucketed_allreduce((G,))
         G.backward(tG, dfake, want_dx=False, param_grads=True, on_unit_done=hook)
 
-        scale = 1.0 / self._world
-        if hD is not None:
-            hD.wait()
-        self.d_optim.apply_gradients(grad_scale=scale)                     # :200
-        if hG is not None:
-            hG.wait()
-        self.g_optim.apply_gradients(grad_scale=scale)                     # :199
+        self._apply_gradients((self.d_optim, hD), (self.g_optim, hG))       # :200, :199
         self._fake_internal = fake
         self.fake_A = _LazyUnpad(fake, self.output_c_dim)
         self.da_real, self.da_fake = da_real, da_fake
         if self.keep_tapes:            # (stacked pass: views of its records, images [0, N) = D(seg), [N, 2N) = D(fake))
             self.tapes = {"G": tG, "D_real": D.slice_tape(tDq, 0, N) if stack else tDr, "D_fake": tDf}
         return self.gen_loss, self.disc_loss
+
+    def _apply_gradients(self, *updates):
+        """(optimizer, its network's all-reduce handle or None) in update order: each Adam launch waits for that network's
+        gradient exchange only, so the exchanges still in flight run under the updates in front of them."""
+        scale = 1.0 / self._world
+        for opt, h in updates:
+            if h is not None:
+                h.wait()
+            opt.apply_gradients(grad_scale=scale)
 
     def networks(self):
         return (self.generator, self.discriminator) + ((self.generator_BA, self.discriminator_B) if self.cycle else ())
@@ -402,11 +398,9 @@ class sggan(object):
         if self.paired and not self.use_pool and not self.mixed:
             return self._train_step_cycle_paired()
         Gab, Gba, Da, Db = self.generator, self.generator_BA, self.discriminator, self.discriminator_B
-        prep_mask = lambda m: (m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m, dtype=np.float32))).to(
-            device=self.device, dtype=torch.float32).contiguous()
         rA, rB = self._prep(self.real_A), self._prep(self.real_B)
         sA, sB = self._prep(self.seg_A), self._prep(self.seg_B)
-        mA, mB = prep_mask(self.mask_A), prep_mask(self.mask_B)
+        mA, mB = self._convert_input("mask_A", self.mask_A), self._convert_input("mask_B", self.mask_B)
         for net in (Gab, Gba, Da, Db):
             net.P.zero_grad()
         C = self.output_c_dim
@@ -486,11 +480,7 @@ class sggan(object):
         Gab.backward(t1, d_fB, on_unit_done=hook)
         Gab.flush_wgrads(); Gab.pair_wgrads = False
 
-        scale = 1.0 / self._world
-        for opt, h in ((self.d_optim, hDa), (self.d_optim_B, hDb), (self.g_optim_BA, hGba), (self.g_optim, hGab)):
-            if h is not None:
-                h.wait()
-            opt.apply_gradients(grad_scale=scale)
+        self._apply_gradients((self.d_optim, hDa), (self.d_optim_B, hDb), (self.g_optim_BA, hGba), (self.g_optim, hGab))
         self.fake_A, self.fake_B = _LazyUnpad(fake_A, self.input_c_dim), _LazyUnpad(fake_B, C)
         self.cyc_A, self.cyc_B = _LazyUnpad(cyc_A, self.input_c_dim), _LazyUnpad(cyc_B, C)
         return self.gen_loss, self.disc_loss
@@ -592,11 +582,7 @@ class sggan(object):
         Gba.flush_wgrads(); Gab.flush_wgrads()                  # (nothing is left to flush unless a partner never came)
         Gab.pair_wgrads = Gba.pair_wgrads = False
 
-        scale = 1.0 / self._world
-        for opt, h in ((self.d_optim, hDa), (self.d_optim_B, hDb), (self.g_optim_BA, hGba), (self.g_optim, hGab)):
-            if h is not None:
-                h.wait()
-            opt.apply_gradients(grad_scale=scale)
+        self._apply_gradients((self.d_optim, hDa), (self.d_optim_B, hDb), (self.g_optim_BA, hGba), (self.g_optim, hGab))
         self.fake_A, self.fake_B = _LazyUnpad(f1[hi], self.input_c_dim), _LazyUnpad(f1[lo], C)
         self.cyc_A, self.cyc_B = _LazyUnpad(c2[lo], self.input_c_dim), _LazyUnpad(c2[hi], C)
         if self.keep_tapes:

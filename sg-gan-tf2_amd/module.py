@@ -148,26 +148,24 @@ class Adam:
         P.adam_step(self.learning_rate, self.beta_1, self.beta_2, self.epsilon, grad_scale)
 
 
+def _layer_specs(name, shape, out_ch, norm=True):
+    """One conv layer's (name, shape) entries: kernel, bias, then the instance norm's gamma, beta."""
+    L = [(name + "_w", shape), (name + "_b", (out_ch,))]
+    return L + [(name + "_g", (out_ch,)), (name + "_beta", (out_ch,))] if norm else L
+
+
 def generator_param_specs(gf_dim=64, in_c=3, out_c=3, n_blocks=9):
     """(name, shape) in Keras ``trainable_variables`` creation order of generator_resnet (module.py:219-269)."""
     L = []
-
-    def conv(name, shape, out_ch, norm=True):
-        L.append((name + "_w", shape))
-        L.append((name + "_b", (out_ch,)))
-        if norm:
-            L.append((name + "_g", (out_ch,)))
-            L.append((name + "_beta", (out_ch,)))
-
-    conv("c1", (7, 7, in_c, gf_dim), gf_dim)
-    conv("c2", (3, 3, gf_dim, gf_dim * 2), gf_dim * 2)
-    conv("c3", (3, 3, gf_dim * 2, gf_dim * 4), gf_dim * 4)
+    L += _layer_specs("c1", (7, 7, in_c, gf_dim), gf_dim)
+    L += _layer_specs("c2", (3, 3, gf_dim, gf_dim * 2), gf_dim * 2)
+    L += _layer_specs("c3", (3, 3, gf_dim * 2, gf_dim * 4), gf_dim * 4)
     for i in range(1, n_blocks + 1):
-        conv(f"r{i}a", (3, 3, gf_dim * 4, gf_dim * 4), gf_dim * 4)
-        conv(f"r{i}b", (3, 3, gf_dim * 4, gf_dim * 4), gf_dim * 4)
-    conv("d1", (3, 3, gf_dim * 2, gf_dim * 4), gf_dim * 2)     # Conv2DTranspose kernel: (kh,kw,out,in)
-    conv("d2", (3, 3, gf_dim, gf_dim * 2), gf_dim)
-    conv("out", (7, 7, gf_dim, out_c), out_c, norm=False)
+        L += _layer_specs(f"r{i}a", (3, 3, gf_dim * 4, gf_dim * 4), gf_dim * 4)
+        L += _layer_specs(f"r{i}b", (3, 3, gf_dim * 4, gf_dim * 4), gf_dim * 4)
+    L += _layer_specs("d1", (3, 3, gf_dim * 2, gf_dim * 4), gf_dim * 2)     # Conv2DTranspose kernel: (kh,kw,out,in)
+    L += _layer_specs("d2", (3, 3, gf_dim, gf_dim * 2), gf_dim)
+    L += _layer_specs("out", (7, 7, gf_dim, out_c), out_c, norm=False)
     return L
 
 
@@ -175,45 +173,29 @@ def unet_param_specs(gf_dim=64, in_c=3, out_c=3):
     """(name, shape) in Keras ``trainable_variables`` creation order of generator_unet (module.py:125-206): per layer, in code
     order, kernel, bias, then the instance norm's gamma, beta.  e1..e8 are Conv2D (HWIO), d1..d8 Conv2DTranspose ((kh,kw,out,in))."""
     L = []
-
-    def conv(name, shape, out_ch, norm=True):
-        L.append((name + "_w", shape))
-        L.append((name + "_b", (out_ch,)))
-        if norm:
-            L.append((name + "_g", (out_ch,)))
-            L.append((name + "_beta", (out_ch,)))
-
     enc = [gf_dim, gf_dim * 2, gf_dim * 4] + [gf_dim * 8] * 5
     cin = in_c
     for i, c in enumerate(enc, 1):                                  # :139-170
-        conv(f"e{i}", (3, 3, cin, c), c)
+        L += _layer_specs(f"e{i}", (3, 3, cin, c), c)
         cin = c
     for i, c in enumerate([gf_dim * 8] * 4 + [gf_dim * 4, gf_dim * 2, gf_dim], 1):   # :172-202
-        conv(f"d{i}", (3, 3, c, cin), c)
+        L += _layer_specs(f"d{i}", (3, 3, c, cin), c)
         cin = c
-    conv("d8", (3, 3, out_c, cin), out_c, norm=False)               # :204-205
+    L += _layer_specs("d8", (3, 3, out_c, cin), out_c, norm=False)  # :204-205
     return L
 
 
 def discriminator_param_specs(df_dim=64, in_c=3, segment_class=34):
     """Creation order of discriminator (module.py:272-318)."""
     L = []
-
-    def conv(name, shape, norm=True):
-        L.append((name + "_w", shape))
-        L.append((name + "_b", (shape[-1],)))
-        if norm:
-            L.append((name + "_g", (shape[-1],)))
-            L.append((name + "_beta", (shape[-1],)))
-
-    conv("h0", (3, 3, in_c, df_dim), norm=False)
-    conv("h1", (3, 3, df_dim, df_dim * 2))
-    conv("h2", (3, 3, df_dim * 2, df_dim * 4))
-    conv("h3", (3, 3, df_dim * 4, df_dim * 8))
-    conv("h31", (3, 3, df_dim * 8, df_dim * 8))
-    conv("h32", (3, 3, df_dim * 8, df_dim * 8))
-    conv("h33", (3, 3, df_dim * 8, df_dim * 8))
-    conv("h4", (3, 3, df_dim * 8, segment_class), norm=False)
+    L += _layer_specs("h0", (3, 3, in_c, df_dim), df_dim, norm=False)
+    L += _layer_specs("h1", (3, 3, df_dim, df_dim * 2), df_dim * 2)
+    L += _layer_specs("h2", (3, 3, df_dim * 2, df_dim * 4), df_dim * 4)
+    L += _layer_specs("h3", (3, 3, df_dim * 4, df_dim * 8), df_dim * 8)
+    L += _layer_specs("h31", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8)
+    L += _layer_specs("h32", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8)
+    L += _layer_specs("h33", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8)
+    L += _layer_specs("h4", (3, 3, df_dim * 8, segment_class), segment_class, norm=False)
     return L
 
 
@@ -266,7 +248,13 @@ FUSE_STEM_IN_STATS = False
 class _ConvUnit:
     """One Conv2D / Conv2DTranspose call site, optionally followed by InstanceNorm (+act, +residual),
     or by a fused activation when there is no norm.  Stateless w.r.t. activations: forward returns a
-    record that backward consumes, so one network can be applied several times per step."""
+    record that backward consumes, so one network can be applied several times per step.
+
+    The unit protocol -- ``name``, ``skip_grad``, ``geom(x)``, ``forward(...)``, ``backward(...)`` -- is answered alike by
+    _SkipActUnit and by the lockstep units (_PairUnit, _PairSkipActUnit): the networks' layer walks never ask which kind
+    they hold."""
+
+    skip_grad = False           # backward returns dx (True: (dx, dskip), the gradient of the skip path as well)
 
     def __init__(self, net, name, kind, stride=1, padding="VALID", reflect=0, norm=True, act=A.ACT_NONE, leak=0.0):
         self.net, self.name, self.kind = net, name, kind            # kind: "conv" | "deconv"
@@ -312,6 +300,24 @@ class _ConvUnit:
                 self._packed = (key, wf, wd)
         return self._packed[1], self._packed[2]
 
+    def _conv(self, x, out=None):
+        """The convolution alone: (g, xc, part).  part: the per-chunk (sum, sumsq) rows of xc where the launch's epilogue
+        delivers them for the norm behind it (that norm then skips its own statistics pass over the tensor), else None."""
+        P, n = self.net.P, self.name
+        assert out is None or not self.norm
+        g = self.geom(x)
+        wf, wd = self.packed(x.dtype)
+        stats = self.norm and g.stats_chunks and self.net.fuse_in_stats
+        if self.kind == "conv" and stats and (self.R != 7 or self.net.fuse_in_stats_stem):
+            return (g,) + K.conv_fwd_stats(g, x, wf, P.p(n + "_b"))
+        if self.kind == "deconv" and stats and self.net.fuse_in_stats_deconv:
+            # Conv2DTranspose + InstanceNormalization (module.py:254-260): the stride-2 halo kernel's epilogue emits the norm's sums too
+            return (g,) + K.deconv_fwd_stats(g, x, wd, P.p(n + "_b"))
+        fused_act = A.ACT_NONE if self.norm else self.act
+        if self.kind == "conv":
+            return g, K.conv_fwd(g, x, wf, P.p(n + "_b"), fused_act, self.leak, out=out), None
+        return g, K.deconv_fwd(g, x, wd, P.p(n + "_b"), fused_act, self.leak, out=out), None
+
     def forward(self, x, residual=None, record_only=False, out=None):
         """out: the caller's buffer for the layer output (layers without a norm only: the generator's last layer writes the
         fakes straight into the discriminators' stacked input).
@@ -319,29 +325,15 @@ class _ConvUnit:
         conv for its backward pass: the block's output is not needed again) -- where the conv's epilogue delivers the norm's
         sums, the norm's apply pass is skipped (same statistics, bit for bit) and y is None."""
         P, n = self.net.P, self.name
-        g = self.geom(x)
-        wf, wd = self.packed(x.dtype)
-        fused_act = A.ACT_NONE if self.norm else self.act
-        if self.kind == "conv" and self.norm and g.stats_chunks and self.net.fuse_in_stats and (self.R != 7 or self.net.fuse_in_stats_stem):
-            # the conv's epilogue emits the norm's per-chunk sums: the norm skips its own pass over the tensor
-            xc, part = K.conv_fwd_stats(g, x, wf, P.p(n + "_b"))
-            if record_only:
-                return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], self.net.eps))
-            y, stats = K.instnorm_fwd_partial(xc, part, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
-            return y, (g, x, xc, stats)
-        assert out is None or not self.norm
-        if self.kind == "deconv" and self.norm and g.stats_chunks and self.net.fuse_in_stats and self.net.fuse_in_stats_deconv:
-            # Conv2DTranspose + InstanceNormalization (module.py:254-260): the stride-2 halo kernel's epilogue emits the norm's sums too
-            xc, part = K.deconv_fwd_stats(g, x, wd, P.p(n + "_b"))
-            y, stats = K.instnorm_fwd_partial(xc, part, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
-            return y, (g, x, xc, stats)
-        if self.kind == "conv":
-            xc = K.conv_fwd(g, x, wf, P.p(n + "_b"), fused_act, self.leak, out=out)
-        else:
-            xc = K.deconv_fwd(g, x, wd, P.p(n + "_b"), fused_act, self.leak, out=out)
+        g, xc, part = self._conv(x, out)
         if not self.norm:
             return xc, (g, x, xc, None)
-        y, stats = K.instnorm_fwd(xc, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
+        if part is None:
+            y, stats = K.instnorm_fwd(xc, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
+        elif record_only:
+            return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], self.net.eps))
+        else:
+            y, stats = K.instnorm_fwd_partial(xc, part, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
         return y, (g, x, xc, stats)
 
     def weight_grad(self, g, x, dxc, gbuf=None):
@@ -413,21 +405,12 @@ class _SkipActUnit(_ConvUnit):
     (generator_unet d3 / d7, module.py:181-184,199-202).  The forward record keeps y as well: the backward derives act'
     from it (sgg_instnorm_bwd_skip) and returns (dx, dskip), dskip being the skip path's gradient."""
 
+    skip_grad = True
+
     def forward(self, x, residual=None, record_only=False, out=None):
         assert residual is not None and out is None and not record_only and self.norm
         P, n = self.net.P, self.name
-        g = self.geom(x)
-        wf, wd = self.packed(x.dtype)
-        part = None
-        if self.kind == "conv":
-            if g.stats_chunks and self.net.fuse_in_stats:
-                xc, part = K.conv_fwd_stats(g, x, wf, P.p(n + "_b"))
-            else:
-                xc = K.conv_fwd(g, x, wf, P.p(n + "_b"))
-        elif g.stats_chunks and self.net.fuse_in_stats and self.net.fuse_in_stats_deconv:
-            xc, part = K.deconv_fwd_stats(g, x, wd, P.p(n + "_b"))
-        else:
-            xc = K.deconv_fwd(g, x, wd, P.p(n + "_b"))
+        g, xc, part = self._conv(x)
         y, stats = K.instnorm_fwd_skip(xc, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak, partial=part)
         return y, (g, x, xc, stats, y)
 
@@ -471,7 +454,7 @@ class _Net:
         self.fuse_in_stats_deconv, self.fuse_in_stats_stem = FUSE_DECONV_IN_STATS, FUSE_STEM_IN_STATS
         self.group2 = True           # lockstep pairs: both networks' generic convolutions in one grouped launch (sgg_*_group2)
         # activation checkpointing (BASELINE.json configs[4]): a generator keeps only each residual block's INPUT and re-runs
-        # the block's two convs + norms in backward (Generator.forward / _block_records)
+        # the block's two convs + norms in backward (_ResNetWalk.forward / _block_records)
         self.checkpoint_blocks = False
         self._pack_tables = {}
 
@@ -539,7 +522,82 @@ class _BlockInput:
         self.x = x
 
 
-class Generator(_Net):
+# One walk per topology, written against the unit protocol (_ConvUnit): the network classes and their lockstep pair classes
+# (GeneratorPair, GeneratorUNetPair, DiscriminatorPair) differ only in the units they hand it, so a network and its pair visit
+# the layers -- and report them to on_unit_done -- in the same order by construction.
+class _ResNetWalk:
+    """generator_resnet (module.py:219-269) over ``head`` (three stem units), ``blocks`` ((a, b) unit pairs of the residual
+    blocks) and ``tail`` (two transposed units + the output unit); ``checkpoint_blocks`` selects activation checkpointing."""
+
+    def conv_units(self):
+        return self.head + [u for pair in self.blocks for u in pair] + self.tail
+
+    def forward(self, x, out=None):
+        """x: internal (N,H,W,8).  Returns (fake internal (N,H,W,8), tape).  out: buffer for the result (the step hands in
+        its slice of the discriminators' stacked input).  tape: one record per stem unit, one entry per block ((ra, rb), or
+        the block's input under checkpointing), one record per tail unit."""
+        tape = []
+        h = x
+        for u in self.head:
+            h, r = u.forward(h)
+            tape.append(r)
+        for ua, ub in self.blocks:
+            y, ra = ua.forward(h)
+            hin = h
+            h, rb = ub.forward(y, residual=h)                 # IN(conv(y)) + x   (:216-217)
+            tape.append(_BlockInput(hin) if self.checkpoint_blocks else (ra, rb))
+        for u in self.tail:
+            h, r = u.forward(h, out=out if u is self.tail[-1] else None)
+            tape.append(r)
+        return h, tape
+
+    def _block_records(self, ua, ub, rec):
+        """(ra, rb) of the residual block (ua, ub): as saved by forward, or -- activation checkpointing -- recomputed from the
+        block's saved input (the kernels are bitwise reproducible, so the records, and with them every gradient, are the same bits)."""
+        if not isinstance(rec, _BlockInput):
+            return rec
+        y, ra = ua.forward(rec.x)
+        _, rb = ub.forward(y, residual=rec.x, record_only=True)
+        return ra, rb
+
+    def backward(self, tape, dy, want_dx=False, param_grads=True, gbuf=None, on_unit_done=None, addend=None):
+        """on_unit_done(name): called after each layer's backward (its weight gradient included) has been queued -- the
+        data-parallel step hangs its per-bucket all-reduce launches on it (``bucket_plan``).  addend: a tensor shaped like the
+        input gradient, added to it in the first layer's data-gradient store (the step's gradient joins: no extra pass)."""
+        done = on_unit_done if on_unit_done is not None else (lambda name: None)
+        nh, nt = len(self.head), len(self.tail)
+        d = dy
+        for u, r in zip(reversed(self.tail), reversed(tape[len(tape) - nt:])):
+            d = u.backward(r, d, True, param_grads, gbuf)
+            done(u.name)
+        # residual blocks: each data gradient also makes the first pass of the norm backward that consumes it (the
+        # norm of the conv before it in forward order), so that norm skips its statistics pass over the tensor
+        part = None
+        blocks = [(ua, ub, rec) for (ua, ub), rec in zip(self.blocks, tape[nh:len(tape) - nt])][::-1]
+        ahead = self._block_records(*blocks[0]) if blocks else None
+        for k, (ua, ub, _) in enumerate(blocks):
+            ra, rb = ahead
+            # (the records of the block in front: its second norm consumes this block's data gradient -- under checkpointing
+            # they are recomputed one block ahead, so at most two blocks' activations are alive)
+            if k + 1 < len(blocks):
+                ahead = self._block_records(*blocks[k + 1])
+                nxt = (blocks[k + 1][1], ahead[1])
+            else:
+                ahead, nxt = None, (self.head[-1], tape[nh - 1])
+            t, pa = ub.backward(rb, d, True, param_grads, gbuf, dy_partial=part, next_norm=(ua, ra))
+            done(ub.name)
+            d, part = ua.backward(ra, t, True, param_grads, gbuf, addend=d, dy_partial=pa, next_norm=nxt)   # + skip gradient (fused)
+            done(ua.name)
+        ra = rb = None
+        for u, r in zip(reversed(self.head), reversed(tape[:nh])):
+            first = u is self.head[0]
+            d = u.backward(r, d, want_dx or not first, param_grads, gbuf, addend=addend if first else None, dy_partial=part)
+            part = None
+            done(u.name)
+        return d
+
+
+class Generator(_ResNetWalk, _Net):
     """generator_resnet (module.py:219-269): c7s1-64, d128, d256, 9 x R256, u128, u64, c7s1-3 + tanh."""
 
     def __init__(self, gf_dim=64, in_c=3, out_c=3, n_blocks=9, dtype=torch.bfloat16, device="cuda", eps=1e-3, seed=19):
@@ -554,70 +612,7 @@ class Generator(_Net):
         self.d1 = U("d1", "deconv", stride=2, act=A.ACT_RELU)                      # :254-256
         self.d2 = U("d2", "deconv", stride=2, act=A.ACT_RELU)                      # :258-260
         self.out = U("out", "conv", reflect=3, norm=False, act=A.ACT_TANH)         # :262-265
-
-    def conv_units(self):
-        return [self.c1, self.c2, self.c3] + [u for pair in self.blocks for u in pair] + [self.d1, self.d2, self.out]
-
-    def forward(self, x, out=None):
-        """x: internal (N,H,W,8).  Returns (fake internal (N,H,W,8), tape).  out: buffer for the result."""
-        tape = []
-        h = x
-        for u in (self.c1, self.c2, self.c3):
-            h, r = u.forward(h)
-            tape.append(r)
-        for ua, ub in self.blocks:
-            y, ra = ua.forward(h)
-            hin = h
-            h, rb = ub.forward(y, residual=h)                 # IN(conv(y)) + x   (:216-217)
-            tape.append(_BlockInput(hin) if self.checkpoint_blocks else (ra, rb))
-        for u in (self.d1, self.d2, self.out):
-            h, r = u.forward(h, out=out if u is self.out else None)
-            tape.append(r)
-        return h, tape
-
-    def _block_records(self, k, rec):
-        """(ra, rb) of residual block k: as saved by forward, or -- activation checkpointing -- recomputed from the block's
-        saved input (the kernels are bitwise reproducible, so the records, and with them every gradient, are the same bits)."""
-        if not isinstance(rec, _BlockInput):
-            return rec
-        ua, ub = self.blocks[k]
-        y, ra = ua.forward(rec.x)
-        _, rb = ub.forward(y, residual=rec.x, record_only=True)
-        return ra, rb
-
-    def backward(self, tape, dy, want_dx=False, param_grads=True, gbuf=None, on_unit_done=None, addend=None):
-        """on_unit_done(name): called after each layer's backward (its weight gradient included) has been queued -- the
-        data-parallel step hangs its per-bucket all-reduce launches on it (``bucket_plan``).  addend: a tensor shaped like the
-        input gradient, added to it in the first layer's data-gradient store (the step's gradient joins: no extra pass)."""
-        nb = self.n_blocks
-        done = on_unit_done if on_unit_done is not None else (lambda name: None)
-        d = dy
-        for u, r in zip((self.out, self.d2, self.d1), (tape[5 + nb], tape[4 + nb], tape[3 + nb])):
-            d = u.backward(r, d, True, param_grads, gbuf)
-            done(u.name)
-        # residual blocks: each data gradient also makes the first pass of the norm backward that consumes it (the
-        # norm of the conv before it in forward order), so that norm skips its statistics pass over the tensor
-        part = None
-        blocks = list(reversed(self.blocks))
-        cur = self._block_records(nb - 1, tape[2 + nb]) if nb else None
-        for k, (ua, ub) in enumerate(blocks):
-            ra, rb = cur
-            # (the records of the block in front: its second norm consumes this block's data gradient -- under checkpointing
-            # they are recomputed one block ahead, so at most two blocks' activations are alive)
-            cur = self._block_records(nb - 2 - k, tape[1 + nb - k]) if k + 1 < nb else None
-            t, pa = ub.backward(rb, d, True, param_grads, gbuf, dy_partial=part, next_norm=(ua, ra))
-            done(ub.name)
-            nxt = (blocks[k + 1][1], cur[1]) if k + 1 < nb else (self.c3, tape[2])
-            d, part = ua.backward(ra, t, True, param_grads, gbuf, addend=d, dy_partial=pa, next_norm=nxt)   # + skip gradient (fused)
-            done(ua.name)
-            ra = rb = None
-        d = self.c3.backward(tape[2], d, True, param_grads, gbuf, dy_partial=part)
-        done("c3")
-        d = self.c2.backward(tape[1], d, True, param_grads, gbuf)
-        done("c2")
-        d = self.c1.backward(tape[0], d, want_dx, param_grads, gbuf, addend=addend)
-        done("c1")
-        return d
+        self.head, self.tail = [self.c1, self.c2, self.c3], [self.d1, self.d2, self.out]
 
     def __call__(self, x):
         """Drop-in for ``self.generator(self.real_A)`` (model.py:175): NHWC float32 in, NHWC float32 out."""
@@ -633,7 +628,55 @@ class Generator(_Net):
         return None if dx is None else K.unpad_channels(dx, self.in_c)
 
 
-class GeneratorUNet(_Net):
+class _UNetWalk:
+    """generator_unet (module.py:125-206) over ``enc`` (the encoder units), ``dec`` (the decoder units that take a skip: one
+    fewer, the last encoder output being the decoder's input) and ``d8`` (the output unit)."""
+
+    def conv_units(self):
+        return self.enc + self.dec + [self.d8]
+
+    def forward(self, x, out=None):
+        """x: internal (N,H,W,8).  Returns (fake internal (N,H,W,8), tape); out: buffer for the result.  tape = the layers'
+        forward records in layer order."""
+        tape, skips = [], []
+        h = x
+        for u in self.enc:
+            h, r = u.forward(h)
+            tape.append(r)
+            skips.append(h)
+        skips.pop()                                            # (the innermost output feeds the decoder: no skip)
+        for u in self.dec:                                     # d(j) + e(8-j): the skips are consumed innermost first
+            h, r = u.forward(h, residual=skips.pop())
+            tape.append(r)
+        h, r = self.d8.forward(h, out=out)
+        tape.append(r)
+        return h, tape
+
+    def backward(self, tape, dy, want_dx=False, param_grads=True, gbuf=None, on_unit_done=None, addend=None):
+        """on_unit_done, addend: as the ResNet walk's.  The decoder produces the skip gradients (units with ``skip_grad``, d3 / d7:
+        dy * relu'(y) from the norm backward; the others: the gradient of the layer's output itself); each is held until the
+        encoder's backward reaches its layer and joins that layer's gradient in the data-gradient store of the conv behind it."""
+        done = on_unit_done if on_unit_done is not None else (lambda name: None)
+        ne = len(self.enc)
+        d = self.d8.backward(tape[-1], dy, True, param_grads, gbuf)
+        done(self.d8.name)
+        joins = [addend]            # what each encoder unit's data-gradient store adds, outermost first: the step's join, then the skips
+        for u, r in zip(reversed(self.dec), reversed(tape[ne:-1])):
+            if u.skip_grad:
+                d, dskip = u.backward(r, d, True, param_grads, gbuf)
+            else:
+                dskip = d
+                d = u.backward(r, d, True, param_grads, gbuf)
+            joins.append(dskip)
+            done(u.name)
+        dskip = None
+        for u, r in zip(reversed(self.enc), reversed(tape[:ne])):
+            d = u.backward(r, d, want_dx or u is not self.enc[0], param_grads, gbuf, addend=joins.pop())   # + skip gradient (fused store)
+            done(u.name)
+        return d
+
+
+class GeneratorUNet(_UNetWalk, _Net):
     """generator_unet (module.py:125-206), the reference's default generator (--use_resnet False): eight 3x3 stride-1 SAME
     Conv2D + IN + LeakyReLU (e8: ReLU), seven 3x3 stride-1 SAME Conv2DTranspose + IN + additive skip from the mirrored
     encoder layer (d3 / d7: ReLU after the add), and a Conv2DTranspose to the output channels + tanh.  Dropout (d1-d3) is the
@@ -650,57 +693,55 @@ class GeneratorUNet(_Net):
                      U(f"d{i}", "deconv", stride=1, act=A.ACT_NONE)) for i in range(1, 8)]
         self.d8 = U("d8", "deconv", stride=1, norm=False, act=A.ACT_TANH)
 
-    def conv_units(self):
-        return self.enc + self.dec + [self.d8]
-
-    def forward(self, x, out=None):
-        """x: internal (N,H,W,8).  Returns (fake internal (N,H,W,8), tape); out: buffer for the result.  tape = the 16 layers'
-        forward records in layer order."""
-        tape, enc_out = [], []
-        h = x
-        for u in self.enc:
-            h, r = u.forward(h)
-            tape.append(r)
-            enc_out.append(h)
-        for j, u in enumerate(self.dec):                       # d(j+1) + e(7-j)
-            h, r = u.forward(h, residual=enc_out[6 - j])
-            tape.append(r)
-        h, r = self.d8.forward(h, out=out)
-        tape.append(r)
-        return h, tape
-
-    def backward(self, tape, dy, want_dx=False, param_grads=True, gbuf=None, on_unit_done=None, addend=None):
-        """As Generator.backward.  The decoder produces the seven skip gradients (d1, d2, d4-d6: the gradient of the layer's
-        output itself; d3, d7: dy * relu'(y) from the norm backward); each is held until the encoder's backward reaches its
-        layer and joins that layer's gradient in the data-gradient store of the conv behind it (addend)."""
-        done = on_unit_done if on_unit_done is not None else (lambda name: None)
-        d = self.d8.backward(tape[15], dy, True, param_grads, gbuf)
-        done("d8")
-        dskip = [None] * 7                                     # dskip[i]: gradient reaching e(i+1)'s output through the skip
-        for j in range(6, -1, -1):
-            u = self.dec[j]
-            if isinstance(u, _SkipActUnit):
-                d, dskip[6 - j] = u.backward(tape[8 + j], d, True, param_grads, gbuf)
-            else:
-                dskip[6 - j] = d
-                d = u.backward(tape[8 + j], d, True, param_grads, gbuf)
-            done(u.name)
-        for k in range(7, -1, -1):
-            u = self.enc[k]
-            if k:
-                d = u.backward(tape[k], d, True, param_grads, gbuf, addend=dskip[k - 1])   # + skip gradient (fused store)
-                dskip[k - 1] = None
-            else:
-                d = u.backward(tape[0], d, want_dx, param_grads, gbuf, addend=addend)
-            done(u.name)
-        return d
-
     __call__ = Generator.__call__
     _run = Generator._run
     _run_backward = Generator._run_backward
 
 
-class Discriminator(_Net):
+class _DiscriminatorWalk:
+    """discriminator (module.py:272-318) over ``units`` (the convs with an activation) and ``h4`` (the class-logit conv), then
+    the mask multiply and channel sum (``segment_class`` channels, activations in ``dtype``)."""
+
+    def conv_units(self):
+        return list(self.units) + [self.h4]
+
+    def forward(self, x, mask):
+        """x internal (N,H,W,8); mask f32 (N,mh,mw,segment_class).  Returns (logits f32 (N,mh,mw,1), tape): one record per
+        unit, then (mask, h4's shape)."""
+        tape = []
+        h = x
+        for u in self.conv_units():
+            h, r = u.forward(h)
+            tape.append(r)
+        mask = mask.to(device=h.device, dtype=torch.float32).contiguous()
+        out = K.mask_reduce_fwd(h, mask, self.segment_class)                     # :312-314
+        tape.append((mask, tuple(h.shape)))
+        return out, tape
+
+    def backward(self, tape, dlogits, want_dx=False, param_grads=True, gbuf=None, addend=None):
+        """addend: added to the image gradient in the first unit's data-gradient store (as in the generators' walks)."""
+        *recs, (mask, h4_shape) = tape
+        d = K.mask_reduce_bwd(dlogits.contiguous(), mask, h4_shape, self.dtype, self.segment_class)
+        units = self.conv_units()
+        for u, r in zip(reversed(units), reversed(recs)):
+            first = u is units[0]
+            d = u.backward(r, d, want_dx or not first, param_grads, gbuf, addend=addend if first else None)
+        return d
+
+    def slice_tape(self, tape, lo, hi):
+        """The forward records of images [lo, hi) of a pass, as views (a backward pass through part of the batch: the step sends
+        reals and fakes through D as one stacked pass, the generator's loss only needs the fakes).  Of a lockstep pair's stacked
+        pass the slice must hold as many images of the first network as of the second."""
+        *recs, (mask, h4_shape) = tape
+        out = []
+        for u, (g, x, xc, stats) in zip(self.conv_units(), recs):
+            xs = x[lo:hi]
+            out.append((u.geom(xs), xs, xc[lo:hi], None if stats is None else stats[lo:hi]))
+        out.append((mask[lo:hi], (hi - lo,) + tuple(h4_shape[1:])))
+        return out
+
+
+class Discriminator(_DiscriminatorWalk, _Net):
     """discriminator (module.py:272-318): 8 convs, mask multiply, channel sum."""
 
     def __init__(self, df_dim=64, in_c=3, segment_class=34, dtype=torch.bfloat16, device="cuda", eps=1e-3, leak=0.3, seed=20):
@@ -715,43 +756,6 @@ class Discriminator(_Net):
                       U("h32", "conv", stride=2, padding="VALID"),                # :303-305
                       U("h33", "conv", stride=1, padding="VALID")]                # :307-309
         self.h4 = _ConvUnit(self, "h4", "conv", stride=1, padding="SAME", norm=False, act=A.ACT_NONE)   # :311
-
-    def conv_units(self):
-        return list(self.units) + [self.h4]
-
-    def forward(self, x, mask):
-        """x internal (N,H,W,8); mask f32 (N,mh,mw,segment_class).  Returns (logits f32 (N,mh,mw,1), tape)."""
-        tape = []
-        h = x
-        for u in self.units:
-            h, r = u.forward(h)
-            tape.append(r)
-        h4, r = self.h4.forward(h)
-        tape.append(r)
-        mask = mask.to(device=self.device, dtype=torch.float32).contiguous()
-        out = K.mask_reduce_fwd(h4, mask, self.segment_class)                    # :312-314
-        tape.append((mask, tuple(h4.shape)))
-        return out, tape
-
-    def backward(self, tape, dlogits, want_dx=False, param_grads=True, gbuf=None, addend=None):
-        """addend: added to the image gradient in h0's data-gradient store (Generator.backward)."""
-        mask, h4_shape = tape[-1]
-        d = K.mask_reduce_bwd(dlogits.contiguous(), mask, h4_shape, self.dtype, self.segment_class)
-        d = self.h4.backward(tape[-2], d, True, param_grads, gbuf)
-        for i in range(len(self.units) - 1, -1, -1):
-            d = self.units[i].backward(tape[i], d, want_dx or i > 0, param_grads, gbuf, addend=addend if i == 0 else None)
-        return d
-
-    def slice_tape(self, tape, lo, hi):
-        """The forward records of images [lo, hi) of a pass, as views (a backward pass through part of the batch: the step sends
-        reals and fakes through D as one stacked pass, the generator's loss only needs the fakes)."""
-        out = []
-        for u, (g, x, xc, stats) in zip(self.conv_units(), tape[:-1]):
-            xs = x[lo:hi]
-            out.append((u.geom(xs), xs, xc[lo:hi], None if stats is None else stats[lo:hi]))
-        mask, h4_shape = tape[-1]
-        out.append((mask[lo:hi], (hi - lo,) + tuple(h4_shape[1:])))
-        return out
 
     def out_hw(self, H, W):
         """Spatial size of the h4 map for an HxW input (deviation D1: the mask grid to use above 128x128)."""
@@ -785,9 +789,15 @@ class _PairUnit:
     a 33 MB one 4.1-4.5), half the launches, and per image exactly the arithmetic of two separate calls."""
 
     def __init__(self, ua, ub):
-        assert (ua.kind, ua.stride, ua.padding, ua.reflect, ua.norm, ua.act, ua.leak, ua.R, ua.cin, ua.cout) == \
-               (ub.kind, ub.stride, ub.padding, ub.reflect, ub.norm, ub.act, ub.leak, ub.R, ub.cin, ub.cout)
-        self.ua, self.ub = ua, ub
+        assert (ua.name, ua.kind, ua.stride, ua.padding, ua.reflect, ua.norm, ua.act, ua.leak, ua.R, ua.cin, ua.cout) == \
+               (ub.name, ub.kind, ub.stride, ub.padding, ub.reflect, ub.norm, ub.act, ub.leak, ub.R, ub.cin, ub.cout)
+        self.ua, self.ub, self.name = ua, ub, ua.name
+
+    def geom(self, x):
+        """The per-network geometry of a stacked batch: each network convolves its half."""
+        return self.ua.geom(x[:x.shape[0] // 2])
+
+    skip_grad = False
 
     def _conv(self, x, out=None):
         """The convolution of both halves into one stacked output: (g, xc, part, one_launch).  part: the per-chunk (sum, sumsq)
@@ -797,7 +807,7 @@ class _PairUnit:
         assert out is None or not ua.norm
         n = x.shape[0] // 2
         halves = ((ua, slice(0, n)), (ub, slice(n, 2 * n)))
-        g = ua.geom(x[:n])
+        g = self.geom(x)
         na, nb = ua.name, ub.name
         PA, PB = ua.net.P, ub.net.P
         fused_act = A.ACT_NONE if ua.norm else ua.act
@@ -867,8 +877,12 @@ class _PairUnit:
         sa, sb = ua.net.scratch_vec(K.cpad(ua.cout)), ub.net.scratch_vec(K.cpad(ub.cout))
         return (sa, sa, sb, sb)
 
-    def backward(self, rec, dy, want_dx=True, param_grads=True, addend=None):
+    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
+        """_ConvUnit.backward's signature and return convention ((dx, partial) when next_norm is given), with the lockstep
+        path's limits: gradients go to the networks' own buffers, the data-gradient epilogue never makes the next norm's
+        sums (fuse_in_bwd has no paired form: partial is None), and mixed mode runs one network at a time."""
         ua, ub = self.ua, self.ub
+        assert gbuf is None and dy_partial is None and not (ua.net.mixed or ub.net.mixed)
         g, x, xc, stats = rec
         n = x.shape[0] // 2
         na, nb = ua.name, ub.name
@@ -884,7 +898,8 @@ class _PairUnit:
             elif param_grads:
                 for u, sl in ((ua, slice(0, n)), (ub, slice(n, 2 * n))):
                     K.bias_grad(dxc[sl], u.net.P.g(u.name + "_b"), accumulate=True)
-        return self._conv_backward(g, x, dxc, want_dx, param_grads, addend)
+        dx = self._conv_backward(g, x, dxc, want_dx, param_grads, addend)
+        return (dx, None) if next_norm is not None else dx
 
     def _conv_backward(self, g, x, dxc, want_dx, param_grads, addend):
         """Weight gradients of both networks, then the stacked data gradient (+ addend)."""
@@ -933,6 +948,8 @@ class _PairSkipActUnit(_PairUnit):
     in the cycle step).  The convolution takes _PairUnit's paths; the norm is sgg_instnorm_*_skip_pair.  The forward record
     carries y, and backward returns (dx, dskip), both stacked."""
 
+    skip_grad = True
+
     def forward(self, x, residual=None, record_only=False, out=None):
         assert residual is not None and out is None and not record_only and self.ua.norm
         ua, ub = self.ua, self.ub
@@ -942,8 +959,8 @@ class _PairSkipActUnit(_PairUnit):
                                             x.shape[0] // 2, residual, ua.net.eps, ua.act, ua.leak, partial=part)
         return y, (g, x, xc, stats, y)
 
-    def backward(self, rec, dy, want_dx=True, param_grads=True, addend=None):
-        assert addend is None
+    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
+        assert gbuf is None and addend is None and dy_partial is None and next_norm is None
         ua, ub = self.ua, self.ub
         PA, PB = ua.net.P, ub.net.P
         g, x, xc, stats, y = rec
@@ -953,157 +970,47 @@ class _PairSkipActUnit(_PairUnit):
         return self._conv_backward(g, x, dxc, want_dx, param_grads, None), dskip
 
 
-class GeneratorPair:
-    """generator_resnet (module.py:219-269) of two generators in lockstep: forward([x_a; x_b]) = [G_a(x_a); G_b(x_b)]."""
+def _pair_units(xs, ys):
+    """The lockstep units of two networks' unit lists (a skip-gradient unit pairs into its own lockstep kind)."""
+    return [(_PairSkipActUnit if ua.skip_grad else _PairUnit)(ua, ub) for ua, ub in zip(xs, ys)]
+
+
+class GeneratorPair(_ResNetWalk):
+    """generator_resnet (module.py:219-269) of two generators in lockstep: forward([x_a; x_b]) = [G_a(x_a); G_b(x_b)] -- the
+    one ResNet walk over lockstep units, on stacked tensors."""
 
     def __init__(self, ga, gb):
         assert ga.n_blocks == gb.n_blocks
         self.a, self.b = ga, gb
-        P = _PairUnit
-        self.head = [P(ga.c1, gb.c1), P(ga.c2, gb.c2), P(ga.c3, gb.c3)]
-        self.blocks = [(P(xa, xb), P(ya, yb)) for (xa, ya), (xb, yb) in zip(ga.blocks, gb.blocks)]
-        self.tail = [P(ga.d1, gb.d1), P(ga.d2, gb.d2), P(ga.out, gb.out)]
+        self.head, self.tail = _pair_units(ga.head, gb.head), _pair_units(ga.tail, gb.tail)
+        self.blocks = [tuple(_pair_units(xa, xb)) for xa, xb in zip(ga.blocks, gb.blocks)]
 
-    def forward(self, x, out=None):
-        """out: buffer for the stacked result (the step hands in the middle of the discriminators' stacked input)."""
-        tape, h = [], x
-        for u in self.head:
-            h, r = u.forward(h)
-            tape.append(r)
-        ckpt = self.a.checkpoint_blocks or self.b.checkpoint_blocks
-        for ua, ub in self.blocks:
-            y, ra = ua.forward(h)
-            hin = h
-            h, rb = ub.forward(y, residual=h)             # IN(conv(y)) + x   (module.py:216-217)
-            tape.append(_BlockInput(hin) if ckpt else (ra, rb))
-        for u in self.tail:
-            h, r = u.forward(h, out=out if u is self.tail[-1] else None)
-            tape.append(r)
-        return h, tape
-
-    def _block_records(self, k, rec):
-        """Generator._block_records for the pair: recompute a checkpointed block from its saved (stacked) input."""
-        if not isinstance(rec, _BlockInput):
-            return rec
-        ua, ub = self.blocks[k]
-        y, ra = ua.forward(rec.x)
-        _, rb = ub.forward(y, residual=rec.x, record_only=True)
-        return ra, rb
-
-    def backward(self, tape, dy, want_dx=False, param_grads=True, on_unit_done=None, addend=None):
-        """on_unit_done(name), addend: as Generator.backward -- both networks of the pair finish a layer together."""
-        nb = len(self.blocks)
-        done = on_unit_done if on_unit_done is not None else (lambda name: None)
-        d = dy
-        for u, r in zip(reversed(self.tail), (tape[5 + nb], tape[4 + nb], tape[3 + nb])):
-            d = u.backward(r, d, True, param_grads)
-            done(u.ua.name)
-        for k in range(nb - 1, -1, -1):
-            ua, ub = self.blocks[k]
-            ra, rb = self._block_records(k, tape[3 + k])
-            t = ub.backward(rb, d, True, param_grads)
-            done(ub.ua.name)
-            d = ua.backward(ra, t, True, param_grads, addend=d)      # + skip gradient (fused into the data-gradient epilogue)
-            done(ua.ua.name)
-        d = self.head[2].backward(tape[2], d, True, param_grads)
-        done("c3")
-        d = self.head[1].backward(tape[1], d, True, param_grads)
-        done("c2")
-        d = self.head[0].backward(tape[0], d, want_dx, param_grads, addend=addend)
-        done("c1")
-        return d
+    @property
+    def checkpoint_blocks(self):
+        return self.a.checkpoint_blocks or self.b.checkpoint_blocks
 
 
-class GeneratorUNetPair:
-    """generator_unet (module.py:125-206) of two generators in lockstep: forward([x_a; x_b]) = [G_a(x_a); G_b(x_b)].  Layer for
-    layer GeneratorUNet.forward / backward on stacked tensors: the seven skips and their gradients stay stacked (the gradients
-    ride in the addend of the encoder convs' data-gradient store), every instance norm is one launch for both networks."""
+class GeneratorUNetPair(_UNetWalk):
+    """generator_unet (module.py:125-206) of two generators in lockstep: forward([x_a; x_b]) = [G_a(x_a); G_b(x_b)] -- the one
+    U-Net walk over lockstep units: the skips and their gradients stay stacked (the gradients ride in the addend of the encoder
+    convs' data-gradient store), every instance norm is one launch for both networks."""
 
     def __init__(self, ga, gb):
         self.a, self.b = ga, gb
-        self.enc = [_PairUnit(ua, ub) for ua, ub in zip(ga.enc, gb.enc)]
-        self.dec = [(_PairSkipActUnit if isinstance(ua, _SkipActUnit) else _PairUnit)(ua, ub) for ua, ub in zip(ga.dec, gb.dec)]
+        self.enc, self.dec = _pair_units(ga.enc, gb.enc), _pair_units(ga.dec, gb.dec)
         self.d8 = _PairUnit(ga.d8, gb.d8)
 
-    def forward(self, x, out=None):
-        """out: buffer for the stacked result (the step hands in the middle of the discriminators' stacked input)."""
-        tape, enc_out = [], []
-        h = x
-        for u in self.enc:
-            h, r = u.forward(h)
-            tape.append(r)
-            enc_out.append(h)
-        for j, u in enumerate(self.dec):                       # d(j+1) + e(7-j)
-            h, r = u.forward(h, residual=enc_out[6 - j])
-            tape.append(r)
-        h, r = self.d8.forward(h, out=out)
-        tape.append(r)
-        return h, tape
 
-    def backward(self, tape, dy, want_dx=False, param_grads=True, on_unit_done=None, addend=None):
-        """on_unit_done(name), addend: as GeneratorUNet.backward -- both networks of the pair finish a layer together."""
-        done = on_unit_done if on_unit_done is not None else (lambda name: None)
-        d = self.d8.backward(tape[15], dy, True, param_grads)
-        done("d8")
-        dskip = [None] * 7                                     # dskip[i]: stacked gradient reaching e(i+1)'s output through the skip
-        for j in range(6, -1, -1):
-            u = self.dec[j]
-            if isinstance(u, _PairSkipActUnit):
-                d, dskip[6 - j] = u.backward(tape[8 + j], d, True, param_grads)
-            else:
-                dskip[6 - j] = d
-                d = u.backward(tape[8 + j], d, True, param_grads)
-            done(u.ua.name)
-        for k in range(7, -1, -1):
-            u = self.enc[k]
-            if k:
-                d = u.backward(tape[k], d, True, param_grads, addend=dskip[k - 1])   # + skip gradient (fused store)
-                dskip[k - 1] = None
-            else:
-                d = u.backward(tape[0], d, want_dx, param_grads, addend=addend)
-            done(u.ua.name)
-        return d
-
-
-class DiscriminatorPair:
-    """discriminator (module.py:272-318) of two discriminators in lockstep on stacked images and masks."""
+class DiscriminatorPair(_DiscriminatorWalk):
+    """discriminator (module.py:272-318) of two discriminators in lockstep on stacked images and masks: the one discriminator
+    walk over lockstep units."""
 
     def __init__(self, da, db):
+        assert (da.segment_class, da.dtype) == (db.segment_class, db.dtype)
         self.a, self.b = da, db
-        self.units = [_PairUnit(ua, ub) for ua, ub in zip(da.units, db.units)]
+        self.segment_class, self.dtype = da.segment_class, da.dtype
+        self.units = _pair_units(da.units, db.units)
         self.h4 = _PairUnit(da.h4, db.h4)
-
-    def forward(self, x, mask):
-        tape, h = [], x
-        for u in self.units:
-            h, r = u.forward(h)
-            tape.append(r)
-        h4, r = self.h4.forward(h)
-        tape.append(r)
-        out = K.mask_reduce_fwd(h4, mask, self.a.segment_class)                    # module.py:312-314
-        tape.append((mask, tuple(h4.shape)))
-        return out, tape
-
-    def backward(self, tape, dlogits, want_dx=False, param_grads=True, addend=None):
-        mask, h4_shape = tape[-1]
-        d = K.mask_reduce_bwd(dlogits.contiguous(), mask, h4_shape, self.a.dtype, self.a.segment_class)
-        d = self.h4.backward(tape[-2], d, True, param_grads)
-        for i in range(len(self.units) - 1, -1, -1):
-            d = self.units[i].backward(tape[i], d, want_dx or i > 0, param_grads, addend=addend if i == 0 else None)
-        return d
-
-    def slice_tape(self, tape, lo, hi):
-        """The forward records of images [lo, hi) of a stacked pass, as views: a backward pass through PART of the batch (the
-        cycle step sends reals and fakes through the discriminators as one pass, the generators' loss only needs the fakes).
-        The slice must hold as many images of the first network as of the second."""
-        k = (hi - lo) // 2
-        out = []
-        for pu, (g, x, xc, stats) in zip(self.units + [self.h4], tape[:-1]):
-            xs = x[lo:hi]
-            out.append((pu.ua.geom(xs[:k]), xs, xc[lo:hi], None if stats is None else stats[lo:hi]))
-        mask, h4_shape = tape[-1]
-        out.append((mask[lo:hi], (hi - lo,) + tuple(h4_shape[1:])))
-        return out
 
 
 # ----------------------------------------------------------------------------- autograd facade
