@@ -408,6 +408,19 @@ int sgg_resample_f32(const float* src, int N, int H0, int W0, const int32_t* fli
  * labels[i] = argmax_c uint8(255*x[i][c]) over the first C_real channels (first maximum wins). */
 int sgg_confusion_hist(const int32_t* label_true, const int32_t* label_pred, int64_t n, int n_class, uint64_t* hist, void* stream);
 int sgg_argmax_u8_labels(const void* x, int32_t* labels, int64_t P, int C_real, int Cpad, int dtype, void* stream);
+/* ---- dense-CRF label refinement: metric.dense_crf (metric.py:49-69; pydensecrf's DenseCRF2D: unary_from_softmax,
+ * addPairwiseGaussian(sxy = pos_xy_std, compat = pos_w), addPairwiseBilateral(sxy = bi_xy_std, srgb = bi_rgb_std, compat = bi_w),
+ * Potts compatibility, NORMALIZE_SYMMETRIC, inference(max_iter)) with EXACT message passing over all (H*W)^2 pixel pairs
+ * (pydensecrf filters through a permutohedral lattice).  The pairwise kernel is never stored.
+ *   img (H,W,3) uint8;  exactly one of probs / unary is non-NULL, both (C,H,W) f32: probs -> U = -log(clip(p, 1e-5, 1)) taken
+ *   in double and rounded once to f32, unary -> U as given;  q_out (C,H,W) f32 = the marginals after max_iter mean-field steps
+ *   (0: softmax(-U)).  C <= 40, H*W <= 2^22 (else SGG_EUNSUPPORTED).  ws: sgg_dense_crf_workspace_bytes(H, W, C) bytes, 16-byte
+ *   aligned; a smaller one returns SGG_EWORKSPACE before anything is launched.  Fixed summation order, no atomics: the same
+ *   inputs give the same bits. */
+size_t sgg_dense_crf_workspace_bytes(int H, int W, int C);
+int sgg_dense_crf(const uint8_t* img, const float* probs, const float* unary, int H, int W, int C, int max_iter,
+                  float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out,
+                  void* ws, size_t ws_bytes, void* stream);
 /* f32 [P][Cs] -> dtype [P][Cd] with zero fill (Cd >= Cs), and back (drops padded channels). */
 int sgg_pad_channels(const float* src, void* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);
 int sgg_unpad_channels(const void* src, float* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);

@@ -119,6 +119,8 @@ SIGNATURES = {
     "sgg_resample_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sgg_confusion_hist": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "sgg_argmax_u8_labels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
+    "sgg_dense_crf_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sgg_dense_crf": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "sgg_pad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "sgg_unpad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
 }

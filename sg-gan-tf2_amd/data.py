@@ -583,9 +583,13 @@ class DirectoryBatches:
 def directory_test_samples(args, cache):
     """``samples(epoch)`` for ``test_during_train`` / ``test``: (name, image (H,W,3), colour label (H,W,3)) float32 in [0,1]
     through load_test_data's one-stage resize (utils.py:116-122).  The reference's ``resize(x, [H, W, 3])`` also interpolates
-    an RGBA label across its channel axis; here the first three channels are resized on their own (deviation D8)."""
+    an RGBA label across its channel axis; here the first three channels are resized on their own (deviation D8).
+    A cache built with ``with_class=True`` adds a fourth element: load_test_data's full-resolution one-hot class mask
+    (utils.py:146-150) as float32 (H,W,segment_class), through segment_class.one_hot_mask (deviation D1) -- what
+    ``test_during_train`` needs for its CRF scores (--crf)."""
     import torch
     from . import kernels as K
+    from .segment_class import one_hot_mask
 
     def gen(epoch=0):
         H, W = args.image_height, args.image_width
@@ -599,7 +603,12 @@ def directory_test_samples(args, cache):
                 rows, cols = _device_tables(test_tables(key[1], key[2], H, W), dev)
                 K.resample_u8(cache.stacks[key], torch.full_like(one, i), one, rows, cols, out, 3)
                 pair.append(K.unpad_channels(out, 3)[0].cpu().numpy())
-            yield os.path.basename(name), pair[0], pair[1]
+            if cache.classmap is None:
+                yield os.path.basename(name), pair[0], pair[1]
+            else:
+                key, i = cache.classmap[f]
+                mask = one_hot_mask(cache.stacks[key][i:i + 1], H, W, args.segment_class)
+                yield os.path.basename(name), pair[0], pair[1], mask[0].cpu().numpy()
     return gen
 
 

@@ -816,3 +816,31 @@ def unpad_channels(x, Cd):
     out = torch.empty(x.shape[:-1] + (Cd,), dtype=torch.float32, device=x.device)
     A.check(A.lib().sgg_unpad_channels(_p(x), _p(out), x.numel() // Cs, Cs, Cd, dt(x), _s()), "unpad_channels")
     return out
+
+
+# ----------------------------------------------------------------------------- dense CRF (metric.dense_crf)
+def dense_crf_workspace_bytes(H, W, C):
+    """Bytes of workspace sgg_dense_crf needs for a (C,H,W) problem; 0: the shape is not supported."""
+    return int(A.lib().sgg_dense_crf_workspace_bytes(int(H), int(W), int(C)))
+
+
+def dense_crf(img_u8, probs=None, unary=None, max_iter=10, pos_w=3.0, pos_xy_std=1.0, bi_w=4.0, bi_xy_std=67.0, bi_rgb_std=3.0,
+              out=None, workspace=None):
+    """Exact mean-field dense CRF (sgg_dense_crf): img_u8 (H,W,3) uint8 and either probs (C,H,W) f32 (the unary
+    -log(clip(p, 1e-5, 1)) is taken on the device) or a ready unary (C,H,W) f32 -> Q (C,H,W) f32 after max_iter steps.
+    ``workspace``: a uint8 device tensor of at least dense_crf_workspace_bytes(H, W, C) bytes (allocated when None)."""
+    assert (probs is None) != (unary is None), "give probs or unary, not both"
+    src = probs if unary is None else unary
+    C_, H, W = src.shape
+    assert img_u8.dtype == torch.uint8 and tuple(img_u8.shape) == (H, W, 3) and src.dtype == torch.float32
+    need = dense_crf_workspace_bytes(H, W, C_)
+    if need == 0:
+        A.check(A.EUNSUPPORTED, f"dense_crf {C_}x{H}x{W}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=src.device)
+    assert workspace.dtype == torch.uint8
+    out = _out(out, (C_, H, W), torch.float32, src.device)
+    A.check(A.lib().sgg_dense_crf(_p(img_u8), _p(probs), _p(unary), H, W, C_, int(max_iter), float(pos_w), float(pos_xy_std),
+                                  float(bi_w), float(bi_xy_std), float(bi_rgb_std), _p(out), _p(workspace), workspace.numel(), _s()),
+            "dense_crf")
+    return out

@@ -62,6 +62,9 @@ def build_parser():
     a("--augment", dest="augment", action="store_true",
       help="train on every sample and its augmented copy (flip / crop / affine, 2 x batch_size images per step): the reference's "
            "default --use_augmentation branch; that flag is type=bool and cannot be switched off, so it stays inert")
+    a("--crf", dest="crf", action="store_true",
+      help="epoch-end test pass: also score dense_crf(test image, class mask) against the class mask (metric.scores_mask_sample_crf) "
+           "and log the four scores as 'CRF ...' scalars; needs testA_seg_class beside testA")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 
@@ -99,7 +102,11 @@ def synthetic_test_samples(args, count=2):
         g = torch.Generator().manual_seed(1000 + epoch)
         H, W = args.image_height, args.image_width
         for i in range(count):
-            yield "synthetic_%03d.png" % i, torch.rand((H, W, 3), generator=g).numpy(), torch.rand((H, W, 3), generator=g).numpy()
+            item = ("synthetic_%03d.png" % i, torch.rand((H, W, 3), generator=g).numpy(), torch.rand((H, W, 3), generator=g).numpy())
+            if getattr(args, "crf", False):        # drawn after the triple, so the triple is what it is without --crf
+                idx = torch.randint(0, args.segment_class, (H, W), generator=g)
+                item += (torch.nn.functional.one_hot(idx, args.segment_class).float().numpy(),)
+            yield item
     return gen
 
 
@@ -136,7 +143,7 @@ def directory_sources(model, args, log=print):
     batches = D.DirectoryBatches(model, args, cache_A, cache_B, augment=augment)
     tests = None
     if os.path.isdir(os.path.join(root, "testA")):
-        tests = D.directory_test_samples(args, D.DatasetCache(root, "testA", device=dev, with_class=False))
+        tests = D.directory_test_samples(args, D.DatasetCache(root, "testA", device=dev, with_class=bool(getattr(args, "crf", False))))
     return batches, tests
 
 

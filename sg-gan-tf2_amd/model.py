@@ -31,7 +31,8 @@ def default_args(**over):
              use_lsgan=True, ratio_gan2seg=10, max_size=50, phase="train", dataset_dir="city",
              dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=None,
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
-             checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False)
+             checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
+             crf=False)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -649,19 +650,38 @@ class sggan(object):
         self.load_state_dict(sd)
         return True
 
+    def get_labels(self, test_label, pred_img, crf=False):
+        """model.py:278-305: (lt, lp) for the label plots.  crf=False: both transposed to (N,C,W,H) (model.py:302-303).
+        crf=True (crf_wrapper, model.py:282-296): lt = uint8(255 * test_label) as it is, lp = dense_crf(lt[0], pred_img
+        transposed to (C,W,H)) with a leading axis of one; like the reference's call this needs H == W."""
+        from . import metric as M
+        as_np = lambda x: x.numpy() if hasattr(x, "numpy") else np.asarray(x)
+        if crf:
+            image = (as_np(test_label) * 255).astype(np.uint8)
+            lp = as_np(pred_img).transpose(0, 3, 2, 1)[0]
+            return image, np.expand_dims(M.dense_crf(image[0], lp), axis=0)
+        return as_np(test_label).transpose(0, 3, 2, 1), as_np(pred_img).transpose(0, 3, 2, 1)
+
     def test_during_train(self, epoch, args, samples, sink=None):
-        """model.py:307-448 (the live part: the CRF variants are commented out there and pydensecrf is out of scope): every
+        """model.py:307-448 (the live part; of the CRF variants, commented out there, scores_mask_sample_crf runs with --crf): every
         test sample -- ``samples`` yields (name, sample_image (H,W,3) in [0,1], seg_image (H,W,3) in [0,1]); reading and
         resizing the files (utils.load_test_data) stays on the caller's side -- is rescaled like the reference does
         (tf.image.convert_image_dtype -> uint8 -> float32), translated by the generator, optionally saved under
         ``args.test_dir``, and labelled against its segmentation image (metric.scores_seg_fake); the FCN scores of all labels
-        go to ``sink`` under the reference's scalar names.  Returns (the stacked fake images as model.py:440-448 does, scores)."""
+        go to ``sink`` under the reference's scalar names.  Returns (the stacked fake images as model.py:440-448 does, scores).
+        With ``args.crf`` the samples carry a fourth element, load_test_data's full-resolution one-hot class mask (H,W,C), each
+        is also scored by metric.scores_mask_sample_crf (model.py:314-315 keeps the lists for it), and the four FCN scores of
+        those labels follow the reference's four in ``sink`` as 'CRF Overall Accuracy' ... 'CRF Mean IoU' (and in the returned
+        scores under "CRF")."""
         from . import metric as M
         from .utils import convert_image_dtype_uint8, get_img, save_images
         import os
         gts, preds, outputs = [], [], []
+        crf = bool(getattr(args, "crf", False))
+        gts2, preds2 = [], []
         test_dir = getattr(args, "test_dir", None)
-        for name, sample_image, seg_image in samples:
+        for item in samples:
+            name, sample_image, seg_image = item[:3]
             rescaled = convert_image_dtype_uint8(np.asarray(sample_image)[None])                 # :352-353
             fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))                   # :357
             if test_dir:
@@ -671,12 +691,25 @@ class sggan(object):
             outputs.append(fake_img)
             lt, lp = M.scores_seg_fake(np.asarray(seg_image, dtype=np.float32)[None], torch.as_tensor(fake_img.astype(np.float32)))   # :373
             preds += list(lp); gts += list(lt)
+            if crf:
+                if len(item) < 4:
+                    raise ValueError("crf: test samples must carry the one-hot class mask (data.directory_test_samples over a "
+                                     "DatasetCache(with_class=True))")
+                lt2, lp2 = M.scores_mask_sample_crf(np.asarray(item[3])[None], rescaled)          # :330,338 seg_mask_64
+                preds2 += list(lp2); gts2 += list(lt2)
         score = M.scores(gts, preds, n_class=args.segment_class)                                 # :378
         if sink is not None:                                                                     # :389-393
             sink.scalar("Overall Accuracy", score["Overall Acc"], epoch)
             sink.scalar("Mean Accuracy", score["Mean Acc"], epoch)
             sink.scalar("Frequency Weighted Accuracy", score["FreqW Acc"], epoch)
             sink.scalar("Mean IoU", score["Mean IoU"], epoch)
+        if crf:
+            score["CRF"] = crf_score = M.scores(gts2, preds2, n_class=args.segment_class)
+            if sink is not None:
+                sink.scalar("CRF Overall Accuracy", crf_score["Overall Acc"], epoch)
+                sink.scalar("CRF Mean Accuracy", crf_score["Mean Acc"], epoch)
+                sink.scalar("CRF Frequency Weighted Accuracy", crf_score["FreqW Acc"], epoch)
+                sink.scalar("CRF Mean IoU", crf_score["Mean IoU"], epoch)
         return (np.concatenate(outputs, axis=0) if outputs else None), score
 
     def test(self, args, samples, log=print):
