@@ -356,6 +356,14 @@ int sgg_adam(float* theta, const float* g, float* m, float* v, int64_t n, int t,
  * graph and replayed (the eager per-op dispatch of model.py:168 is what this removes). */
 int sgg_adam_iter(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, float lr, float beta1,
                   float beta2, float eps, float grad_scale, void* stream);
+/* sgg_adam_iter with the reference's linear learning-rate decay (model.py:223) evaluated by the 1-thread launch:
+ * `sched` is int64[3] on the DEVICE = {steps_per_epoch, epoch_step, epochs}, read when the launch RUNS (it may be written
+ * after the call was captured into a HIP graph).  With e = state[0] / steps_per_epoch (steps_per_epoch clamped to >= 1):
+ *   lr_e = lr                                               if epochs <= epoch_step or e < epoch_step
+ *   lr_e = (float)(lr * max(epochs - e, 0) / (epochs - epoch_step))   otherwise (in double, one rounding to f32);
+ * the update is sgg_adam_iter's with lr_e in place of lr (bit-identical to it).  {1, 0, 0} never decays. */
+int sgg_adam_sched(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched,
+                   float lr, float beta1, float beta2, float eps, float grad_scale, void* stream);
 
 /* ---- data side of the step ----
  * segment_class.py:60-70,95-97: colour -> class index, bit exact.  rgb: uint8 [n_pixels][channels>=3]. */

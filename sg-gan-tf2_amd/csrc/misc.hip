@@ -427,6 +427,25 @@ __global__ void adam_prep_kernel(int64_t* state, float lr, float b1, float b2) {
     state[0] += 1;
     reinterpret_cast<float*>(state + 1)[0] = lr_t;
 }
+// The prep launch of sgg_adam_sched: the same, with the base rate first put through the reference's linear decay
+// (model.py:223, commented out there).  The epoch is iterations / steps_per_epoch, and `sched` = {steps_per_epoch,
+// epoch_step, epochs} is read from device memory at run time -- never a kernel argument -- so a captured launch follows a
+// descriptor that is written after the capture.  lr_e is rounded to f32 once (what a Keras learning_rate.assign would
+// hold); from there on the arithmetic is adam_prep_kernel's, so the pair is bit-identical to sgg_adam_iter given lr_e.
+__global__ void adam_sched_prep_kernel(int64_t* state, const int64_t* sched, float lr, float b1, float b2) {
+    const int64_t it = state[0];
+    const int64_t spe = sched[0] < 1 ? 1 : sched[0], epoch_step = sched[1], epochs = sched[2];
+    const int64_t e = it / spe;
+    float lr_e = lr;
+    if (!(epochs <= epoch_step || e < epoch_step)) {
+        const int64_t left = epochs - e > 0 ? epochs - e : 0;
+        lr_e = (float)(((double)lr * (double)left) / (double)(epochs - epoch_step));
+    }
+    const double t = (double)(it + 1);
+    const float lr_t = (float)((double)lr_e * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+    state[0] = it + 1;
+    reinterpret_cast<float*>(state + 1)[0] = lr_t;
+}
 __global__ __launch_bounds__(256) void adam_iter_kernel(float* th, const float* g, float* m, float* v, int64_t n, const int64_t* state,
                                                         float b1, float b2, float eps, float gs) {
     const float lr_t = reinterpret_cast<const float*>(state + 1)[0];
@@ -752,6 +771,17 @@ int sgg_adam_iter(float* theta, const float* g, float* m, float* v, int64_t n, i
                   float eps, float grad_scale, void* stream) {
     if (!theta || !g || !m || !v || !state || n < 0) return SGG_EINVAL;
     hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2);
+    int rc = sgg_check_launch();
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(adam_iter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n, (const int64_t*)state,
+                       beta1, beta2, eps, grad_scale);
+    return sgg_check_launch();
+}
+
+int sgg_adam_sched(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched, float lr,
+                   float beta1, float beta2, float eps, float grad_scale, void* stream) {
+    if (!theta || !g || !m || !v || !state || !sched || n < 0) return SGG_EINVAL;
+    hipLaunchKernelGGL(adam_sched_prep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, sched, lr, beta1, beta2);
     int rc = sgg_check_launch();
     if (rc || n == 0) return rc;
     hipLaunchKernelGGL(adam_iter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n, (const int64_t*)state,

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 
+import numpy as np
 import torch
 
 from . import _abi as A
@@ -739,6 +740,30 @@ def adam_iter(theta, g, m, v, state, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, 
     assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
     assert state.dtype == torch.int64 and state.numel() == 2
     A.check(A.lib().sgg_adam_iter(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(state), lr, beta1, beta2, eps, grad_scale, _s()), "adam_iter")
+
+
+def adam_sched(theta, g, m, v, state, sched, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0):
+    """``adam_iter`` with the base rate ``lr`` put through the linear decay of model.py:223 on the device: ``sched`` is a device
+    int64[3] = [steps_per_epoch, epoch_step, epochs], read when the launch runs (``scheduled_lr`` states the rule)."""
+    assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
+    assert state.dtype == torch.int64 and state.numel() == 2
+    assert sched.dtype == torch.int64 and sched.numel() == 3
+    A.check(A.lib().sgg_adam_sched(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(state), _p(sched), lr, beta1, beta2, eps, grad_scale, _s()),
+            "adam_sched")
+
+
+def scheduled_lr(lr, iterations, steps_per_epoch, epoch_step, epochs):
+    """The rate ``adam_sched`` applies at step number ``iterations`` (0-based: the counter before the update), as np.float32 --
+    the kernel's rule in the kernel's order of evaluation, on the host (logging, tests):
+    ``lr if epoch < epoch_step else lr*(epochs-epoch)/(epochs-epoch_step)`` (model.py:223) with epoch = iterations //
+    steps_per_epoch, clamped at 0 past the last epoch.  ``lr`` enters as the f32 the kernel receives; the decayed rate is
+    evaluated in double and rounded to f32 once."""
+    lr = np.float32(lr)
+    iterations, epoch_step, epochs = int(iterations), int(epoch_step), int(epochs)
+    e = iterations // max(int(steps_per_epoch), 1)
+    if epochs <= epoch_step or e < epoch_step:
+        return lr
+    return np.float32((float(lr) * float(max(epochs - e, 0))) / float(epochs - epoch_step))
 
 
 # ----------------------------------------------------------------------------- data side

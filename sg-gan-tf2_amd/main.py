@@ -65,6 +65,11 @@ def build_parser():
     a("--crf", dest="crf", action="store_true",
       help="epoch-end test pass: also score dense_crf(test image, class mask) against the class mask (metric.scores_mask_sample_crf) "
            "and log the four scores as 'CRF ...' scalars; needs testA_seg_class beside testA")
+    a("--lr_decay", dest="lr_decay", action="store_true",
+      help="linear learning-rate decay, the rule --epoch_step was written for (model.py:223): "
+           "lr if epoch < epoch_step else lr*(epoch_total-epoch)/(epoch_total-epoch_step), with epoch_total = --epoch and lr = --lr "
+           "in --cycle mode (the reference-mode step's hard-coded 1e-3 otherwise); evaluated on the device from each optimizer's step "
+           "counter (epoch = iterations // steps per epoch), so it survives graph replay and goes on after --continue_train")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 

@@ -32,7 +32,7 @@ def default_args(**over):
              dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=None,
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
-             crf=False)
+             crf=False, lr_decay=False)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -102,11 +102,18 @@ class sggan(object):
         # model.py:83-84 / 205-207: one Keras Adam per network (lr hard-coded 1e-3 on the live step; the cycle step
         # uses --lr).  d_optim / g_optim are the reference's attribute names; the cycle step adds the other two.
         lr = self.cycle_lr if self.cycle else self.lr
-        self.g_optim = Adam(self.generator, lr, self.beta1)
-        self.d_optim = Adam(self.discriminator, lr, self.beta1)
+        # lr_decay: the linear decay of model.py:223 (commented out there), evaluated on the device by every optimizer's update
+        # from its own step counter and ONE descriptor [steps_per_epoch, epoch_step, epochs] all of them share.  It exists
+        # from here on and starts as "never decays", so a step recorded before train() carries its address;
+        # set_lr_schedule only writes into it.  Each optimizer's learning_rate is the base rate.
+        self.lr_decay = bool(g("lr_decay", False))
+        self._lr_sched = torch.tensor([1, 0, 0], dtype=torch.int64, device=self.device) if self.lr_decay else None
+        self._lr_sched_host = (1, 0, 0)
+        self.g_optim = Adam(self.generator, lr, self.beta1, schedule=self._lr_sched)
+        self.d_optim = Adam(self.discriminator, lr, self.beta1, schedule=self._lr_sched)
         if self.cycle:
-            self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1)
-            self.d_optim_B = Adam(self.discriminator_B, lr, self.beta1)
+            self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1, schedule=self._lr_sched)
+            self.d_optim_B = Adam(self.discriminator_B, lr, self.beta1, schedule=self._lr_sched)
         # cycle step: run the two generators (and the two discriminators) in lockstep on stacked batches (module._PairUnit);
         # bit-identical to the one-network-at-a-time sequencing, which stays for the image pool and for mixed mode.  paired=None
         # picks the default: on for the ResNet (the step bench.py times); off for the U-Net, whose step is bound by
@@ -387,6 +394,18 @@ class sggan(object):
             if h is not None:
                 h.wait()
             opt.apply_gradients(grad_scale=scale)
+
+    def set_lr_schedule(self, steps_per_epoch, epoch_step, epochs):
+        """The decay's parameters (``lr_decay`` models only): the base rate until epoch ``epoch_step``, then linearly down to 0
+        at epoch ``epochs`` (model.py:223), where an optimizer's epoch is its ``iterations // steps_per_epoch`` -- so a run
+        resumed from a checkpoint goes on decaying where it stopped.  Only writes the device descriptor the updates read:
+        recorded steps follow it without being recorded again."""
+        if self._lr_sched is None:
+            raise RuntimeError("set_lr_schedule: this model was built without lr_decay")
+        sched = (max(int(steps_per_epoch), 1), int(epoch_step), int(epochs))
+        self._lr_sched.copy_(torch.tensor(sched, dtype=torch.int64))
+        self._lr_sched_host = sched
+        return self
 
     def networks(self):
         return (self.generator, self.discriminator) + ((self.generator_BA, self.discriminator_B) if self.cycle else ())
@@ -753,6 +772,8 @@ class sggan(object):
                 data = batches(epoch)
                 if not hasattr(data, "__len__"):       # a sized source (data.DirectoryBatches) refills its buffers per step: keep it lazy
                     data = list(data)
+                if self.lr_decay:
+                    self.set_lr_schedule(len(data), args.epoch_step, args.epoch)
                 for idx, b in enumerate(data):
                     for k, v in b.items():
                         setattr(self, k, v)
@@ -770,6 +791,9 @@ class sggan(object):
                 if sink is not None:
                     sink.scalar("Generator Loss", self.gen_loss_metric, epoch)
                     sink.scalar("Discriminator Loss", self.disc_loss_metric, epoch)
+                    if self.lr_decay:              # the rate the generator's last update of this epoch applied
+                        last = max(self.g_optim.iterations.item() - 1, 0)
+                        sink.scalar("Learning Rate", float(K.scheduled_lr(self.g_optim.learning_rate, last, *self._lr_sched_host)), epoch)
                 history.append({"epoch": epoch, "Generator Loss": self.gen_loss_metric, "Discriminator Loss": self.disc_loss_metric})
         finally:
             if getattr(args, "checkpoint_dir", None):

@@ -113,9 +113,14 @@ class ParamStore:
     def zero_grad(self):
         self.grad.zero_()
 
-    def adam_step(self, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0):
-        """tf.keras.optimizers.Adam.apply_gradients (model.py:199-200) over the whole network: one launch."""
-        K.adam_iter(self.flat, self.grad, self.m, self.v, self._adam_state, lr, beta1, beta2, eps, grad_scale)
+    def adam_step(self, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, schedule=None):
+        """tf.keras.optimizers.Adam.apply_gradients (model.py:199-200) over the whole network: one launch.  ``schedule``: a
+        device int64[3] [steps_per_epoch, epoch_step, epochs] -- ``lr`` is then the base rate of the linear decay of
+        model.py:223, evaluated on the device from ``iterations`` (K.adam_sched); None: ``lr`` as it is."""
+        if schedule is None:
+            K.adam_iter(self.flat, self.grad, self.m, self.v, self._adam_state, lr, beta1, beta2, eps, grad_scale)
+        else:
+            K.adam_sched(self.flat, self.grad, self.m, self.v, self._adam_state, schedule, lr, beta1, beta2, eps, grad_scale)
         self.version += 1
 
 
@@ -123,8 +128,11 @@ class Adam:
     """``tf.keras.optimizers.Adam`` as the reference holds it in ``self.g_optim`` / ``self.d_optim`` (model.py:83-84,
     199-200, 205-207), bound to one network's flat parameter store: the whole update is one fused launch."""
 
-    def __init__(self, net, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+    def __init__(self, net, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule=None):
         self.net, self.learning_rate, self.beta_1, self.beta_2, self.epsilon = net, learning_rate, beta_1, beta_2, epsilon
+        # device int64[3] [steps_per_epoch, epoch_step, epochs] or None (ParamStore.adam_step): with it, learning_rate is the
+        # base rate of the linear decay
+        self.schedule = schedule
 
     @property
     def iterations(self):
@@ -145,7 +153,7 @@ class Adam:
                     raise ValueError("apply_gradients: variable does not belong to this optimizer's network")
                 if g is not None:
                     P.g(name).copy_(torch.as_tensor(g, device=P.device).reshape(P.g(name).shape))
-        P.adam_step(self.learning_rate, self.beta_1, self.beta_2, self.epsilon, grad_scale)
+        P.adam_step(self.learning_rate, self.beta_1, self.beta_2, self.epsilon, grad_scale, self.schedule)
 
 
 def _layer_specs(name, shape, out_ch, norm=True):
