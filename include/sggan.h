@@ -364,6 +364,26 @@ int sgg_adam_iter(float* theta, const float* g, float* m, float* v, int64_t n, i
  * the update is sgg_adam_iter's with lr_e in place of lr (bit-identical to it).  {1, 0, 0} never decays. */
 int sgg_adam_sched(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched,
                    float lr, float beta1, float beta2, float eps, float grad_scale, void* stream);
+/* Guarded update (no counterpart in the reference): the global L2 norm of the gradient is measured on the
+ * device, the gradient is clipped to max_norm, and an update whose gradient holds a NaN or +-Inf is skipped.
+ *   sgg_grad_sumsq: one pass over g (16-byte aligned, any n > 0).  Every 8192-element chunk leaves a 16-byte record
+ *     {double sum of squares, uint32 non-finite flag, 0} at ws + 16 + 16 * chunk; the flag tests the bit pattern (exponent
+ *     all ones).  Fixed summation order, no atomics; the chunking depends on n only.
+ *   sgg_adam_guard: that pass, a 1-block launch that folds the records in a fixed order and decides, then the update.
+ *       norm = sqrt(sum) * grad_scale         (double)
+ *       skip = any flag set
+ *       clip = 1 if max_norm <= 0 or norm <= max_norm, else (float)(max_norm / norm)      (1 on skip)
+ *     Not skipped: sgg_adam_sched's step (sched == NULL: sgg_adam_iter's) with g * (grad_scale * clip), the factor formed
+ *     once in f32 -- with clip == 1 bit-identical to those calls.  Skipped: theta, m, v and state[0] keep their bits and
+ *     the scratch rate is written as 0.  guard is double[4] on the DEVICE = {last_norm, last_clip, skipped_total,
+ *     applied_total}, read and written by the launches only (the call can be captured; max_norm is a launch argument).
+ *   ws: sgg_grad_guard_workspace(n) bytes, 16-byte aligned (its first 16 bytes carry the decision to the update launch);
+ *   a smaller one returns SGG_EWORKSPACE before anything is launched; NULL pointers or n <= 0 return SGG_EINVAL. */
+size_t sgg_grad_guard_workspace(int64_t n);
+int sgg_grad_sumsq(const float* g, int64_t n, void* ws, size_t ws_bytes, void* stream);
+int sgg_adam_guard(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched,
+                   float lr, float beta1, float beta2, float eps, float grad_scale, float max_norm, double* guard,
+                   void* ws, size_t ws_bytes, void* stream);
 
 /* ---- data side of the step ----
  * segment_class.py:60-70,95-97: colour -> class index, bit exact.  rgb: uint8 [n_pixels][channels>=3]. */

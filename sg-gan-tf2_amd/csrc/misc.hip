@@ -405,15 +405,37 @@ __global__ __launch_bounds__(256) void l1_final_kernel(const float* partial, int
 }
 
 // ---------------------------------------------------------------- Adam (Keras form), flat buffer
+// one element of the update (every Adam kernel below goes through it, so their results are the same bits)
+__device__ __forceinline__ void adam_apply(float* th, const float* g, float* m, float* v, int64_t i, float lr_t, float b1, float b2,
+                                           float eps, float gs) {
+    float gi = g[i] * gs;
+    float mi = b1 * m[i] + (1.f - b1) * gi;
+    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    th[i] = th[i] - lr_t * mi / (sqrtf(vi) + eps);
+}
 __global__ __launch_bounds__(256) void adam_kernel(float* th, const float* g, float* m, float* v, int64_t n, float lr_t,
                                                    float b1, float b2, float eps, float gs) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gi = g[i] * gs;
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        th[i] = th[i] - lr_t * mi / (sqrtf(vi) + eps);
+        adam_apply(th, g, m, v, i, lr_t, b1, b2, eps, gs);
     }
+}
+
+// The two pieces of the prep launches' arithmetic (below), shared by all of them so that they cannot drift apart: the
+// bias-corrected rate of step t, and the linear decay of the base rate.
+__device__ inline float adam_lr_t(float lr, int64_t t_, float b1, float b2) {
+    const double t = (double)t_;
+    return (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+}
+__device__ inline float adam_sched_rate(int64_t it, const int64_t* sched, float lr) {
+    const int64_t spe = sched[0] < 1 ? 1 : sched[0], epoch_step = sched[1], epochs = sched[2];
+    const int64_t e = it / spe;
+    float lr_e = lr;
+    if (!(epochs <= epoch_step || e < epoch_step)) {
+        const int64_t left = epochs - e > 0 ? epochs - e : 0;
+        lr_e = (float)(((double)lr * (double)left) / (double)(epochs - epoch_step));
+    }
+    return lr_e;
 }
 
 // Same update with the step number read from a device-resident counter (Keras keeps `optimizer.iterations` as a variable
@@ -422,8 +444,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* th, const float* g, fl
 // counter; the update kernel reads the float.  The host never touches t, so the pair of launches can sit inside a captured
 // HIP graph and be replayed.  (Evaluating pow() in every block of the update kernel cost +18 us per launch.)
 __global__ void adam_prep_kernel(int64_t* state, float lr, float b1, float b2) {
-    const double t = (double)(state[0] + 1);
-    const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+    const float lr_t = adam_lr_t(lr, state[0] + 1, b1, b2);
     state[0] += 1;
     reinterpret_cast<float*>(state + 1)[0] = lr_t;
 }
@@ -434,15 +455,7 @@ __global__ void adam_prep_kernel(int64_t* state, float lr, float b1, float b2) {
 // hold); from there on the arithmetic is adam_prep_kernel's, so the pair is bit-identical to sgg_adam_iter given lr_e.
 __global__ void adam_sched_prep_kernel(int64_t* state, const int64_t* sched, float lr, float b1, float b2) {
     const int64_t it = state[0];
-    const int64_t spe = sched[0] < 1 ? 1 : sched[0], epoch_step = sched[1], epochs = sched[2];
-    const int64_t e = it / spe;
-    float lr_e = lr;
-    if (!(epochs <= epoch_step || e < epoch_step)) {
-        const int64_t left = epochs - e > 0 ? epochs - e : 0;
-        lr_e = (float)(((double)lr * (double)left) / (double)(epochs - epoch_step));
-    }
-    const double t = (double)(it + 1);
-    const float lr_t = (float)((double)lr_e * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+    const float lr_t = adam_lr_t(adam_sched_rate(it, sched, lr), it + 1, b1, b2);
     state[0] = it + 1;
     reinterpret_cast<float*>(state + 1)[0] = lr_t;
 }
@@ -450,12 +463,112 @@ __global__ __launch_bounds__(256) void adam_iter_kernel(float* th, const float* 
                                                         float b1, float b2, float eps, float gs) {
     const float lr_t = reinterpret_cast<const float*>(state + 1)[0];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gi = g[i] * gs;
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        th[i] = th[i] - lr_t * mi / (sqrtf(vi) + eps);
+        adam_apply(th, g, m, v, i, lr_t, b1, b2, eps, gs);
     }
+}
+
+// ---------------------------------------------------------------- guarded Adam: global gradient norm, clip, non-finite skip
+// Three launches, nothing on the host, no atomics (two runs give the same bits):
+//   gradsq_partial_kernel   one pass over the gradient: per GSQ_CHUNK elements a sum of squares (double) and a non-finite flag
+//   adam_guard_prep_kernel  folds the chunk records in a fixed order; ONE thread then decides skip / clip / lr_t
+//   adam_guard_kernel       adam_iter_kernel's update with g * (grad_scale * clip); returns at once on skip
+// Workspace: a 16-byte decision header {u32 skip, f32 grad_scale * clip, 0, 0} followed by one 16-byte record per chunk.
+// The chunk is a constant and the grid is ceil(n / GSQ_CHUNK): neither depends on the device, so neither does the sum.
+#define GSQ_CHUNK 8192
+struct GsqPartial { double sumsq; uint32_t bad, pad; };
+static_assert(sizeof(GsqPartial) == 16, "one 16-byte record per chunk");
+static inline int64_t gsq_chunks(int64_t n) { return (n + GSQ_CHUNK - 1) / GSQ_CHUNK; }
+
+__device__ __forceinline__ void gsq_acc(const u32x4& c, double& s, uint32_t& bad) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        // NaN / +-Inf by the bit pattern (exponent all ones): a finite sum that overflows is not "non-finite"
+        bad |= (c[e] & 0x7f800000u) == 0x7f800000u;
+        const double x = (double)__uint_as_float(c[e]);
+        s += x * x;                                             // (an f32 squared is exact in double)
+    }
+}
+__global__ __launch_bounds__(256) void gradsq_partial_kernel(const float* g, int64_t n, GsqPartial* part) {
+    const int64_t e0 = (int64_t)blockIdx.x * GSQ_CHUNK;
+    const int64_t e1 = e0 + GSQ_CHUNK < n ? e0 + GSQ_CHUNK : n;
+    const int64_t v1 = e0 + ((e1 - e0) & ~(int64_t)3);          // end of the chunk's whole 16-byte groups (e0 is a multiple of 4)
+    double s = 0.0;
+    uint32_t bad = 0;
+    // thread t takes the 16-byte groups t, t + 256, ... of the chunk in that order.  A whole chunk (every block but the last)
+    // issues its 8 loads back to back -- 32 KiB in flight per block -- before the first is consumed; the last chunk walks
+    // what it has, then the n % 4 scalar tail.  Same order either way, so a chunk's sum does not depend on which path ran.
+    if (e1 - e0 == GSQ_CHUNK) {
+        u32x4 c[GSQ_CHUNK / 1024];
+#pragma unroll
+        for (int u = 0; u < GSQ_CHUNK / 1024; ++u) c[u] = ld16(g + e0 + 4 * (threadIdx.x + 256 * u));
+#pragma unroll
+        for (int u = 0; u < GSQ_CHUNK / 1024; ++u) gsq_acc(c[u], s, bad);
+    } else {
+        for (int64_t i = e0 + 4 * threadIdx.x; i + 4 <= v1; i += 1024) gsq_acc(ld16(g + i), s, bad);
+        if (v1 + threadIdx.x < e1) {
+            u32x4 c = zero16();                                 // (+0.0 squared adds nothing and sets no flag)
+            c[0] = __float_as_uint(g[v1 + threadIdx.x]);
+            gsq_acc(c, s, bad);
+        }
+    }
+    __shared__ double red[256];
+    __shared__ uint32_t flag[256];
+    red[threadIdx.x] = s; flag[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { red[threadIdx.x] += red[threadIdx.x + o]; flag[threadIdx.x] |= flag[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { GsqPartial r; r.sumsq = red[0]; r.bad = flag[0]; r.pad = 0; part[blockIdx.x] = r; }
+}
+
+// One block.  Its 256 threads fold the chunk records (thread k takes records k, k + 256, ... in order, then the same fixed
+// tree as above): a single thread walking the 1 400 - 2 700 records of a generator one dependent load after the other would
+// take longer than the pass that made them (cf. colsum_final_kernel).  Thread 0 alone then decides, in double:
+//   norm = sqrt(sumsq) * grad_scale;   skip = any flag;   clip = 1 if max_norm <= 0 or norm <= max_norm, else
+//   (float)(max_norm / norm);   lr_t as adam_prep_kernel / adam_sched_prep_kernel (sched == NULL: no decay).
+// On skip `iterations` stays, lr_t = 0 and clip = 1 are written, and the update kernel returns at once; bias correction and
+// the decay's epoch count therefore follow APPLIED updates.  guard = {last_norm, last_clip, skipped_total, applied_total}.
+__global__ __launch_bounds__(256) void adam_guard_prep_kernel(int64_t* state, const int64_t* sched, const GsqPartial* part, int chunks,
+                                                              uint32_t* head, double* guard, float lr, float b1, float b2, float gs,
+                                                              float max_norm) {
+    __shared__ double red[256];
+    __shared__ uint32_t flag[256];
+    double s = 0.0;
+    uint32_t bad = 0;
+    for (int k = threadIdx.x; k < chunks; k += 256) { const GsqPartial r = part[k]; s += r.sumsq; bad |= r.bad; }
+    red[threadIdx.x] = s; flag[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { red[threadIdx.x] += red[threadIdx.x + o]; flag[threadIdx.x] |= flag[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(red[0]) * (double)gs;
+    const bool skip = flag[0] != 0;
+    float clip = 1.f;
+    if (!skip && max_norm > 0.f && !(norm <= (double)max_norm)) clip = (float)((double)max_norm / norm);
+    float lr_t = 0.f;
+    if (!skip) {
+        const int64_t it = state[0];
+        lr_t = adam_lr_t(sched ? adam_sched_rate(it, sched, lr) : lr, it + 1, b1, b2);
+        state[0] = it + 1;
+    }
+    reinterpret_cast<float*>(state + 1)[0] = lr_t;
+    head[0] = skip ? 1u : 0u;
+    head[1] = __float_as_uint(gs * clip);                       // the update's gradient factor, formed once in f32
+    head[2] = 0u; head[3] = 0u;
+    guard[0] = norm; guard[1] = (double)clip;
+    guard[2] += skip ? 1.0 : 0.0; guard[3] += skip ? 0.0 : 1.0;
+}
+
+__global__ __launch_bounds__(256) void adam_guard_kernel(float* th, const float* g, float* m, float* v, int64_t n, const int64_t* state,
+                                                         const uint32_t* head, float b1, float b2, float eps) {
+    if (head[0]) return;                                        // skipped step: theta, m and v keep their bits
+    const float lr_t = reinterpret_cast<const float*>(state + 1)[0];
+    const float gs = __uint_as_float(head[1]);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adam_apply(th, g, m, v, i, lr_t, b1, b2, eps, gs);
 }
 
 // ---------------------------------------------------------------- colour -> class index (integer, bit exact)
@@ -786,6 +899,38 @@ int sgg_adam_sched(float* theta, const float* g, float* m, float* v, int64_t n, 
     if (rc || n == 0) return rc;
     hipLaunchKernelGGL(adam_iter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n, (const int64_t*)state,
                        beta1, beta2, eps, grad_scale);
+    return sgg_check_launch();
+}
+
+size_t sgg_grad_guard_workspace(int64_t n) {
+    if (n <= 0) return 0;
+    return 16 + (size_t)gsq_chunks(n) * sizeof(GsqPartial);
+}
+static int grad_guard_args(const float* g, int64_t n, void* ws, size_t ws_bytes) {
+    if (!g || !ws || n <= 0 || ((uintptr_t)g & 15) || ((uintptr_t)ws & 15) || gsq_chunks(n) > 0x7fffffff) return SGG_EINVAL;
+    if (ws_bytes < sgg_grad_guard_workspace(n)) return SGG_EWORKSPACE;
+    return SGG_OK;
+}
+int sgg_grad_sumsq(const float* g, int64_t n, void* ws, size_t ws_bytes, void* stream) {
+    int rc = grad_guard_args(g, n, ws, ws_bytes);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gradsq_partial_kernel, dim3((unsigned)gsq_chunks(n)), dim3(256), 0, (hipStream_t)stream, g, n,
+                       reinterpret_cast<GsqPartial*>((char*)ws + 16));
+    return sgg_check_launch();
+}
+int sgg_adam_guard(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched, float lr,
+                   float beta1, float beta2, float eps, float grad_scale, float max_norm, double* guard, void* ws, size_t ws_bytes,
+                   void* stream) {
+    if (!theta || !m || !v || !state || !guard) return SGG_EINVAL;
+    int rc = sgg_grad_sumsq(g, n, ws, ws_bytes, stream);        // (validates g, n and the workspace before anything is launched)
+    if (rc) return rc;
+    hipLaunchKernelGGL(adam_guard_prep_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, sched,
+                       reinterpret_cast<const GsqPartial*>((char*)ws + 16), (int)gsq_chunks(n), (uint32_t*)ws, guard, lr, beta1, beta2,
+                       grad_scale, max_norm);
+    rc = sgg_check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(adam_guard_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n,
+                       (const int64_t*)state, (const uint32_t*)ws, beta1, beta2, eps);
     return sgg_check_launch();
 }
 

@@ -766,6 +766,70 @@ def scheduled_lr(lr, iterations, steps_per_epoch, epoch_step, epochs):
     return np.float32((float(lr) * float(max(epochs - e, 0))) / float(epochs - epoch_step))
 
 
+GRAD_GUARD_CHUNK = 8192          # elements per block of the sum-of-squares pass (GSQ_CHUNK, csrc/misc.hip)
+
+
+def grad_guard_workspace(n: int, device) -> torch.Tensor:
+    """A workspace of its own for the guarded update of an ``n``-element buffer (``sgg_grad_guard_workspace`` bytes): the
+    decision header is read by the update launch, so it is not taken from the shared scratch buffer."""
+    return torch.zeros(int(A.lib().sgg_grad_guard_workspace(int(n))), dtype=torch.uint8, device=device)
+
+
+def grad_sumsq(g, ws=None):
+    """The partial pass alone (``sgg_grad_sumsq``): returns (float64 sums of squares, int32 non-finite flags), one entry per
+    ``GRAD_GUARD_CHUNK`` elements of ``g`` -- views into ``ws``."""
+    assert g.dtype == torch.float32
+    n = g.numel()
+    ws = grad_guard_workspace(n, g.device) if ws is None else ws
+    A.check(A.lib().sgg_grad_sumsq(_p(g), n, _p(ws), ws.numel(), _s()), "grad_sumsq")
+    chunks = (n + GRAD_GUARD_CHUNK - 1) // GRAD_GUARD_CHUNK
+    rec = ws[16:16 + 16 * chunks]
+    return rec.view(torch.float64)[0::2], rec.view(torch.int32)[2::4]
+
+
+def adam_guard(theta, g, m, v, state, guard, ws, sched=None, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, max_norm=0.0):
+    """``adam_iter`` (``sched`` None) or ``adam_sched`` behind the device-side guard (``guarded_update`` states the rule):
+    ``guard`` is a device float64[4] = [last_norm, last_clip, skipped_total, applied_total], ``ws`` a ``grad_guard_workspace``."""
+    assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
+    assert state.dtype == torch.int64 and state.numel() == 2
+    assert guard.dtype == torch.float64 and guard.numel() == 4
+    assert sched is None or (sched.dtype == torch.int64 and sched.numel() == 3)
+    A.check(A.lib().sgg_adam_guard(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(state), _p(sched), lr, beta1, beta2, eps,
+                                   grad_scale, float(max_norm), _p(guard), _p(ws), ws.numel(), _s()), "adam_guard")
+
+
+def guarded_update(theta, g, m, v, iterations, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, max_norm=0.0, sched=None):
+    """The whole rule of ``adam_guard`` in float64 NumPy (logging, tests), for one step:
+
+        norm = sqrt(sum g^2) * grad_scale;   skip = any g is NaN or +-Inf
+        clip = 1 if skip or max_norm <= 0 or norm <= max_norm else float32(max_norm / norm)
+        skipped: theta, m, v and iterations stay;   otherwise Keras Adam at t = iterations + 1 on g * float32(grad_scale * clip)
+        at the rate ``scheduled_lr(lr, iterations, *sched)`` (``sched`` None: ``lr``)
+
+    ``lr``, ``grad_scale``, ``max_norm`` and the betas enter as the f32 values the kernel receives; everything else is
+    float64.  Returns (theta, m, v, iterations, info) with info = {"norm", "clip", "skip"}."""
+    f = np.float32
+    theta, g, m, v = (np.asarray(x, dtype=np.float64) for x in (theta, g, m, v))
+    gs, mx = f(grad_scale), f(max_norm)
+    skip = not bool(np.isfinite(g).all())
+    with np.errstate(over="ignore", invalid="ignore"):
+        norm = float(np.sqrt(np.sum(g * g))) * float(gs)
+    clip = f(1.0)
+    if not skip and mx > 0 and not norm <= float(mx):
+        clip = f(float(mx) / norm)
+    info = {"norm": norm, "clip": float(clip), "skip": skip}
+    if skip:
+        return theta, m, v, int(iterations), info
+    t = int(iterations) + 1
+    b1, b2, eps = float(f(beta1)), float(f(beta2)), float(f(eps))
+    lr_e = float(f(lr)) if sched is None else float(scheduled_lr(lr, iterations, *sched))
+    lr_t = lr_e * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+    gi = g * float(f(gs * clip))
+    m = b1 * m + (1.0 - b1) * gi
+    v = b2 * v + (1.0 - b2) * gi * gi
+    return theta - lr_t * m / (np.sqrt(v) + eps), m, v, t, info
+
+
 # ----------------------------------------------------------------------------- data side
 def seg_class_map(rgb_u8):
     """uint8 (..., M, N, 3|4) -> uint8 (..., M, N) class indices (segment_class.py:60-99), bit exact."""

@@ -70,6 +70,15 @@ def build_parser():
            "lr if epoch < epoch_step else lr*(epoch_total-epoch)/(epoch_total-epoch_step), with epoch_total = --epoch and lr = --lr "
            "in --cycle mode (the reference-mode step's hard-coded 1e-3 otherwise); evaluated on the device from each optimizer's step "
            "counter (epoch = iterations // steps per epoch), so it survives graph replay and goes on after --continue_train")
+    # (the two guard flags are absent from the namespace unless given -- sggan reads them with its own defaults, 0 and off --
+    # so a run without them is configured by exactly the namespace it had before they existed)
+    a("--clip_grad_norm", dest="clip_grad_norm", type=float, default=argparse.SUPPRESS,
+      help="clip every network's gradient to this global L2 norm before its Adam update (default 0 = off); the norm is measured "
+           "and the factor applied on the device by the update's own launches, so it costs no host sync and works under --graph; "
+           "a gradient that holds a NaN or Inf is skipped, as with --skip_nonfinite")
+    a("--skip_nonfinite", dest="skip_nonfinite", action="store_true", default=argparse.SUPPRESS,
+      help="skip a network's update when its gradient holds a NaN or Inf: parameters, Adam slots and step counter keep their "
+           "bits and the skip is counted ('<network> Skipped Updates' scalar at epoch end)")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 

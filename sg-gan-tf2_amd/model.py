@@ -32,7 +32,7 @@ def default_args(**over):
              dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=None,
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
-             crf=False, lr_decay=False)
+             crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -109,11 +109,17 @@ class sggan(object):
         self.lr_decay = bool(g("lr_decay", False))
         self._lr_sched = torch.tensor([1, 0, 0], dtype=torch.int64, device=self.device) if self.lr_decay else None
         self._lr_sched_host = (1, 0, 0)
-        self.g_optim = Adam(self.generator, lr, self.beta1, schedule=self._lr_sched)
-        self.d_optim = Adam(self.discriminator, lr, self.beta1, schedule=self._lr_sched)
+        # clip_grad_norm / skip_nonfinite (no counterpart in the reference, off by default): every optimizer
+        # measures its network's global gradient norm on the device, clips to clip_grad_norm (> 0) and skips an update whose
+        # gradient is not finite -- decided by the update's own launches, so it costs no host sync and survives graph replay
+        self.clip_grad_norm = max(float(g("clip_grad_norm", 0.0) or 0.0), 0.0)
+        self.skip_nonfinite = bool(g("skip_nonfinite", False))
+        okw = dict(schedule=self._lr_sched, clip_norm=self.clip_grad_norm or None, skip_nonfinite=self.skip_nonfinite)
+        self.g_optim = Adam(self.generator, lr, self.beta1, **okw)
+        self.d_optim = Adam(self.discriminator, lr, self.beta1, **okw)
         if self.cycle:
-            self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1, schedule=self._lr_sched)
-            self.d_optim_B = Adam(self.discriminator_B, lr, self.beta1, schedule=self._lr_sched)
+            self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1, **okw)
+            self.d_optim_B = Adam(self.discriminator_B, lr, self.beta1, **okw)
         # cycle step: run the two generators (and the two discriminators) in lockstep on stacked batches (module._PairUnit);
         # bit-identical to the one-network-at-a-time sequencing, which stays for the image pool and for mixed mode.  paired=None
         # picks the default: on for the ResNet (the step bench.py times); off for the U-Net, whose step is bound by
@@ -274,6 +280,7 @@ class sggan(object):
         back, then record ONE step without executing it."""
         nets = self.networks()
         keep = [(n.P.flat.clone(), n.P.m.clone(), n.P.v.clone(), n.P.iterations.clone()) for n in nets]
+        guard_keep = [None if n.P._guard is None else n.P._guard.clone() for n in nets]     # (the warm-up step counts as none)
         loss_keep = self._loss.clone()
         hook, K.PROFILE = K.PROFILE, None          # timing hooks (bench.py) record events: not while recording
         try:
@@ -287,6 +294,11 @@ class sggan(object):
             for n, (f, m, v, it) in zip(nets, keep):
                 n.P.flat.copy_(f); n.P.m.copy_(m); n.P.v.copy_(v); n.P.iterations.copy_(it)
                 n.P.version += 1                   # the recorded step starts by re-packing the conv weights
+            for n, rec in zip(nets, guard_keep):
+                if n.P._guard is not None and rec is not None:
+                    n.P._guard.copy_(rec)
+                elif n.P._guard is not None:       # first allocated by the warm-up step
+                    n.P._guard.zero_()
             self._loss.copy_(loss_keep)
             prog = StepProgram(self.device)
             K._RECORDER = prog
@@ -388,7 +400,9 @@ class sggan(object):
 
     def _apply_gradients(self, *updates):
         """(optimizer, its network's all-reduce handle or None) in update order: each Adam launch waits for that network's
-        gradient exchange only, so the exchanges still in flight run under the updates in front of them."""
+        gradient exchange only, so the exchanges still in flight run under the updates in front of them.  A guarded update
+        (clip_grad_norm / skip_nonfinite) measures the buffer AFTER the exchange: every rank sees the same summed bits and
+        1 / world enters the norm as grad_scale, so all ranks take the same decision without another collective."""
         scale = 1.0 / self._world
         for opt, h in updates:
             if h is not None:
@@ -409,6 +423,28 @@ class sggan(object):
 
     def networks(self):
         return (self.generator, self.discriminator) + ((self.generator_BA, self.discriminator_B) if self.cycle else ())
+
+    def _net_names(self):
+        return ("G", "D", "G_BA", "D_B") if self.cycle else ("G", "D")
+
+    @property
+    def guarded(self):
+        return self.clip_grad_norm > 0 or self.skip_nonfinite
+
+    def grad_stats(self):
+        """The guarded updates' records, {"G": {"norm", "clip", "skipped", "applied"}, "D": ...}: the last step's global
+        gradient norm and clip factor and the running totals of skipped and applied updates per network.  ONE synchronising
+        read -- for epoch ends and tests, not for the step.  Networks that never took a guarded step report zeros (clip 1)."""
+        nets = self.networks()
+        recs = [n.P._guard for n in nets]
+        host = torch.stack([r for r in recs if r is not None]).cpu().tolist() if any(r is not None for r in recs) else []
+        out, k = {}, 0
+        for name, r in zip(self._net_names(), recs):
+            row = [0.0, 1.0, 0.0, 0.0]
+            if r is not None:
+                row, k = host[k], k + 1
+            out[name] = {"norm": row[0], "clip": row[1], "skipped": int(row[2]), "applied": int(row[3])}
+        return out
 
     def _train_step_cycle(self):
         """2G+2D step assembled from the reference's defined-not-wired criteria (deviation D5):
@@ -624,6 +660,8 @@ class sggan(object):
         for key, net in zip(names, self.networks()):
             P = net.P
             sd[key] = {"flat": P.flat.cpu(), "m": P.m.cpu(), "v": P.v.cpu(), "t": P.step_count}
+            if P._guard is not None:            # the guarded update's counters [skipped_total, applied_total]
+                sd[key]["guard"] = [int(c) for c in P._guard[2:4].cpu().tolist()]
         sd["G"]["arch"] = self.arch             # generator architecture tag (a checkpoint without one is a ResNet checkpoint)
         return sd
 
@@ -637,6 +675,11 @@ class sggan(object):
             P = net.P
             P.flat.copy_(sd[key]["flat"]); P.m.copy_(sd[key]["m"]); P.v.copy_(sd[key]["v"])
             P.step_count = int(sd[key]["t"]); P.version += 1
+            counters = sd[key].get("guard")     # (absent from a checkpoint of a run without the options)
+            if counters is not None:
+                P.guard_buffers()[0][2:4].copy_(torch.tensor([float(c) for c in counters], dtype=torch.float64))
+            elif P._guard is not None:
+                P._guard[2:4].zero_()
 
     def _ckpt_paths(self, checkpoint_dir, ep=None):
         """model.py:454-456: <checkpoint_dir>/<dataset_dir>/{gen,disc}/cp-{epoch:04d}.ckpt"""
@@ -794,6 +837,10 @@ class sggan(object):
                     if self.lr_decay:              # the rate the generator's last update of this epoch applied
                         last = max(self.g_optim.iterations.item() - 1, 0)
                         sink.scalar("Learning Rate", float(K.scheduled_lr(self.g_optim.learning_rate, last, *self._lr_sched_host)), epoch)
+                    if self.guarded:               # the last step's gradient norm and the skipped updates so far, per network
+                        for name, st in self.grad_stats().items():
+                            sink.scalar(name + " Grad Norm", st["norm"], epoch)
+                            sink.scalar(name + " Skipped Updates", st["skipped"], epoch)
                 history.append({"epoch": epoch, "Generator Loss": self.gen_loss_metric, "Discriminator Loss": self.disc_loss_metric})
         finally:
             if getattr(args, "checkpoint_dir", None):

@@ -46,6 +46,9 @@ class ParamStore:
         # carries no host state and can be replayed from a captured HIP graph
         self._adam_state = torch.zeros(2, dtype=torch.int64, device=self.device)    # [iterations, scratch] (sgg_adam_iter)
         self.iterations = self._adam_state[0:1]
+        # the guarded update's record [last_norm, last_clip, skipped_total, applied_total] and workspace: device memory,
+        # allocated at the first guarded step (guard_buffers), so a model without the options carries neither
+        self._guard = self._guard_ws = None
 
     @property
     def step_count(self):
@@ -113,11 +116,26 @@ class ParamStore:
     def zero_grad(self):
         self.grad.zero_()
 
-    def adam_step(self, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, schedule=None):
+    def guard_buffers(self):
+        """(record, workspace) of the guarded update, allocated on first use -- before a step is captured: the recording's
+        eager warm-up step gets here first."""
+        if self._guard is None:
+            self._guard = torch.zeros(4, dtype=torch.float64, device=self.device)
+            self._guard_ws = K.grad_guard_workspace(self.numel, self.device)
+        return self._guard, self._guard_ws
+
+    def adam_step(self, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, schedule=None, max_norm=None, guard=False):
         """tf.keras.optimizers.Adam.apply_gradients (model.py:199-200) over the whole network: one launch.  ``schedule``: a
         device int64[3] [steps_per_epoch, epoch_step, epochs] -- ``lr`` is then the base rate of the linear decay of
-        model.py:223, evaluated on the device from ``iterations`` (K.adam_sched); None: ``lr`` as it is."""
-        if schedule is None:
+        model.py:223, evaluated on the device from ``iterations`` (K.adam_sched); None: ``lr`` as it is.  ``max_norm`` (clip
+        the gradient's global L2 norm to it) and ``guard`` (skip the update when the gradient holds a NaN or Inf) send the
+        step through K.adam_guard instead, which decides on the device; clipping implies the skip, since a non-finite norm
+        has no clip factor.  With neither, the launches are the ones above and nothing else."""
+        if max_norm is not None or guard:
+            rec, ws = self.guard_buffers()
+            K.adam_guard(self.flat, self.grad, self.m, self.v, self._adam_state, rec, ws, schedule, lr, beta1, beta2, eps, grad_scale,
+                         0.0 if max_norm is None else max_norm)
+        elif schedule is None:
             K.adam_iter(self.flat, self.grad, self.m, self.v, self._adam_state, lr, beta1, beta2, eps, grad_scale)
         else:
             K.adam_sched(self.flat, self.grad, self.m, self.v, self._adam_state, schedule, lr, beta1, beta2, eps, grad_scale)
@@ -128,8 +146,13 @@ class Adam:
     """``tf.keras.optimizers.Adam`` as the reference holds it in ``self.g_optim`` / ``self.d_optim`` (model.py:83-84,
     199-200, 205-207), bound to one network's flat parameter store: the whole update is one fused launch."""
 
-    def __init__(self, net, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule=None):
+    def __init__(self, net, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule=None, clip_norm=None,
+                 skip_nonfinite=False):
         self.net, self.learning_rate, self.beta_1, self.beta_2, self.epsilon = net, learning_rate, beta_1, beta_2, epsilon
+        # clip_norm: clip the global L2 norm of the network's gradient to it (None or <= 0: off); skip_nonfinite: leave the
+        # network and its Adam state alone for a step whose gradient holds a NaN or Inf (ParamStore.adam_step)
+        self.clip_norm = float(clip_norm) if clip_norm is not None and float(clip_norm) > 0 else None
+        self.skip_nonfinite = bool(skip_nonfinite)
         # device int64[3] [steps_per_epoch, epoch_step, epochs] or None (ParamStore.adam_step): with it, learning_rate is the
         # base rate of the linear decay
         self.schedule = schedule
@@ -153,7 +176,8 @@ class Adam:
                     raise ValueError("apply_gradients: variable does not belong to this optimizer's network")
                 if g is not None:
                     P.g(name).copy_(torch.as_tensor(g, device=P.device).reshape(P.g(name).shape))
-        P.adam_step(self.learning_rate, self.beta_1, self.beta_2, self.epsilon, grad_scale, self.schedule)
+        P.adam_step(self.learning_rate, self.beta_1, self.beta_2, self.epsilon, grad_scale, self.schedule, self.clip_norm,
+                    self.skip_nonfinite)
 
 
 def _layer_specs(name, shape, out_ch, norm=True):
