@@ -33,7 +33,7 @@ extern "C" {
 #define SGG_CPAD 8               /* activation channel granule */
 
 typedef enum { SGG_OK = 0, SGG_EINVAL = -1, SGG_EUNSUPPORTED = -2, SGG_ELAUNCH = -3, SGG_EWORKSPACE = -4 } sgg_status;
-typedef enum { SGG_F32 = 0, SGG_BF16 = 1 } sgg_dtype;
+typedef enum { SGG_F32 = 0, SGG_BF16 = 1, SGG_U8 = 2 /* image input of sgg_palette_* only */ } sgg_dtype;
 typedef enum { SGG_ACT_NONE = 0, SGG_ACT_RELU = 1, SGG_ACT_LRELU = 2, SGG_ACT_TANH = 3 } sgg_act;
 typedef enum { SGG_PAD_ZERO = 0, SGG_PAD_REFLECT = 1 } sgg_pad_mode;
 
@@ -449,6 +449,35 @@ size_t sgg_dense_crf_workspace_bytes(int H, int W, int C);
 int sgg_dense_crf(const uint8_t* img, const float* probs, const float* unary, int H, int W, int C, int max_iter,
                   float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out,
                   void* ws, size_t ws_bytes, void* stream);
+/* ---- class-level evaluation of generated segmentation maps (no counterpart in the reference) ----
+ * A generated colour image is decoded to class labels through a palette of K entries {key = R<<16|G<<8|B, class}, 1 <= K <= 64,
+ * given as HOST arrays and passed to the kernels by value (nothing is allocated or copied: the calls can be captured); both
+ * NULL selects the library's built-in table (sgg_seg_class_table, K ignored).
+ *   img: [n_pixels][cstride] of kind SGG_F32 / SGG_BF16 (cstride >= 3, the first three channels used; cstride = SGG_CPAD with a
+ *        16-byte aligned base takes one 16-byte load per pixel) or SGG_U8 (cstride = 3 | 4; dword loads, four pixels per thread).
+ *   colour: float input q_c = (int)(((x_c + 1.f) * 0.5f) * 255.f) in f32, clamped to 0..255, NaN -> 0 (utils.inverse_transform
+ *        inside [-1,1]); uint8 input: the byte.   d2_k = sum_c (q_c - key_k.c)^2 (int32); the smallest wins, ties to the LOWEST k;
+ *        label = class[k] if max_dist2 < 0 or d2 <= max_dist2, else other_class (0..255).
+ * sgg_palette_decode -- outputs, each optional, at least one required:
+ *   labels int32 [n_pixels];
+ *   truth uint8 [n_pixels] + hist uint64 [n_class^2] (both or neither, 1 <= n_class <= 64): hist[n_class*t + p] += 1 for every
+ *   pixel with t, p < n_class -- and, where select uint8 [n_pixels] is given, select != 0.  Counted in per-block LDS counters and
+ *   added with 64-bit atomics: exact, order independent, accumulates into what hist holds.
+ *   SGG_EINVAL before any launch: NULL img, K out of range, a key above 0xFFFFFF, other_class out of range, no output, truth
+ *   without hist (or the reverse), select without hist, n_class out of range or <= a palette class.  n_pixels < 2^31.
+ * sgg_palette_probs -- probs f32 (N, n_class, HW) from img (N, HW, cstride): with m_c = the smallest d2 over the entries of
+ *   class c (other_class, where no entry names it and max_dist2 >= 0: the pseudo-distance max_dist2) and m_min = min_c m_c,
+ *   e_c = exp(-(m_c - m_min) / (2 sigma^2)), classes with no distance e_c = 0, p = e / sum(e): the `probs` of sgg_dense_crf.
+ *   Every palette class must be < n_class <= 64; sigma > 0.
+ * sgg_class_boundary_band -- cls uint8 (N,H,W), 0 <= r <= 8: band[n,y,x] = 1 iff a pixel of image n with |dy|, |dx| <= r has a
+ *   class other than cls[n,y,x], else 0 (r = 0: all zeros).  Nothing outside an image is read. */
+int sgg_palette_decode(const void* img, int kind, int64_t n_pixels, int cstride, const uint32_t* keys_host,
+                       const uint8_t* classes_host, int K, int other_class, int max_dist2, int32_t* labels,
+                       const uint8_t* truth, const uint8_t* select, int n_class, uint64_t* hist, void* stream);
+int sgg_palette_probs(const void* img, int kind, int N, int HW, int cstride, const uint32_t* keys_host,
+                      const uint8_t* classes_host, int K, int other_class, int max_dist2, int n_class, float sigma,
+                      float* probs, void* stream);
+int sgg_class_boundary_band(const uint8_t* cls, uint8_t* band, int N, int H, int W, int r, void* stream);
 /* f32 [P][Cs] -> dtype [P][Cd] with zero fill (Cd >= Cs), and back (drops padded channels). */
 int sgg_pad_channels(const float* src, void* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);
 int sgg_unpad_channels(const void* src, float* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);

@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsggan.so")      # the package reads no environment; tools pick another build with use_library()
 
-SGG_F32, SGG_BF16 = 0, 1
+SGG_F32, SGG_BF16, SGG_U8 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT = 0, 1
 CPAD = 8
@@ -125,6 +125,9 @@ SIGNATURES = {
     "sgg_argmax_u8_labels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "sgg_dense_crf_workspace_bytes": (_sz, [_i, _i, _i]),
     "sgg_dense_crf": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
+    "sgg_palette_decode": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "sgg_palette_probs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "sgg_class_boundary_band": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "sgg_pad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "sgg_unpad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
 }

@@ -933,3 +933,62 @@ def dense_crf(img_u8, probs=None, unary=None, max_iter=10, pos_w=3.0, pos_xy_std
                                   float(bi_w), float(bi_xy_std), float(bi_rgb_std), _p(out), _p(workspace), workspace.numel(), _s()),
             "dense_crf")
     return out
+
+
+# ----------------------------------------------------------------------------- class-level evaluation (csrc/evalseg.hip)
+def _palette_args(palette):
+    """(keys, classes, K) for the C ABI from ``(keys, classes)`` host arrays; None -> the library's built-in table."""
+    if palette is None:
+        return None, None, 0, ()
+    keys = np.ascontiguousarray(palette[0], dtype=np.uint32)
+    classes = np.ascontiguousarray(palette[1], dtype=np.uint8)
+    assert keys.ndim == 1 and keys.shape == classes.shape, "palette: (keys uint32[K], classes uint8[K])"
+    return keys.ctypes.data_as(C.c_void_p), classes.ctypes.data_as(C.c_void_p), int(keys.size), (keys, classes)
+
+
+def _pixel_input(img):
+    """A contiguous device image (N,H,W,Cs) -> (tensor, kind): f32 / bf16 with Cs >= 3, or uint8 with Cs = 3 | 4."""
+    assert img.is_cuda and img.dim() == 4, "device image (N,H,W,C) required"
+    if img.dtype == torch.uint8:
+        return img.contiguous(), A.SGG_U8
+    return img.contiguous(), dt(img)
+
+
+def palette_decode(img, palette=None, other_class=0, max_dist2=-1, labels=None, truth=None, select=None, n_class=0, hist=None,
+                   want_labels=True):
+    """sgg_palette_decode: img (N,H,W,Cs) -> labels int32 (N,H,W) (``want_labels``) and / or, with ``truth`` uint8 (N,H,W) and
+    ``hist`` int64 [n_class^2], the confusion counts added into ``hist`` (only where ``select`` uint8 (N,H,W) is non-zero, when
+    given).  One launch.  Returns (labels or None, hist or None)."""
+    img, kind = _pixel_input(img)
+    N, H, W, Cs = img.shape
+    if want_labels:
+        labels = _out(labels, (N, H, W), torch.int32, img.device)
+    for t in (truth, select):
+        assert t is None or (t.dtype == torch.uint8 and tuple(t.shape) == (N, H, W))
+    assert hist is None or (hist.dtype == torch.int64 and hist.numel() == n_class * n_class)
+    keys, classes, K_, keep = _palette_args(palette)
+    A.check(A.lib().sgg_palette_decode(_p(img), kind, N * H * W, Cs, keys, classes, K_, int(other_class), int(max_dist2),
+                                       _p(labels) if want_labels else None, _p(truth), _p(select), int(n_class), _p(hist), _s()),
+            "palette_decode")
+    return (labels if want_labels else None), hist
+
+
+def palette_probs(img, n_class, palette=None, sigma=32.0, other_class=0, max_dist2=-1, out=None):
+    """sgg_palette_probs: img (N,H,W,Cs) -> class probabilities f32 (N,n_class,H,W), the ``probs`` of dense_crf."""
+    img, kind = _pixel_input(img)
+    N, H, W, Cs = img.shape
+    out = _out(out, (N, int(n_class), H, W), torch.float32, img.device)
+    keys, classes, K_, keep = _palette_args(palette)
+    A.check(A.lib().sgg_palette_probs(_p(img), kind, N, H * W, Cs, keys, classes, K_, int(other_class), int(max_dist2), int(n_class),
+                                      float(sigma), _p(out), _s()), "palette_probs")
+    return out
+
+
+def class_boundary_band(cls_u8, r, out=None):
+    """sgg_class_boundary_band: class map uint8 (N,H,W) -> uint8 (N,H,W), 1 where a pixel within r (Chebyshev, inside the image)
+    has another class."""
+    assert cls_u8.dtype == torch.uint8 and cls_u8.dim() == 3
+    N, H, W = cls_u8.shape
+    out = _out(out, (N, H, W), torch.uint8, cls_u8.device)
+    A.check(A.lib().sgg_class_boundary_band(_p(cls_u8), _p(out), N, H, W, int(r), _s()), "class_boundary_band")
+    return out

@@ -79,6 +79,18 @@ def build_parser():
     a("--skip_nonfinite", dest="skip_nonfinite", action="store_true", default=argparse.SUPPRESS,
       help="skip a network's update when its gradient holds a NaN or Inf: parameters, Adam slots and step counter keep their "
            "bits and the skip is counted ('<network> Skipped Updates' scalar at epoch end)")
+    # (absent from the namespace unless given, like the guard flags)
+    a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
+      help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "
+           "class map) pairs and score it against the class map: 'Class Overall Accuracy' ... 'Class Mean IoU' scalars, "
+           "'Boundary Class Mean IoU' (--boundary_px) and, with --crf, the 'Class CRF ...' scores of the CRF-refined map; "
+           "needs testA_seg_class beside testA; --segment_class is the class count")
+    a("--boundary_px", dest="boundary_px", type=int, default=argparse.SUPPRESS,
+      help="--class_scores: half-width in pixels (0..8, default 3) of the band around ground-truth class boundaries that "
+           "'Boundary Class Mean IoU' is scored on; 0 leaves the scalar out")
+    a("--class_max_dist", dest="class_max_dist", type=int, default=argparse.SUPPRESS,
+      help="--class_scores: a pixel whose 8-bit colour is farther than this (Euclidean, RGB) from every palette colour counts as "
+           "class 0 (default -1: always the nearest colour)")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 
@@ -117,7 +129,8 @@ def synthetic_test_samples(args, count=2):
         H, W = args.image_height, args.image_width
         for i in range(count):
             item = ("synthetic_%03d.png" % i, torch.rand((H, W, 3), generator=g).numpy(), torch.rand((H, W, 3), generator=g).numpy())
-            if getattr(args, "crf", False):        # drawn after the triple, so the triple is what it is without --crf
+            if getattr(args, "crf", False) or getattr(args, "class_scores", False):      # drawn after the triple (once for both
+                # flags), so the triple is what it is without them
                 idx = torch.randint(0, args.segment_class, (H, W), generator=g)
                 item += (torch.nn.functional.one_hot(idx, args.segment_class).float().numpy(),)
             yield item
@@ -157,8 +170,30 @@ def directory_sources(model, args, log=print):
     batches = D.DirectoryBatches(model, args, cache_A, cache_B, augment=augment)
     tests = None
     if os.path.isdir(os.path.join(root, "testA")):
-        tests = D.directory_test_samples(args, D.DatasetCache(root, "testA", device=dev, with_class=bool(getattr(args, "crf", False))))
+        tests = D.directory_test_samples(args, class_test_cache(args, root, dev, with_class=bool(getattr(args, "crf", False))))
     return batches, tests
+
+
+def class_test_cache(args, root, device, with_class=False):
+    """The testA cache; with --class_scores it holds the class maps and ``args.class_palette`` is learned from it."""
+    from . import data as D
+    if not getattr(args, "class_scores", False):
+        return D.DatasetCache(root, "testA", device=device, with_class=with_class)
+    folder = os.path.join(root, "testA_seg_class")
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"--class_scores needs the class maps of the test set: {folder} does not exist")
+    from .segment_class import learn_palette
+    cache = D.DatasetCache(root, "testA", device=device, with_class=True)
+    args.class_palette = learn_palette(cache)
+    check_class_palette(args)
+    return cache
+
+
+def check_class_palette(args):
+    """--class_scores: every palette class must be a class of the score (--segment_class)."""
+    pal = getattr(args, "class_palette", None)
+    if pal is not None and len(pal[1]) and int(max(pal[1])) >= args.segment_class:
+        raise ValueError(f"--class_scores: the palette holds class {int(max(pal[1]))} but --segment_class is {args.segment_class}")
 
 
 def main(argv=None):
@@ -176,12 +211,16 @@ def main(argv=None):
     if args.phase == "test":          # main.py:58-60
         root = D.resolve_root(args.dataset_dir, "testA")
         if root is not None:
-            return model.test(args, D.directory_test_samples(args, D.DatasetCache(root, "testA", device=model.device, with_class=False))())
+            return model.test(args, D.directory_test_samples(args, class_test_cache(args, root, model.device))())
         return model.test(args, synthetic_test_samples(args)())
     sink = SummarySink(os.path.join(getattr(args, "log_dir", "./logs"), "train", "scalars.jsonl"))
     src = directory_sources(model, args)
     if src is not None:
         return model.train(args, src[0], test_samples=src[1], sink=sink)
+    if getattr(args, "class_scores", False):          # synthetic samples: the built-in colour table
+        from .segment_class import palette
+        args.class_palette = palette()
+        check_class_palette(args)
     if getattr(args, "augment", False):
         print(" [*] --augment has no effect on the synthetic batches (--dataset_dir names no folder with trainA)")
     return model.train(args, synthetic_batches(model, args), test_samples=synthetic_test_samples(args), sink=sink)

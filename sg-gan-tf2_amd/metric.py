@@ -7,7 +7,12 @@ exact and order-independent) and ``scores_seg_fake`` (metric.py:71-77).
 Gaussian + bilateral kernels, Potts compatibility, symmetric normalisation and iteration count as the pydensecrf calls of the
 reference, with every pixel pair summed instead of pydensecrf's permutohedral-lattice approximation (parity
 with pydensecrf's own numbers is unpinned).  ``scores_mask_sample_crf`` / ``scores_fake_mask_crf`` (metric.py:79-102) sit on
-it.  Left out: ``scores_mask_fake_crf`` (a cubic-spline zoom across the class axis) and ``scores_seg_da_fake``.
+it.  ``scores_mask_fake_crf`` (a cubic-spline zoom across the class axis) is superseded by ``scores_class_fake_crf``;
+``scores_seg_da_fake`` is left out.
+
+Class-level scores (not in the reference): ``palette_labels`` / ``palette_probs`` decode a generated colour map
+to classes through a palette learned from the dataset (csrc/evalseg.hip), ``scores_class_fake`` counts it against the class
+map in the same launch (optionally on a boundary band), ``scores_class_fake_crf`` refines it with ``dense_crf`` first.
 """
 from __future__ import annotations
 
@@ -142,3 +147,88 @@ def scores_fake_mask_crf(seg_mask_64, rescaled_sample, fake_img):
     f_uint = f if f.dtype == np.uint8 else convert_image_dtype_uint8(f).astype(np.uint8)
     crf_labels = np.argmax(f_uint.transpose(0, 3, 2, 1), axis=1)
     return crf_labels, crf_probs.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------- class-level scores (csrc/evalseg.hip)
+def _image_tensor(img):
+    """A generated image as a device tensor (N,H,W,C): a lazy generator output, a torch tensor or a NumPy array (float in
+    [-1,1] -- bf16 / f32 -- or uint8, e.g. the PNG ``save_images`` wrote)."""
+    t = img.tensor() if hasattr(img, "tensor") else img
+    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.array(t))      # (a copy: a decoded PNG is read-only)
+    t = t.cuda()
+    if t.dim() == 3:
+        t = t[None]
+    if t.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+        t = t.float()
+    return t.contiguous()
+
+
+def _class_tensor(class_map):
+    t = class_map if isinstance(class_map, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(class_map))
+    t = t.cuda().to(torch.uint8)
+    return (t[None] if t.dim() == 2 else t).contiguous()
+
+
+def palette_labels(img, palette=None, other_class=0, max_dist2=-1):
+    """Class labels int32 (N,H,W), on the device, of a generated colour image: the class of the nearest palette colour (squared
+    RGB distance of the 8-bit colours, ties to the lowest entry), ``other_class`` where that distance exceeds ``max_dist2 >= 0``.
+    ``palette``: ``(keys, classes)`` from segment_class.learn_palette; None: the built-in table (segment_class.palette)."""
+    return K.palette_decode(_image_tensor(img), palette, other_class, max_dist2)[0]
+
+
+def palette_probs(img, n_class, palette=None, sigma=32.0, other_class=0, max_dist2=-1):
+    """Class probabilities f32 (N,n_class,H,W), on the device, of a generated colour image: a softmax over the classes of
+    -(smallest squared distance to a colour of the class) / (2 sigma^2); classes without a colour get 0.  Each image's slice
+    is what ``dense_crf`` takes as ``output_probs``."""
+    return K.palette_probs(_image_tensor(img), n_class, palette, sigma, other_class, max_dist2)
+
+
+def scores_from_hist(hist):
+    """The FCN score set of ``scores`` (same five keys) from a confusion matrix (n_class, n_class) or its flat form."""
+    h = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+    n_class = int(round(np.sqrt(h.size)))
+    h = h.reshape(n_class, n_class)
+    tp = np.diagonal(h).astype(np.float64)
+    n_true = h.sum(axis=1).astype(np.float64)
+    n_pred = h.sum(axis=0).astype(np.float64)
+    total = float(h.sum())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = tp / (n_true + n_pred - tp)
+        seen = n_true > 0
+        share = n_true / total
+        return {"Overall Acc": tp.sum() / total,
+                "Mean Acc": np.nanmean(tp / n_true),
+                "FreqW Acc": (share[share > 0] * iou[share > 0]).sum(),
+                "Mean IoU": np.nanmean(iou[seen]),
+                "Class IoU": {c: iou[c] for c in range(n_class)}}
+
+
+def _new_hist(n_class, hist):
+    return torch.zeros((n_class, n_class), dtype=torch.int64, device="cuda") if hist is None else hist
+
+
+def scores_class_fake(class_map, fake_img, n_class, palette, band_radius=0, hist=None, other_class=0, max_dist2=-1):
+    """Confusion matrix int64 (n_class, n_class), on the device, of the ground-truth class map (N,H,W) against the palette
+    labels of ``fake_img`` -- decode and count fused in one launch.  ``band_radius > 0`` counts only the pixels within that many
+    pixels of a class boundary of the ground truth (one more launch).  ``hist``: a matrix to add into (accumulation over a test
+    set); feed the result to ``scores_from_hist``."""
+    truth, img = _class_tensor(class_map), _image_tensor(fake_img)
+    hist = _new_hist(n_class, hist)
+    select = K.class_boundary_band(truth, band_radius) if band_radius > 0 else None
+    K.palette_decode(img, palette, other_class, max_dist2, truth=truth, select=select, n_class=n_class, hist=hist, want_labels=False)
+    return hist
+
+
+def scores_class_fake_crf(class_map, rescaled_sample, fake_img, n_class, palette, hist=None, other_class=0, max_dist2=-1):
+    """As ``scores_class_fake`` with the generated map refined by the photo first: per image the labels are
+    ``argmax(dense_crf(photo, palette_probs(fake)))`` (``rescaled_sample`` (N,H,W,3) in 0..255, the MAX_ITER ... Bi_RGB_STD
+    constants of this module as they are at call time), counted against the class map by ``sgg_confusion_hist``."""
+    truth, img = _class_tensor(class_map), _image_tensor(fake_img)
+    photo = _device(rescaled_sample).to(torch.uint8)
+    photo = (photo[None] if photo.dim() == 3 else photo).contiguous()
+    hist = _new_hist(n_class, hist)
+    probs = palette_probs(img, n_class, palette, other_class=other_class, max_dist2=max_dist2)
+    for n in range(img.shape[0]):
+        labels = torch.argmax(dense_crf(photo[n], probs[n]), dim=0)
+        _accumulate_hist(hist.view(-1), truth[n], labels, n_class)
+    return hist

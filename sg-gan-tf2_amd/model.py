@@ -734,13 +734,28 @@ class sggan(object):
         With ``args.crf`` the samples carry a fourth element, load_test_data's full-resolution one-hot class mask (H,W,C), each
         is also scored by metric.scores_mask_sample_crf (model.py:314-315 keeps the lists for it), and the four FCN scores of
         those labels follow the reference's four in ``sink`` as 'CRF Overall Accuracy' ... 'CRF Mean IoU' (and in the returned
-        scores under "CRF")."""
+        scores under "CRF").
+        With ``args.class_scores`` the samples carry that mask too; its argmax is the ground-truth class map, the
+        translation is decoded to classes through ``args.class_palette`` (segment_class.learn_palette; None: the built-in table)
+        and ONE confusion matrix per score is accumulated on the device over all samples and read back once.  After the scalars
+        above follow 'Class Overall Accuracy' ... 'Class Mean IoU', with ``args.boundary_px`` > 0 'Boundary Class Mean IoU' (the
+        pixels within that distance of a ground-truth class boundary), and with ``args.crf`` as well the four 'Class CRF ...'
+        scores of the CRF-refined map (metric.scores_class_fake_crf); the returned scores gain "Class", "Class Boundary" and
+        "Class CRF"."""
         from . import metric as M
         from .utils import convert_image_dtype_uint8, get_img, save_images
         import os
         gts, preds, outputs = [], [], []
         crf = bool(getattr(args, "crf", False))
         gts2, preds2 = [], []
+        class_scores = bool(getattr(args, "class_scores", False))
+        if class_scores:
+            n_class, class_palette = args.segment_class, getattr(args, "class_palette", None)
+            band_px = int(getattr(args, "boundary_px", 3))
+            far = int(getattr(args, "class_max_dist", -1))
+            decode = dict(max_dist2=far * far if far >= 0 else -1)
+            class_hist = {k: torch.zeros((n_class, n_class), dtype=torch.int64, device=self.device)
+                          for k, on in (("Class", True), ("Class Boundary", band_px > 0), ("Class CRF", crf)) if on}
         test_dir = getattr(args, "test_dir", None)
         for item in samples:
             name, sample_image, seg_image = item[:3]
@@ -759,6 +774,16 @@ class sggan(object):
                                      "DatasetCache(with_class=True))")
                 lt2, lp2 = M.scores_mask_sample_crf(np.asarray(item[3])[None], rescaled)          # :330,338 seg_mask_64
                 preds2 += list(lp2); gts2 += list(lt2)
+            if class_scores:
+                if len(item) < 4:
+                    raise ValueError("class_scores: test samples must carry the one-hot class mask (data.directory_test_samples "
+                                     "over a DatasetCache(with_class=True))")
+                truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
+                M.scores_class_fake(truth, fake_A, n_class, class_palette, hist=class_hist["Class"], **decode)
+                if "Class Boundary" in class_hist:
+                    M.scores_class_fake(truth, fake_A, n_class, class_palette, band_radius=band_px, hist=class_hist["Class Boundary"], **decode)
+                if crf:
+                    M.scores_class_fake_crf(truth, rescaled, fake_A, n_class, class_palette, hist=class_hist["Class CRF"], **decode)
         score = M.scores(gts, preds, n_class=args.segment_class)                                 # :378
         if sink is not None:                                                                     # :389-393
             sink.scalar("Overall Accuracy", score["Overall Acc"], epoch)
@@ -772,13 +797,33 @@ class sggan(object):
                 sink.scalar("CRF Mean Accuracy", crf_score["Mean Acc"], epoch)
                 sink.scalar("CRF Frequency Weighted Accuracy", crf_score["FreqW Acc"], epoch)
                 sink.scalar("CRF Mean IoU", crf_score["Mean IoU"], epoch)
+        if class_scores:
+            for key, h in class_hist.items():
+                score[key] = M.scores_from_hist(h)
+            if sink is not None:
+                self._class_scalars(sink, "Class ", score["Class"], epoch)
+                if "Class Boundary" in score:
+                    sink.scalar("Boundary Class Mean IoU", score["Class Boundary"]["Mean IoU"], epoch)
+                if "Class CRF" in score:
+                    self._class_scalars(sink, "Class CRF ", score["Class CRF"], epoch)
         return (np.concatenate(outputs, axis=0) if outputs else None), score
+
+    @staticmethod
+    def _class_scalars(sink, prefix, s, epoch):
+        sink.scalar(prefix + "Overall Accuracy", s["Overall Acc"], epoch)
+        sink.scalar(prefix + "Mean Accuracy", s["Mean Acc"], epoch)
+        sink.scalar(prefix + "Frequency Weighted Accuracy", s["FreqW Acc"], epoch)
+        sink.scalar(prefix + "Mean IoU", s["Mean IoU"], epoch)
 
     def test(self, args, samples, log=print):
         """model.py:535-567 (--phase test): load the latest checkpoint, translate every test sample and save the input and the
-        translation under ``args.test_dir``.  ``samples`` yields (name, sample_image (H,W,3) in [0,1])."""
+        translation under ``args.test_dir``.  ``samples`` yields (name, sample_image (H,W,3) in [0,1]).  With
+        ``args.class_scores`` and samples that carry the one-hot class mask as their fourth element, the four class-level scores
+        of the translations are logged at the end."""
+        from . import metric as M
         from .utils import convert_image_dtype_uint8, save_images
         import os
+        class_hist = None
         log(" [*] Running Test ...")
         log(" [*] Load SUCCESS" if self.load(args.checkpoint_dir) else " [!] Load failed...")
         os.makedirs(args.test_dir, exist_ok=True)
@@ -791,6 +836,15 @@ class sggan(object):
             save_images(sample_image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(name)))
             save_images(fake_A, [1, 1], os.path.join(args.test_dir, os.path.basename(name)))
             out.append(fake_A)
+            if getattr(args, "class_scores", False) and len(item) >= 4:
+                truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
+                far = int(getattr(args, "class_max_dist", -1))
+                class_hist = M.scores_class_fake(truth, fake_A, args.segment_class, getattr(args, "class_palette", None), hist=class_hist,
+                                                 max_dist2=far * far if far >= 0 else -1)
+        if class_hist is not None:
+            s = M.scores_from_hist(class_hist)
+            log("Class Overall Accuracy: %f Class Mean Accuracy: %f Class Frequency Weighted Accuracy: %f Class Mean IoU: %f"
+                % (s["Overall Acc"], s["Mean Acc"], s["FreqW Acc"], s["Mean IoU"]))
         return out
 
     def train(self, args, batches, log=print, test_samples=None, sink=None):
