@@ -384,6 +384,23 @@ int sgg_grad_sumsq(const float* g, int64_t n, void* ws, size_t ws_bytes, void* s
 int sgg_adam_guard(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched,
                    float lr, float beta1, float beta2, float eps, float grad_scale, float max_norm, double* guard,
                    void* ws, size_t ws_bytes, void* stream);
+/* The same updates keeping an exponential moving average of theta beside it, in the update's own launches:
+ *   guarded == 0: sgg_adam_sched's launches (sched == NULL: sgg_adam_iter's); guard and ws may be NULL, max_norm is unused.
+ *   guarded != 0: sgg_adam_guard's launches with its guard, ws and max_norm.
+ * theta, m, v, state[0] (and guard[0..3]) come out bit-identical to those calls.  The prep launch also forms, with t =
+ * state[0] AFTER this update's increment,
+ *       d_t = (float)min((double)ema_decay, (1 + t) / (10 + t))       (tf.train.ExponentialMovingAverage with num_updates)
+ * and writes ema_state = {d_t, 1.f - d_t} (float[2] on the DEVICE); the update launch then does, per element in f32,
+ *       ema[i] = d_t * ema[i] + (1 - d_t) * theta_new[i].
+ * A skipped step leaves ema and ema_state with their bits, like theta, m and v; t counts applied updates.  The update launch
+ * moves 16 bytes per lane on all five streams: theta, g, m, v and ema must be 16-byte aligned; any n > 0 (scalar tail for
+ * n % 4).  No atomics.  NULL pointers, n <= 0, a misaligned buffer or ema_decay outside (0, 1) return SGG_EINVAL, a short ws
+ * with guarded SGG_EWORKSPACE -- before anything is launched. */
+int sgg_adam_ema(float* theta, const float* g, float* m, float* v, float* ema, int64_t n, int64_t* state, const int64_t* sched,
+                 float lr, float beta1, float beta2, float eps, float grad_scale, float ema_decay, float* ema_state,
+                 float max_norm, int guarded, double* guard, void* ws, size_t ws_bytes, void* stream);
+/* Exchange the contents of two n-element buffers (16-byte aligned, n > 0) bit for bit in one pass. */
+int sgg_swap_f32(float* a, float* b, int64_t n, void* stream);
 
 /* ---- data side of the step ----
  * segment_class.py:60-70,95-97: colour -> class index, bit exact.  rgb: uint8 [n_pixels][channels>=3]. */

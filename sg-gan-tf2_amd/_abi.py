@@ -115,6 +115,8 @@ SIGNATURES = {
     "sgg_grad_guard_workspace": (_sz, [_i64]),
     "sgg_grad_sumsq": (_i, [_vp, _i64, _vp, _sz, _vp]),
     "sgg_adam_guard": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
+    "sgg_adam_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _f, _i, _vp, _vp, _sz, _vp]),
+    "sgg_swap_f32": (_i, [_vp, _vp, _i64, _vp]),
     "sgg_seg_class_map": (_i, [_vp, _i, _i64, _vp, _vp]),
     "sgg_seg_class_table": (_i, [_vp, _vp, _i]),
     "sgg_onehot_resample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -830,6 +830,32 @@ def guarded_update(theta, g, m, v, iterations, lr=1e-3, beta1=0.5, beta2=0.999, 
     return theta - lr_t * m / (np.sqrt(v) + eps), m, v, t, info
 
 
+EMA_CHUNK = 2048                 # elements per block of the fused update and of swap_ (EMA_CHUNK, csrc/misc.hip)
+
+
+def adam_ema(theta, g, m, v, ema, state, ema_state, ema_decay, sched=None, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0,
+             guard=None, ws=None, max_norm=0.0):
+    """``adam_iter`` / ``adam_sched`` (``guard`` None) or ``adam_guard`` (``guard`` and ``ws`` given) that also keeps ``ema``, the
+    exponential moving average of ``theta``, in the same launches: ``ema = d_t ema + (1 - d_t) theta_new`` with ``d_t = min(ema_decay, (1 + t) / (10 + t))``, t = iterations
+    after the update (include/sggan.h).  ``ema_state`` is a device
+    float32[2] = [d_t, 1 - d_t], written by the prep launch; theta, m, v, iterations and the guard record come out with the
+    bits of the calls named above."""
+    assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel() == ema.numel()
+    assert state.dtype == torch.int64 and state.numel() == 2
+    assert ema.dtype == torch.float32 and ema_state.dtype == torch.float32 and ema_state.numel() == 2
+    assert sched is None or (sched.dtype == torch.int64 and sched.numel() == 3)
+    assert guard is None or (guard.dtype == torch.float64 and guard.numel() == 4 and ws is not None)
+    A.check(A.lib().sgg_adam_ema(_p(theta), _p(g), _p(m), _p(v), _p(ema), theta.numel(), _p(state), _p(sched), lr, beta1, beta2, eps,
+                                 grad_scale, float(ema_decay), _p(ema_state), float(max_norm), int(guard is not None), _p(guard),
+                                 _p(ws) if guard is not None else None, ws.numel() if guard is not None else 0, _s()), "adam_ema")
+
+
+def swap_(a, b):
+    """Exchange the contents of two float32 buffers of equal length bit for bit, in place, in one pass (``sgg_swap_f32``)."""
+    assert a.dtype == b.dtype == torch.float32 and a.numel() == b.numel()
+    A.check(A.lib().sgg_swap_f32(_p(a), _p(b), a.numel(), _s()), "swap_")
+
+
 # ----------------------------------------------------------------------------- data side
 def seg_class_map(rgb_u8):
     """uint8 (..., M, N, 3|4) -> uint8 (..., M, N) class indices (segment_class.py:60-99), bit exact."""

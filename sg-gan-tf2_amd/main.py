@@ -79,6 +79,11 @@ def build_parser():
     a("--skip_nonfinite", dest="skip_nonfinite", action="store_true", default=argparse.SUPPRESS,
       help="skip a network's update when its gradient holds a NaN or Inf: parameters, Adam slots and step counter keep their "
            "bits and the skip is counted ('<network> Skipped Updates' scalar at epoch end)")
+    a("--ema_decay", dest="ema_decay", type=float, default=argparse.SUPPRESS,
+      help="keep an exponential moving average of the generator weights with this decay (in (0, 1), e.g. 0.999; default: off) and "
+           "run the epoch-end test pass and --phase test on the average; the average is updated inside the Adam launch with "
+           "the ramp min(decay, (1 + t) / (10 + t)) over applied updates, so it works under --graph, leaves the average alone when "
+           "an update is skipped, and goes on after --continue_train")
     # (absent from the namespace unless given, like the guard flags)
     a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
       help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "

@@ -8,6 +8,7 @@ parameter/gradient buffers and (optionally) overlaps the data-parallel gradient 
 """
 from __future__ import annotations
 
+import contextlib
 from types import SimpleNamespace
 
 import numpy as np
@@ -32,7 +33,7 @@ def default_args(**over):
              dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=None,
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
-             crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False)
+             crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -115,11 +116,24 @@ class sggan(object):
         self.clip_grad_norm = max(float(g("clip_grad_norm", 0.0) or 0.0), 0.0)
         self.skip_nonfinite = bool(g("skip_nonfinite", False))
         okw = dict(schedule=self._lr_sched, clip_norm=self.clip_grad_norm or None, skip_nonfinite=self.skip_nonfinite)
-        self.g_optim = Adam(self.generator, lr, self.beta1, **okw)
+        # ema_decay (off by default): the generators' updates also keep an exponential moving average of their
+        # parameters, in the update's own launches -- the decay ramp follows the device step counter and a skipped update
+        # leaves the average alone -- and the test passes run on the average (ema_weights).  Data parallel: nothing to
+        # exchange, every rank applies the same update to the same average.
+        ema = g("ema_decay", None)
+        self.ema_decay = None if ema is None else float(ema)
+        if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:
+            raise ValueError(f"ema_decay must lie in (0, 1), got {ema!r}")
+        gkw = dict(okw, ema_decay=self.ema_decay)
+        self.g_optim = Adam(self.generator, lr, self.beta1, **gkw)
         self.d_optim = Adam(self.discriminator, lr, self.beta1, **okw)
         if self.cycle:
-            self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1, **okw)
+            self.g_optim_BA = Adam(self.generator_BA, lr, self.beta1, **gkw)
             self.d_optim_B = Adam(self.discriminator_B, lr, self.beta1, **okw)
+        if self.ema_decay is not None:
+            for net in self._ema_nets():
+                net.P.enable_ema()
+        self._ema_notice = False
         # cycle step: run the two generators (and the two discriminators) in lockstep on stacked batches (module._PairUnit);
         # bit-identical to the one-network-at-a-time sequencing, which stays for the image pool and for mixed mode.  paired=None
         # picks the default: on for the ResNet (the step bench.py times); off for the U-Net, whose step is bound by
@@ -281,6 +295,7 @@ class sggan(object):
         nets = self.networks()
         keep = [(n.P.flat.clone(), n.P.m.clone(), n.P.v.clone(), n.P.iterations.clone()) for n in nets]
         guard_keep = [None if n.P._guard is None else n.P._guard.clone() for n in nets]     # (the warm-up step counts as none)
+        ema_keep = [None if n.P.ema is None else (n.P.ema.clone(), n.P._ema_state.clone()) for n in nets]
         loss_keep = self._loss.clone()
         hook, K.PROFILE = K.PROFILE, None          # timing hooks (bench.py) record events: not while recording
         try:
@@ -299,6 +314,9 @@ class sggan(object):
                     n.P._guard.copy_(rec)
                 elif n.P._guard is not None:       # first allocated by the warm-up step
                     n.P._guard.zero_()
+            for n, kept in zip(nets, ema_keep):
+                if kept is not None:
+                    n.P.ema.copy_(kept[0]); n.P._ema_state.copy_(kept[1])
             self._loss.copy_(loss_keep)
             prog = StepProgram(self.device)
             K._RECORDER = prog
@@ -430,6 +448,32 @@ class sggan(object):
     @property
     def guarded(self):
         return self.clip_grad_norm > 0 or self.skip_nonfinite
+
+    def _ema_nets(self):
+        return (self.generator, self.generator_BA) if self.cycle else (self.generator,)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the generators on the moving average of their weights (``ema_decay`` models only): on entry each generator's
+        ``P.flat`` and ``P.ema`` change contents (K.swap_, one pass, bit for bit) and ``P.version`` is bumped so the packed
+        operands are rebuilt; on exit they change back.  The trained weights return with every bit, so a step after the
+        context -- eager or replayed from a recording made before it -- is the step it would have been.  Data parallel:
+        nothing to exchange; every rank holds the same average, because every rank applies the same updates."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_weights: this model was built without ema_decay")
+        def swap():
+            for net in self._ema_nets():
+                K.swap_(net.P.flat, net.P.ema)
+                net.P.version += 1
+        swap()
+        try:
+            yield self
+        finally:
+            swap()
+
+    def _test_weights(self):
+        """The weights the test passes run on: the average where the model keeps one, else the parameters as they are."""
+        return self.ema_weights() if self.ema_decay is not None else contextlib.nullcontext()
 
     def grad_stats(self):
         """The guarded updates' records, {"G": {"norm", "clip", "skipped", "applied"}, "D": ...}: the last step's global
@@ -662,6 +706,8 @@ class sggan(object):
             sd[key] = {"flat": P.flat.cpu(), "m": P.m.cpu(), "v": P.v.cpu(), "t": P.step_count}
             if P._guard is not None:            # the guarded update's counters [skipped_total, applied_total]
                 sd[key]["guard"] = [int(c) for c in P._guard[2:4].cpu().tolist()]
+            if P.ema is not None:               # the moving average of the generator's parameters (ema_decay)
+                sd[key]["ema"] = P.ema.cpu()
         sd["G"]["arch"] = self.arch             # generator architecture tag (a checkpoint without one is a ResNet checkpoint)
         return sd
 
@@ -680,6 +726,12 @@ class sggan(object):
                 P.guard_buffers()[0][2:4].copy_(torch.tensor([float(c) for c in counters], dtype=torch.float64))
             elif P._guard is not None:
                 P._guard[2:4].zero_()
+            if P.ema is not None:               # (a model without ema_decay ignores the key)
+                ema = sd[key].get("ema")
+                if ema is None and not self._ema_notice:
+                    self._ema_notice = True
+                    print(" [*] checkpoint without a weight average: the average starts from the loaded weights")
+                P.ema.copy_(sd[key]["flat"] if ema is None else ema)
 
     def _ckpt_paths(self, checkpoint_dir, ep=None):
         """model.py:454-456: <checkpoint_dir>/<dataset_dir>/{gen,disc}/cp-{epoch:04d}.ckpt"""
@@ -741,7 +793,9 @@ class sggan(object):
         above follow 'Class Overall Accuracy' ... 'Class Mean IoU', with ``args.boundary_px`` > 0 'Boundary Class Mean IoU' (the
         pixels within that distance of a ground-truth class boundary), and with ``args.crf`` as well the four 'Class CRF ...'
         scores of the CRF-refined map (metric.scores_class_fake_crf); the returned scores gain "Class", "Class Boundary" and
-        "Class CRF"."""
+        "Class CRF".
+        A model built with ``ema_decay`` translates with the moving average of the generator's weights
+        (ema_weights) and logs 'EMA Decay', the decay its last applied update used, after all the scalars above."""
         from . import metric as M
         from .utils import convert_image_dtype_uint8, get_img, save_images
         import os
@@ -757,33 +811,34 @@ class sggan(object):
             class_hist = {k: torch.zeros((n_class, n_class), dtype=torch.int64, device=self.device)
                           for k, on in (("Class", True), ("Class Boundary", band_px > 0), ("Class CRF", crf)) if on}
         test_dir = getattr(args, "test_dir", None)
-        for item in samples:
-            name, sample_image, seg_image = item[:3]
-            rescaled = convert_image_dtype_uint8(np.asarray(sample_image)[None])                 # :352-353
-            fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))                   # :357
-            if test_dir:
-                os.makedirs(test_dir, exist_ok=True)
-                save_images(fake_A, [1, 1], os.path.join(test_dir, os.path.basename(name)))      # :362-365
-            fake_img = get_img(fake_A, [1, 1])                                                   # :369
-            outputs.append(fake_img)
-            lt, lp = M.scores_seg_fake(np.asarray(seg_image, dtype=np.float32)[None], torch.as_tensor(fake_img.astype(np.float32)))   # :373
-            preds += list(lp); gts += list(lt)
-            if crf:
-                if len(item) < 4:
-                    raise ValueError("crf: test samples must carry the one-hot class mask (data.directory_test_samples over a "
-                                     "DatasetCache(with_class=True))")
-                lt2, lp2 = M.scores_mask_sample_crf(np.asarray(item[3])[None], rescaled)          # :330,338 seg_mask_64
-                preds2 += list(lp2); gts2 += list(lt2)
-            if class_scores:
-                if len(item) < 4:
-                    raise ValueError("class_scores: test samples must carry the one-hot class mask (data.directory_test_samples "
-                                     "over a DatasetCache(with_class=True))")
-                truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
-                M.scores_class_fake(truth, fake_A, n_class, class_palette, hist=class_hist["Class"], **decode)
-                if "Class Boundary" in class_hist:
-                    M.scores_class_fake(truth, fake_A, n_class, class_palette, band_radius=band_px, hist=class_hist["Class Boundary"], **decode)
+        with self._test_weights():                  # (the moving average, where the model keeps one)
+            for item in samples:
+                name, sample_image, seg_image = item[:3]
+                rescaled = convert_image_dtype_uint8(np.asarray(sample_image)[None])                 # :352-353
+                fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))                   # :357
+                if test_dir:
+                    os.makedirs(test_dir, exist_ok=True)
+                    save_images(fake_A, [1, 1], os.path.join(test_dir, os.path.basename(name)))      # :362-365
+                fake_img = get_img(fake_A, [1, 1])                                                   # :369
+                outputs.append(fake_img)
+                lt, lp = M.scores_seg_fake(np.asarray(seg_image, dtype=np.float32)[None], torch.as_tensor(fake_img.astype(np.float32)))   # :373
+                preds += list(lp); gts += list(lt)
                 if crf:
-                    M.scores_class_fake_crf(truth, rescaled, fake_A, n_class, class_palette, hist=class_hist["Class CRF"], **decode)
+                    if len(item) < 4:
+                        raise ValueError("crf: test samples must carry the one-hot class mask (data.directory_test_samples over a "
+                                         "DatasetCache(with_class=True))")
+                    lt2, lp2 = M.scores_mask_sample_crf(np.asarray(item[3])[None], rescaled)          # :330,338 seg_mask_64
+                    preds2 += list(lp2); gts2 += list(lt2)
+                if class_scores:
+                    if len(item) < 4:
+                        raise ValueError("class_scores: test samples must carry the one-hot class mask (data.directory_test_samples "
+                                         "over a DatasetCache(with_class=True))")
+                    truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
+                    M.scores_class_fake(truth, fake_A, n_class, class_palette, hist=class_hist["Class"], **decode)
+                    if "Class Boundary" in class_hist:
+                        M.scores_class_fake(truth, fake_A, n_class, class_palette, band_radius=band_px, hist=class_hist["Class Boundary"], **decode)
+                    if crf:
+                        M.scores_class_fake_crf(truth, rescaled, fake_A, n_class, class_palette, hist=class_hist["Class CRF"], **decode)
         score = M.scores(gts, preds, n_class=args.segment_class)                                 # :378
         if sink is not None:                                                                     # :389-393
             sink.scalar("Overall Accuracy", score["Overall Acc"], epoch)
@@ -806,6 +861,8 @@ class sggan(object):
                     sink.scalar("Boundary Class Mean IoU", score["Class Boundary"]["Mean IoU"], epoch)
                 if "Class CRF" in score:
                     self._class_scalars(sink, "Class CRF ", score["Class CRF"], epoch)
+        if self.ema_decay is not None and sink is not None:     # the decay the generator's last applied update used
+            sink.scalar("EMA Decay", float(self.generator.P._ema_state[0].item()), epoch)
         return (np.concatenate(outputs, axis=0) if outputs else None), score
 
     @staticmethod
@@ -819,7 +876,8 @@ class sggan(object):
         """model.py:535-567 (--phase test): load the latest checkpoint, translate every test sample and save the input and the
         translation under ``args.test_dir``.  ``samples`` yields (name, sample_image (H,W,3) in [0,1]).  With
         ``args.class_scores`` and samples that carry the one-hot class mask as their fourth element, the four class-level scores
-        of the translations are logged at the end."""
+        of the translations are logged at the end.  A model built with ``ema_decay`` translates with the moving
+        average of the generator's weights, as the checkpoint holds it."""
         from . import metric as M
         from .utils import convert_image_dtype_uint8, save_images
         import os
@@ -828,19 +886,20 @@ class sggan(object):
         log(" [*] Load SUCCESS" if self.load(args.checkpoint_dir) else " [!] Load failed...")
         os.makedirs(args.test_dir, exist_ok=True)
         out = []
-        for item in samples:
-            name, sample_image = item[0], np.asarray(item[1], dtype=np.float32)
-            log("Processing image: " + name)
-            rescaled = convert_image_dtype_uint8(sample_image[None])
-            fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))
-            save_images(sample_image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(name)))
-            save_images(fake_A, [1, 1], os.path.join(args.test_dir, os.path.basename(name)))
-            out.append(fake_A)
-            if getattr(args, "class_scores", False) and len(item) >= 4:
-                truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
-                far = int(getattr(args, "class_max_dist", -1))
-                class_hist = M.scores_class_fake(truth, fake_A, args.segment_class, getattr(args, "class_palette", None), hist=class_hist,
-                                                 max_dist2=far * far if far >= 0 else -1)
+        with self._test_weights():                  # (the moving average, where the model keeps one)
+            for item in samples:
+                name, sample_image = item[0], np.asarray(item[1], dtype=np.float32)
+                log("Processing image: " + name)
+                rescaled = convert_image_dtype_uint8(sample_image[None])
+                fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))
+                save_images(sample_image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(name)))
+                save_images(fake_A, [1, 1], os.path.join(args.test_dir, os.path.basename(name)))
+                out.append(fake_A)
+                if getattr(args, "class_scores", False) and len(item) >= 4:
+                    truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
+                    far = int(getattr(args, "class_max_dist", -1))
+                    class_hist = M.scores_class_fake(truth, fake_A, args.segment_class, getattr(args, "class_palette", None), hist=class_hist,
+                                                     max_dist2=far * far if far >= 0 else -1)
         if class_hist is not None:
             s = M.scores_from_hist(class_hist)
             log("Class Overall Accuracy: %f Class Mean Accuracy: %f Class Frequency Weighted Accuracy: %f Class Mean IoU: %f"

@@ -49,6 +49,8 @@ class ParamStore:
         # the guarded update's record [last_norm, last_clip, skipped_total, applied_total] and workspace: device memory,
         # allocated at the first guarded step (guard_buffers), so a model without the options carries neither
         self._guard = self._guard_ws = None
+        # the moving average of `flat` and its [d_t, 1 - d_t] (enable_ema): a store without it carries neither
+        self.ema = self._ema_state = None
 
     @property
     def step_count(self):
@@ -124,14 +126,31 @@ class ParamStore:
             self._guard_ws = K.grad_guard_workspace(self.numel, self.device)
         return self._guard, self._guard_ws
 
-    def adam_step(self, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, schedule=None, max_norm=None, guard=False):
+    def enable_ema(self):
+        """Allocate ``ema``, the exponential moving average of ``flat`` that ``adam_step(ema_decay=...)`` keeps, as a copy of
+        ``flat`` as it is now (call it after init or load), and the device float32[2] [d_t, 1 - d_t] its launches hand over."""
+        if self.ema is None:
+            self.ema = self.flat.clone()
+            self._ema_state = torch.zeros(2, dtype=torch.float32, device=self.device)
+        return self.ema
+
+    def adam_step(self, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, schedule=None, max_norm=None, guard=False,
+                  ema_decay=None):
         """tf.keras.optimizers.Adam.apply_gradients (model.py:199-200) over the whole network: one launch.  ``schedule``: a
         device int64[3] [steps_per_epoch, epoch_step, epochs] -- ``lr`` is then the base rate of the linear decay of
         model.py:223, evaluated on the device from ``iterations`` (K.adam_sched); None: ``lr`` as it is.  ``max_norm`` (clip
         the gradient's global L2 norm to it) and ``guard`` (skip the update when the gradient holds a NaN or Inf) send the
         step through K.adam_guard instead, which decides on the device; clipping implies the skip, since a non-finite norm
-        has no clip factor.  With neither, the launches are the ones above and nothing else."""
-        if max_norm is not None or guard:
+        has no clip factor.  With neither, the launches are the ones above and nothing else.  ``ema_decay``: the same launches
+        through K.adam_ema, which also moves ``ema`` towards the new parameters (enable_ema first); a skipped update leaves
+        the average alone.  None: exactly the launches above."""
+        if ema_decay is not None:
+            if self.ema is None:
+                raise RuntimeError("adam_step(ema_decay=...): call enable_ema() first")
+            rec, ws = self.guard_buffers() if max_norm is not None or guard else (None, None)
+            K.adam_ema(self.flat, self.grad, self.m, self.v, self.ema, self._adam_state, self._ema_state, ema_decay, schedule, lr, beta1,
+                       beta2, eps, grad_scale, rec, ws, 0.0 if max_norm is None else max_norm)
+        elif max_norm is not None or guard:
             rec, ws = self.guard_buffers()
             K.adam_guard(self.flat, self.grad, self.m, self.v, self._adam_state, rec, ws, schedule, lr, beta1, beta2, eps, grad_scale,
                          0.0 if max_norm is None else max_norm)
@@ -147,12 +166,14 @@ class Adam:
     199-200, 205-207), bound to one network's flat parameter store: the whole update is one fused launch."""
 
     def __init__(self, net, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule=None, clip_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, ema_decay=None):
         self.net, self.learning_rate, self.beta_1, self.beta_2, self.epsilon = net, learning_rate, beta_1, beta_2, epsilon
         # clip_norm: clip the global L2 norm of the network's gradient to it (None or <= 0: off); skip_nonfinite: leave the
         # network and its Adam state alone for a step whose gradient holds a NaN or Inf (ParamStore.adam_step)
         self.clip_norm = float(clip_norm) if clip_norm is not None and float(clip_norm) > 0 else None
         self.skip_nonfinite = bool(skip_nonfinite)
+        # ema_decay: keep the network's ParamStore.ema in the update's launches (None: off)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
         # device int64[3] [steps_per_epoch, epoch_step, epochs] or None (ParamStore.adam_step): with it, learning_rate is the
         # base rate of the linear decay
         self.schedule = schedule
@@ -177,7 +198,7 @@ class Adam:
                 if g is not None:
                     P.g(name).copy_(torch.as_tensor(g, device=P.device).reshape(P.g(name).shape))
         P.adam_step(self.learning_rate, self.beta_1, self.beta_2, self.epsilon, grad_scale, self.schedule, self.clip_norm,
-                    self.skip_nonfinite)
+                    self.skip_nonfinite, self.ema_decay)
 
 
 def _layer_specs(name, shape, out_ch, norm=True):

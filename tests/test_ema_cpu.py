@@ -1,0 +1,233 @@
+"""CPU-side checks of the generator weight average (--ema_decay): the float64 statement of the rule
+(tests/ema_oracle.py), the C ABI of sgg_adam_ema / sgg_swap_f32, the build resources of their kernels, the flag, and the
+checkpoint key handling of sggan.state_dict / load_state_dict on host-memory parameter stores."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from sggan_amd import _abi as A
+from tests import ema_oracle as E
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LR, B1, B2, EPS = 2e-4, 0.5, 0.999, 1e-7
+
+
+# ----------------------------------------------------------------------------- the oracle itself
+def test_decay_ramp_values_and_where_it_ends():
+    """d_t for t = 1, 2, 10 is 2/11, 3/12, 11/20 (under a decay above them); the ramp hands over to the decay D at the first t
+    with (1 + t) / (10 + t) >= D, and never exceeds D."""
+    assert [E.decay_at(0.999, t) for t in (1, 2, 10)] == [2.0 / 11.0, 3.0 / 12.0, 11.0 / 20.0]
+    for D in (0.2, 0.5, 0.9, 0.999, 0.9999):
+        end = E.ramp_end(D)
+        assert (1.0 + end) / (10.0 + end) >= D and (end == 0 or end / (9.0 + end) < D)
+        assert all(E.decay_at(D, t) == (1.0 + t) / (10.0 + t) < D for t in range(0, end))
+        assert all(E.decay_at(D, t) == D for t in (end, end + 1, 10 * end + 7))
+    assert E.ramp_end(0.5) == 8 and E.ramp_end(0.999) == 8990            # (1 + t) / (10 + t) >= D  <=>  t >= (10 D - 1) / (1 - D)
+    d, omd = E.decay_f32(0.999, 5)
+    assert d.dtype == omd.dtype == np.float32 and d == np.float32(6.0 / 15.0) and omd == np.float32(1.0) - d
+    d, omd = E.decay_f32(0.999, 10 ** 6)
+    assert d == np.float32(0.999) and float(omd) == 1.0 - float(np.float32(0.999))   # (exact: Sterbenz, d >= 1/2)
+
+
+def test_constant_parameters_are_a_fixed_point():
+    """ema == theta and theta never moves: the average stays where it is -- to the rounding of the f32 complement 1 - d_t, which
+    for d_t < 1/2 is not exact, so d_t + (1 - d_t) may miss 1 by 2^-25 per step -- and an average away from theta closes in."""
+    th = np.ones(7)
+    ema, max_abs = E.ema_run(th, [th] * 30, 0.999)
+    assert np.abs(ema - th).max() <= 30 * 2.0 ** -25 and abs(max_abs - 1.0) <= 30 * 2.0 ** -25
+    tail, _ = E.ema_run(th, [th] * 5, 0.999, t0=10 ** 5)                 # past the ramp d_t >= 1/2: the complement is exact
+    assert np.array_equal(tail, th)
+    rng = np.random.default_rng(3)
+    th = rng.standard_normal(33)
+    ema, _ = E.ema_run(th, [th] * 30, 0.9)
+    assert np.abs(ema - th).max() <= 30 * 2.0 ** -24 * np.abs(th).max()
+    far, _ = E.ema_run(np.zeros(33), [th] * 200, 0.9)
+    assert np.abs(far - th).max() < 1e-6 * np.abs(th).max()
+    one, _ = E.ema_run(np.zeros(33), [th], 0.9)                          # first step: d_1 = 2 / 11
+    d, omd = E.decay_f32(0.9, 1)
+    assert d == np.float32(2.0 / 11.0) and np.array_equal(one, float(omd) * th)
+
+
+# ----------------------------------------------------------------------------- C ABI
+def _params(src, name):
+    decl = re.search(r"\b%s\((.*?)\);" % name, src, flags=re.S)
+    assert decl, name + " not declared"
+    return [" ".join(p.split()) for p in decl.group(1).split(",")]
+
+
+def test_ema_entry_points_are_declared_exported_and_bound():
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sggan.h")).read(), flags=re.S)
+    assert _params(src, "int sgg_adam_ema") == [
+        "float* theta", "const float* g", "float* m", "float* v", "float* ema", "int64_t n", "int64_t* state", "const int64_t* sched",
+        "float lr", "float beta1", "float beta2", "float eps", "float grad_scale", "float ema_decay", "float* ema_state",
+        "float max_norm", "int guarded", "double* guard", "void* ws", "size_t ws_bytes", "void* stream"]
+    assert _params(src, "int sgg_swap_f32") == ["float* a", "float* b", "int64_t n", "void* stream"]
+    vp, f, i, i64, sz = C.c_void_p, C.c_float, C.c_int, C.c_int64, C.c_size_t
+    assert A.SIGNATURES["sgg_adam_ema"] == (i, [vp, vp, vp, vp, vp, i64, vp, vp, f, f, f, f, f, f, vp, f, i, vp, vp, sz, vp])
+    assert A.SIGNATURES["sgg_swap_f32"] == (i, [vp, vp, i64, vp])
+    L = A.lib()
+    assert L.sgg_adam_ema.argtypes == A.SIGNATURES["sgg_adam_ema"][1] and L.sgg_swap_f32.argtypes == A.SIGNATURES["sgg_swap_f32"][1]
+    from sggan_amd import kernels as K
+    assert callable(K.adam_ema) and callable(K.swap_) and K.EMA_CHUNK % 1024 == 0
+    assert re.search(r"#define EMA_CHUNK %d\b" % K.EMA_CHUNK, open(os.path.join(ROOT, "sg-gan-tf2_amd", "csrc", "misc.hip")).read())
+
+
+def test_ema_entry_points_validate_on_the_host():
+    """NULL pointers, n <= 0, a misaligned buffer and ema_decay outside (0, 1) return SGG_EINVAL; a short workspace with
+    ``guarded`` returns SGG_EWORKSPACE; without ``guarded`` no workspace is asked for.  All before any launch: the buffers are
+    host memory that is never dereferenced, and no GPU is needed."""
+    L = A.lib()
+    raw = (C.c_char * 256)()
+    base = (C.addressof(raw) + 15) & ~15
+    p, odd = C.c_void_p(base), C.c_void_p(base + 4)
+    n = 3 * 2048 + 13
+    need = L.sgg_grad_guard_workspace(n)
+    hp = (LR, B1, B2, EPS, 1.0)
+
+    def call(theta=p, g=p, m=p, v=p, ema=p, n=n, state=p, sched=None, decay=0.999, ema_state=p, guarded=0, guard=None, ws=None, ws_bytes=0):
+        return L.sgg_adam_ema(theta, g, m, v, ema, n, state, sched, *hp, decay, ema_state, 0.0, guarded, guard, ws, ws_bytes, None)
+
+    for hole in ("theta", "g", "m", "v", "ema", "state", "ema_state"):
+        assert call(**{hole: None}) == A.EINVAL, hole
+        assert call(**{hole: None}, guarded=1, guard=p, ws=p, ws_bytes=need) == A.EINVAL, hole
+    for hole in ("theta", "g", "m", "v", "ema"):
+        assert call(**{hole: odd}) == A.EINVAL, hole
+    assert call(n=0) == A.EINVAL and call(n=-5) == A.EINVAL
+    for decay in (0.0, 1.0, -0.5, 1.5, float("nan"), float("inf")):
+        assert call(decay=decay) == A.EINVAL, decay
+        assert call(decay=decay, guarded=1, guard=p, ws=p, ws_bytes=need) == A.EINVAL, decay
+    assert call(guarded=1, guard=None, ws=p, ws_bytes=need) == A.EINVAL
+    assert call(guarded=1, guard=p, ws=None, ws_bytes=need) == A.EINVAL
+    assert call(guarded=1, guard=p, ws=p, ws_bytes=need - 1) == A.EWORKSPACE
+    assert call(guarded=1, guard=p, ws=p, ws_bytes=0) == A.EWORKSPACE
+    assert call(guarded=1, guard=p, ws=p, ws_bytes=16, sched=p) == A.EWORKSPACE
+
+    assert L.sgg_swap_f32(None, p, n, None) == A.EINVAL and L.sgg_swap_f32(p, None, n, None) == A.EINVAL
+    assert L.sgg_swap_f32(p, p, 0, None) == A.EINVAL and L.sgg_swap_f32(p, p, -1, None) == A.EINVAL
+    assert L.sgg_swap_f32(odd, p, n, None) == A.EINVAL and L.sgg_swap_f32(p, odd, n, None) == A.EINVAL
+
+
+# ----------------------------------------------------------------------------- build
+def test_ema_kernels_do_not_spill_and_use_no_scratch(tmp_path):
+    """csrc/misc.hip recompiled with -Rpass-analysis=kernel-resource-usage (the method of tests/test_build_resources.py): the
+    three new kernels are in the build, each once, with zero VGPR / SGPR spills and no scratch.  The update kernel keeps its
+    ten 16-byte loads (40 VGPRs) in flight and still runs several waves per SIMD; the swap needs no LDS."""
+    sys.path.insert(0, os.path.join(ROOT, "sg-gan-tf2_amd"))
+    import build as B
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("hipcc not available")
+    r = subprocess.run([hipcc, *B.FLAGS, "-c", os.path.join(B.CSRC, "misc.hip"), "-o", str(tmp_path / "misc.o"),
+                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    usage, name = {}, None
+    pats = (("vspill", r"VGPRs Spill: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+            ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("vgpr", r" VGPRs: (\d+)"))
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+            continue
+        for key, pat in pats:
+            m = re.search(pat, line)
+            if m and name:
+                usage[name][key] = int(m.group(1))
+    for frag, lds, min_occ in (("adam_ema_prep_kernel", 3072, 8), ("adam_ema_kernel", 0, 4), ("swap_f32_kernel", 0, 8)):
+        hits = [v for k, v in usage.items() if frag in k]
+        assert len(hits) == 1, f"kernel {frag}: {len(hits)} matches in the build"
+        u = hits[0]
+        print(frag, u)
+        assert (u["vspill"], u["sspill"], u["scratch"], u["lds"]) == (0, 0, 0, lds) and u["occ"] >= min_occ, (frag, u)
+    assert [v for k, v in usage.items() if "adam_ema_kernel" in k][0]["vgpr"] >= 40
+
+
+# ----------------------------------------------------------------------------- flag
+def test_ema_flag_and_default_arguments():
+    from sggan_amd.main import build_parser, parse_args
+    from sggan_amd.model import default_args
+    assert not hasattr(parse_args([]), "ema_decay") and "ema_decay" not in vars(parse_args(["--skip_nonfinite"]))
+    assert parse_args(["--ema_decay", "0.999"]).ema_decay == 0.999
+    with pytest.raises(SystemExit):
+        parse_args(["--ema_decay", "slow"])
+    text = " ".join(build_parser().format_help().split())
+    for word in ("--ema_decay", "moving average", "(0, 1)"):
+        assert word in text, word
+    assert default_args().ema_decay is None and default_args(ema_decay=0.99).ema_decay == 0.99
+
+
+def test_optimizer_and_store_carry_no_average_by_default():
+    from sggan_amd.module import Adam, ParamStore, discriminator_param_specs
+
+    class _Net:
+        P = ParamStore(discriminator_param_specs(df_dim=8), "cpu")
+    assert Adam(_Net()).ema_decay is None and _Net.P.ema is None and _Net.P._ema_state is None
+    assert Adam(_Net(), ema_decay=0.99).ema_decay == 0.99 and _Net.P.ema is None      # (the optimizer allocates nothing)
+    with pytest.raises(RuntimeError, match="enable_ema"):
+        _Net.P.adam_step(ema_decay=0.99)
+    _Net.P.flat[:5] = torch.arange(5.0)
+    ema = _Net.P.enable_ema()
+    assert ema is _Net.P.ema and torch.equal(ema, _Net.P.flat) and ema.data_ptr() != _Net.P.flat.data_ptr()
+    assert _Net.P._ema_state.dtype == torch.float32 and _Net.P._ema_state.tolist() == [0.0, 0.0]
+    _Net.P.flat[0] = 9.0
+    assert _Net.P.enable_ema() is ema and ema[0].item() == 0.0                         # (a second call keeps the average)
+
+
+# ----------------------------------------------------------------------------- checkpoints, on host-memory stores
+def _stub(ema_decay, seed):
+    """An sggan with its two parameter stores in host memory and nothing else: what state_dict / load_state_dict touch."""
+    from sggan_amd.model import sggan
+    from sggan_amd.module import ParamStore, discriminator_param_specs, generator_param_specs
+
+    class _Net:
+        def __init__(self, specs, seed):
+            self.P = ParamStore(specs, "cpu")
+            g = torch.Generator().manual_seed(seed)
+            for buf in (self.P.flat, self.P.m, self.P.v):
+                buf.copy_(torch.randn(self.P.numel, generator=g))
+            self.P.step_count = seed
+    m = sggan.__new__(sggan)
+    m.cycle, m.arch, m.ema_decay, m._ema_notice = False, "resnet", ema_decay, False
+    m.generator = _Net(generator_param_specs(gf_dim=8, n_blocks=1), seed)
+    m.discriminator = _Net(discriminator_param_specs(df_dim=8), seed + 1)
+    if ema_decay is not None:
+        m.generator.P.enable_ema()
+        m.generator.P.ema.mul_(0.5)                         # (an average that differs from the weights)
+    return m
+
+
+@pytest.mark.parametrize("ckpt_has", [False, True], ids=["ckpt-plain", "ckpt-ema"])
+@pytest.mark.parametrize("model_has", [False, True], ids=["model-plain", "model-ema"])
+def test_checkpoint_key_in_all_four_combinations(ckpt_has, model_has, capsys):
+    """state_dict carries "ema" for the generator of an EMA model only.  Loading: key + EMA model restores the average bitwise;
+    no key + EMA model sets the average to the loaded weights and says so once; a plain model ignores the key and allocates
+    nothing.  Weights, slots and step counts load as they always did."""
+    src = _stub(0.999 if ckpt_has else None, 3)
+    sd = src.state_dict()
+    assert ("ema" in sd["G"]) == ckpt_has and "ema" not in sd["D"]
+    if ckpt_has:
+        assert torch.equal(sd["G"]["ema"], src.generator.P.ema) and not torch.equal(sd["G"]["ema"], sd["G"]["flat"])
+    dst = _stub(0.999 if model_has else None, 11)
+    capsys.readouterr()
+    dst.load_state_dict(sd)
+    dst.load_state_dict(sd)
+    said = capsys.readouterr().out
+    for a, b in ((src.generator, dst.generator), (src.discriminator, dst.discriminator)):
+        assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in ((a.P.flat, b.P.flat), (a.P.m, b.P.m), (a.P.v, b.P.v)))
+        assert a.P.step_count == b.P.step_count
+    assert dst.discriminator.P.ema is None
+    if not model_has:
+        assert dst.generator.P.ema is None and dst.generator.P._ema_state is None and said == ""
+        assert "ema" not in dst.state_dict()["G"]
+    elif ckpt_has:
+        assert torch.equal(dst.generator.P.ema.view(torch.int32), src.generator.P.ema.view(torch.int32)) and said == ""
+    else:
+        assert torch.equal(dst.generator.P.ema.view(torch.int32), src.generator.P.flat.view(torch.int32))
+        assert said.count("\n") == 1 and "average" in said                              # once, not per load
