@@ -33,7 +33,7 @@ extern "C" {
 #define SGG_CPAD 8               /* activation channel granule */
 
 typedef enum { SGG_OK = 0, SGG_EINVAL = -1, SGG_EUNSUPPORTED = -2, SGG_ELAUNCH = -3, SGG_EWORKSPACE = -4 } sgg_status;
-typedef enum { SGG_F32 = 0, SGG_BF16 = 1, SGG_U8 = 2 /* image input of sgg_palette_* only */ } sgg_dtype;
+typedef enum { SGG_F32 = 0, SGG_BF16 = 1, SGG_U8 = 2 /* image input of sgg_palette_* and sgg_image_quality only */ } sgg_dtype;
 typedef enum { SGG_ACT_NONE = 0, SGG_ACT_RELU = 1, SGG_ACT_LRELU = 2, SGG_ACT_TANH = 3 } sgg_act;
 typedef enum { SGG_PAD_ZERO = 0, SGG_PAD_REFLECT = 1 } sgg_pad_mode;
 
@@ -495,6 +495,28 @@ int sgg_palette_probs(const void* img, int kind, int N, int HW, int cstride, con
                       const uint8_t* classes_host, int K, int other_class, int max_dist2, int n_class, float sigma,
                       float* probs, void* stream);
 int sgg_class_boundary_band(const uint8_t* cls, uint8_t* band, int N, int H, int W, int r, void* stream);
+/* ---- paired image-quality sums (no counterpart in the reference): MAE / PSNR / SSIM of a translation against
+ * its target, both taken as 8-bit colour images.
+ *   a, b: (N,H,W,cstride) images, the first three channels used, each of its own kind exactly as sgg_palette_decode takes them:
+ *        SGG_F32 / SGG_BF16 (cstride >= 3; cstride = SGG_CPAD with a 16-byte aligned base takes one 16-byte load per pixel),
+ *        quantised q = (int)(((x + 1.f) * 0.5f) * 255.f) in f32, clamped to 0..255, NaN -> 0; or SGG_U8 (cstride = 3 | 4), the byte.
+ *   out double [N][3] on the DEVICE, written (not accumulated) per image n:
+ *     out[n][0] = sum |a - b|, out[n][1] = sum (a - b)^2 over all H*W*3 values -- counted as integers (per-block sums, 64-bit
+ *        adds, converted once): exact and independent of the grid;
+ *     out[n][2] = sum over the three channels and the (H-10)*(W-10) windows wholly inside the image of the SSIM map
+ *        S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), C1 = (0.01*255)^2, C2 = (0.03*255)^2, with the
+ *        moments ux, uy, vx = E[xx] - ux^2, vy, vxy = E[xy] - ux uy under the separable 11 x 11 window w_k ~ exp(-k^2 / (2*1.5^2)),
+ *        k = -5..5, normalised to sum 1 (scikit-image's structural_similarity with gaussian_weights=True, sigma=1.5,
+ *        use_sample_covariance=False, data_range=255 -- [3P-recall]).  Moments, S and the sums are double; the weights are formed
+ *        in double on the host; the order of every sum is fixed (no floating-point atomics): the same inputs give the same
+ *        bits, image n of a batch the bits of the call on that image alone, identical operands exactly the window count.
+ *   ws: sgg_image_quality_workspace(N, H, W) bytes (0: the shape is not supported), 8-byte aligned; need not be initialised.
+ *   Two launches, nothing allocated, no host sync: the call can be captured.
+ *   Before any launch -- SGG_EINVAL: NULL a / b / out / ws, a bad kind, cstride outside its kind's range, N <= 0, out or ws not
+ *   8-byte aligned; SGG_EUNSUPPORTED: H < 11, W < 11 or H*W > 2^22 (or more than 2^31-1 tiles); SGG_EWORKSPACE: a short ws. */
+size_t sgg_image_quality_workspace(int N, int H, int W);
+int sgg_image_quality(const void* a, int kind_a, int cstride_a, const void* b, int kind_b, int cstride_b,
+                      int N, int H, int W, double* out, void* ws, size_t ws_bytes, void* stream);
 /* f32 [P][Cs] -> dtype [P][Cd] with zero fill (Cd >= Cs), and back (drops padded channels). */
 int sgg_pad_channels(const float* src, void* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);
 int sgg_unpad_channels(const void* src, float* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);

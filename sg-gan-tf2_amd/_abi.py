@@ -130,6 +130,8 @@ SIGNATURES = {
     "sgg_palette_decode": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "sgg_palette_probs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "sgg_class_boundary_band": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "sgg_image_quality_workspace": (_sz, [_i, _i, _i]),
+    "sgg_image_quality": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "sgg_pad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "sgg_unpad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
 }

@@ -73,6 +73,41 @@ __device__ inline u32x4 ld16_nt(const void* p) { return __builtin_nontemporal_lo
 __device__ inline void st16_nt(void* p, const u32x4& v) { __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p)); }
 __device__ inline u32x4 zero16() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
 
+// ---- 8-bit colours of an image operand (evalseg.hip, imgqual.hip) ----
+// utils.inverse_transform inside [-1,1]: (int)(((x + 1) * 0.5) * 255) in f32, clamped to 0..255
+__device__ inline int quant(float x) {
+    const float v = ((x + 1.f) * 0.5f) * 255.f;
+    return v >= 255.f ? 255 : (v > 0.f ? (int)v : 0);                  // NaN fails both comparisons -> 0
+}
+__device__ inline float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ inline float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+
+// the 8-bit colour of pixel i.  KIND: SGG_F32 / SGG_BF16 (cs elements per pixel, the first three used) or SGG_U8 (cs = 3 | 4).
+// vec: cs == 8 and a 16-byte aligned base -- one 16-byte load covers the three channels of either float type.
+template <int KIND>
+__device__ inline void load_colour(const void* img, int64_t i, int cs, bool vec, int& r, int& g, int& b) {
+    if constexpr (KIND == SGG_BF16) {
+        const bf16* p = static_cast<const bf16*>(img) + (size_t)i * cs;
+        if (vec) {
+            const u32x4 c = ld16(p);
+            r = quant(bf16_lo(c[0])); g = quant(bf16_hi(c[0])); b = quant(bf16_lo(c[1]));
+        } else {
+            r = quant((float)p[0]); g = quant((float)p[1]); b = quant((float)p[2]);
+        }
+    } else if constexpr (KIND == SGG_F32) {
+        const float* p = static_cast<const float*>(img) + (size_t)i * cs;
+        if (vec) {
+            const u32x4 c = ld16(p);
+            r = quant(__uint_as_float(c[0])); g = quant(__uint_as_float(c[1])); b = quant(__uint_as_float(c[2]));
+        } else {
+            r = quant(p[0]); g = quant(p[1]); b = quant(p[2]);
+        }
+    } else {
+        const uint8_t* p = static_cast<const uint8_t*>(img) + (size_t)i * cs;
+        r = p[0]; g = p[1]; b = p[2];
+    }
+}
+
 __device__ inline float act_apply(float v, int act, float leak) {
     switch (act) {
         case SGG_ACT_RELU: return v > 0.f ? v : 0.f;

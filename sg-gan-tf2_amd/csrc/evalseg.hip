@@ -32,42 +32,9 @@ struct EvClassPalette {                             // the same entries grouped 
     float neg_inv_2s2;                              // -1 / (2 sigma^2)
 };
 
-__device__ inline int quant(float x) {
-    const float v = ((x + 1.f) * 0.5f) * 255.f;
-    return v >= 255.f ? 255 : (v > 0.f ? (int)v : 0);                  // NaN fails both comparisons -> 0
-}
-__device__ inline float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ inline float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
 __device__ inline int dist2(int r, int g, int b, uint32_t key) {
     const int dr = r - (int)(key >> 16), dg = g - (int)((key >> 8) & 0xffu), db = b - (int)(key & 0xffu);
     return dr * dr + dg * dg + db * db;
-}
-
-// the 8-bit colour of pixel i.  KIND: SGG_F32 / SGG_BF16 (cs elements per pixel, the first three used) or SGG_U8 (cs = 3 | 4).
-// vec: cs == 8 and a 16-byte aligned base -- one 16-byte load covers the three channels of either float type.
-template <int KIND>
-__device__ inline void load_colour(const void* img, int64_t i, int cs, bool vec, int& r, int& g, int& b) {
-    if constexpr (KIND == SGG_BF16) {
-        const bf16* p = static_cast<const bf16*>(img) + (size_t)i * cs;
-        if (vec) {
-            const u32x4 c = ld16(p);
-            r = quant(bf16_lo(c[0])); g = quant(bf16_hi(c[0])); b = quant(bf16_lo(c[1]));
-        } else {
-            r = quant((float)p[0]); g = quant((float)p[1]); b = quant((float)p[2]);
-        }
-    } else if constexpr (KIND == SGG_F32) {
-        const float* p = static_cast<const float*>(img) + (size_t)i * cs;
-        if (vec) {
-            const u32x4 c = ld16(p);
-            r = quant(__uint_as_float(c[0])); g = quant(__uint_as_float(c[1])); b = quant(__uint_as_float(c[2]));
-        } else {
-            r = quant(p[0]); g = quant(p[1]); b = quant(p[2]);
-        }
-    } else {
-        const uint8_t* p = static_cast<const uint8_t*>(img) + (size_t)i * cs;
-        r = p[0]; g = p[1]; b = p[2];
-    }
 }
 
 __device__ inline int classify(const EvPalette& pal, int r, int g, int b) {

@@ -1018,3 +1018,29 @@ def class_boundary_band(cls_u8, r, out=None):
     out = _out(out, (N, H, W), torch.uint8, cls_u8.device)
     A.check(A.lib().sgg_class_boundary_band(_p(cls_u8), _p(out), N, H, W, int(r), _s()), "class_boundary_band")
     return out
+
+
+# ----------------------------------------------------------------------------- paired image quality (csrc/imgqual.hip)
+def image_quality_workspace_bytes(N, H, W):
+    """Bytes of workspace sgg_image_quality needs for N pairs of H x W images; 0: the shape is not supported."""
+    return int(A.lib().sgg_image_quality_workspace(int(N), int(H), int(W)))
+
+
+def image_quality(a, b, out=None, workspace=None):
+    """sgg_image_quality: two device images (N,H,W,Cs), each f32 / bf16 (Cs >= 3, values in [-1,1]) or uint8 (Cs = 3 | 4) ->
+    (N,3) float64 device tensor {sum |a-b|, sum (a-b)^2, sum of the SSIM map} over the 8-bit colours.  Two launches, no sync.
+    ``workspace``: a uint8 device tensor of at least image_quality_workspace_bytes(N, H, W) bytes (allocated when None)."""
+    a, kind_a = _pixel_input(a)
+    b, kind_b = _pixel_input(b)
+    N, H, W, Ca = a.shape
+    assert tuple(b.shape[:3]) == (N, H, W), f"image_quality: {tuple(a.shape)} against {tuple(b.shape)}"
+    need = image_quality_workspace_bytes(N, H, W)
+    if need == 0:
+        A.check(A.EUNSUPPORTED, f"image_quality {N}x{H}x{W}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=a.device)
+    assert workspace.dtype == torch.uint8
+    out = _out(out, (N, 3), torch.float64, a.device)
+    A.check(A.lib().sgg_image_quality(_p(a), kind_a, Ca, _p(b), kind_b, b.shape[3], N, H, W, _p(out), _p(workspace), workspace.numel(),
+                                      _s()), "image_quality")
+    return out

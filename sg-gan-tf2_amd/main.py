@@ -96,6 +96,11 @@ def build_parser():
     a("--class_max_dist", dest="class_max_dist", type=int, default=argparse.SUPPRESS,
       help="--class_scores: a pixel whose 8-bit colour is farther than this (Euclidean, RGB) from every palette colour counts as "
            "class 0 (default -1: always the nearest colour)")
+    a("--image_scores", dest="image_scores", action="store_true", default=argparse.SUPPRESS,
+      help="test pass: compare every translation, as the 8-bit image it is saved as, with the 8-bit label image: 'Image MAE', "
+           "'Image PSNR' and 'Image SSIM' scalars (SSIM: 11x11 Gaussian window, sigma 1.5, the mean over the windows inside the "
+           "image; computed in double on the GPU); with --cycle also 'Cycle MAE / PSNR / SSIM' of the reconstruction "
+           "G_BA(G_AB(x)) against the input; images must be at least 11 pixels high and wide")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 

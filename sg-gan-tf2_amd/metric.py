@@ -13,6 +13,12 @@ it.  ``scores_mask_fake_crf`` (a cubic-spline zoom across the class axis) is sup
 Class-level scores (not in the reference): ``palette_labels`` / ``palette_probs`` decode a generated colour map
 to classes through a palette learned from the dataset (csrc/evalseg.hip), ``scores_class_fake`` counts it against the class
 map in the same launch (optionally on a boundary band), ``scores_class_fake_crf`` refines it with ``dense_crf`` first.
+
+Paired image quality (not in the reference): ``image_quality`` gives the mean absolute error, MSE, PSNR and SSIM
+(Wang et al.; 11 x 11 Gaussian window, sigma 1.5, data range 255, the mean over the windows inside the image) of two images
+taken as 8-bit colours -- the bytes ``save_images`` writes -- from integer sums and a double-precision SSIM map summed in a
+fixed order on the GPU (csrc/imgqual.hip).  ``scores_image_fake`` keeps the per-image sums of a test pass on the device,
+``scores_from_quality`` reads them back once and pools them.
 """
 from __future__ import annotations
 
@@ -232,3 +238,55 @@ def scores_class_fake_crf(class_map, rescaled_sample, fake_img, n_class, palette
         labels = torch.argmax(dense_crf(photo[n], probs[n]), dim=0)
         _accumulate_hist(hist.view(-1), truth[n], labels, n_class)
     return hist
+
+
+# ----------------------------------------------------------------------------- paired image quality (csrc/imgqual.hip)
+def _quality_counts(H, W):
+    """(values the two integer sums run over, values of the SSIM map) per image."""
+    return 3 * H * W, 3 * (H - 10) * (W - 10)
+
+
+def _per_image_quality(rows, n_all, n_valid):
+    """The derived scores of (N,3) sums; n_all / n_valid: scalars or per-row arrays."""
+    mse = rows[:, 1] / n_all
+    psnr = np.full(len(rows), np.inf)
+    psnr[mse > 0] = 10.0 * np.log10(255.0 ** 2 / mse[mse > 0])
+    return {"MAE": rows[:, 0] / n_all, "MSE": mse, "PSNR": psnr, "SSIM": rows[:, 2] / n_valid}
+
+
+def image_quality(a, b):
+    """Per-image arrays {"MAE", "MSE", "PSNR", "SSIM"} (float64, NumPy) of two images (N,H,W,C) or (H,W,C), NumPy or torch:
+    uint8 with C = 3 | 4, float in [-1,1] (quantised as utils.inverse_transform does), or what the generators return (the
+    internal channel-padded activations, a lazy output).  MAE = sum |a-b| / (3HW), MSE = sum (a-b)^2 / (3HW), PSNR =
+    10 log10(255^2 / MSE) (inf where MSE is 0), SSIM = the mean of the SSIM map over the (H-10)(W-10) windows inside the image
+    and the three channels.  H, W >= 11."""
+    ta, tb = _image_tensor(a), _image_tensor(b)
+    rows = K.image_quality(ta, tb).cpu().numpy()
+    return _per_image_quality(rows, *_quality_counts(ta.shape[1], ta.shape[2]))
+
+
+def scores_image_fake(target_u8, fake_img, acc=None):
+    """Appends the raw (N,3) device rows {sum |a-b|, sum (a-b)^2, SSIM sum} of ``fake_img`` against ``target_u8`` and their
+    value counts to ``acc`` (a list; a new one when None) and returns it: nothing is read back, so a test pass collects every
+    sample and hands the list to ``scores_from_quality`` once at its end."""
+    acc = [] if acc is None else acc
+    target, fake = _image_tensor(target_u8), _image_tensor(fake_img)
+    acc.append((K.image_quality(target, fake), _quality_counts(target.shape[1], target.shape[2])))
+    return acc
+
+
+def scores_from_quality(acc):
+    """{"MAE", "PSNR", "SSIM", "per_image": {"MAE", "MSE", "PSNR", "SSIM"}} of the rows ``scores_image_fake`` collected (ONE
+    read-back).  MAE is pooled over all values; PSNR comes from the pooled MSE -- where that is 0, the finite bound
+    10 log10(255^2 * count), the PSNR of a single unit error among ``count`` values, so that a JSON sink never holds inf;
+    SSIM is the mean of the per-image SSIMs."""
+    if not acc:
+        raise ValueError("scores_from_quality: no image pair was scored")
+    rows = torch.cat([r for r, _ in acc]).cpu().numpy()
+    n_all = np.concatenate([np.full(len(r), c[0], dtype=np.float64) for r, c in acc])
+    n_valid = np.concatenate([np.full(len(r), c[1], dtype=np.float64) for r, c in acc])
+    per = _per_image_quality(rows, n_all, n_valid)
+    count = float(n_all.sum())
+    pooled_mse = float(rows[:, 1].sum()) / count
+    psnr = 10.0 * np.log10(255.0 ** 2 / pooled_mse) if pooled_mse > 0 else 10.0 * np.log10(255.0 ** 2 * count)
+    return {"MAE": float(rows[:, 0].sum()) / count, "PSNR": float(psnr), "SSIM": float(np.mean(per["SSIM"])), "per_image": per}

@@ -794,6 +794,11 @@ class sggan(object):
         pixels within that distance of a ground-truth class boundary), and with ``args.crf`` as well the four 'Class CRF ...'
         scores of the CRF-refined map (metric.scores_class_fake_crf); the returned scores gain "Class", "Class Boundary" and
         "Class CRF".
+        With ``args.image_scores`` every translation is also compared, as the 8-bit image ``save_images`` writes,
+        with the 8-bit label image ``convert_image_dtype_uint8(seg_image)`` (metric.scores_image_fake: the sums stay on the
+        device and are read back once); 'Image MAE', 'Image PSNR' and 'Image SSIM' follow the scalars above and the returned
+        scores gain "Image".  A cycle model also scores the reconstruction ``generator_BA(fake_A)`` against the 8-bit input,
+        under the same weights as the translation: 'Cycle MAE', 'Cycle PSNR', 'Cycle SSIM' and "Cycle".
         A model built with ``ema_decay`` translates with the moving average of the generator's weights
         (ema_weights) and logs 'EMA Decay', the decay its last applied update used, after all the scalars above."""
         from . import metric as M
@@ -810,6 +815,8 @@ class sggan(object):
             decode = dict(max_dist2=far * far if far >= 0 else -1)
             class_hist = {k: torch.zeros((n_class, n_class), dtype=torch.int64, device=self.device)
                           for k, on in (("Class", True), ("Class Boundary", band_px > 0), ("Class CRF", crf)) if on}
+        image_scores = bool(getattr(args, "image_scores", False))
+        image_acc, cycle_acc = [], []
         test_dir = getattr(args, "test_dir", None)
         with self._test_weights():                  # (the moving average, where the model keeps one)
             for item in samples:
@@ -821,6 +828,10 @@ class sggan(object):
                     save_images(fake_A, [1, 1], os.path.join(test_dir, os.path.basename(name)))      # :362-365
                 fake_img = get_img(fake_A, [1, 1])                                                   # :369
                 outputs.append(fake_img)
+                if image_scores:
+                    M.scores_image_fake(convert_image_dtype_uint8(np.asarray(seg_image)[None]).astype(np.uint8), fake_A, image_acc)
+                    if self.cycle:
+                        M.scores_image_fake(rescaled.astype(np.uint8), self.generator_BA(fake_A), cycle_acc)
                 lt, lp = M.scores_seg_fake(np.asarray(seg_image, dtype=np.float32)[None], torch.as_tensor(fake_img.astype(np.float32)))   # :373
                 preds += list(lp); gts += list(lt)
                 if crf:
@@ -861,6 +872,13 @@ class sggan(object):
                     sink.scalar("Boundary Class Mean IoU", score["Class Boundary"]["Mean IoU"], epoch)
                 if "Class CRF" in score:
                     self._class_scalars(sink, "Class CRF ", score["Class CRF"], epoch)
+        for key, acc in (("Image", image_acc), ("Cycle", cycle_acc)):
+            if acc:
+                score[key] = q = M.scores_from_quality(acc)
+                if sink is not None:
+                    sink.scalar(key + " MAE", q["MAE"], epoch)
+                    sink.scalar(key + " PSNR", q["PSNR"], epoch)
+                    sink.scalar(key + " SSIM", q["SSIM"], epoch)
         if self.ema_decay is not None and sink is not None:     # the decay the generator's last applied update used
             sink.scalar("EMA Decay", float(self.generator.P._ema_state[0].item()), epoch)
         return (np.concatenate(outputs, axis=0) if outputs else None), score
@@ -876,12 +894,13 @@ class sggan(object):
         """model.py:535-567 (--phase test): load the latest checkpoint, translate every test sample and save the input and the
         translation under ``args.test_dir``.  ``samples`` yields (name, sample_image (H,W,3) in [0,1]).  With
         ``args.class_scores`` and samples that carry the one-hot class mask as their fourth element, the four class-level scores
-        of the translations are logged at the end.  A model built with ``ema_decay`` translates with the moving
+        of the translations are logged at the end; with ``args.image_scores`` and samples that carry their label
+        image as the third element, 'Image MAE / PSNR / SSIM' of the translations against it.  A model built with ``ema_decay`` translates with the moving
         average of the generator's weights, as the checkpoint holds it."""
         from . import metric as M
         from .utils import convert_image_dtype_uint8, save_images
         import os
-        class_hist = None
+        class_hist, image_acc = None, []
         log(" [*] Running Test ...")
         log(" [*] Load SUCCESS" if self.load(args.checkpoint_dir) else " [!] Load failed...")
         os.makedirs(args.test_dir, exist_ok=True)
@@ -895,6 +914,8 @@ class sggan(object):
                 save_images(sample_image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(name)))
                 save_images(fake_A, [1, 1], os.path.join(args.test_dir, os.path.basename(name)))
                 out.append(fake_A)
+                if getattr(args, "image_scores", False) and len(item) >= 3:
+                    M.scores_image_fake(convert_image_dtype_uint8(np.asarray(item[2])[None]).astype(np.uint8), fake_A, image_acc)
                 if getattr(args, "class_scores", False) and len(item) >= 4:
                     truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
                     far = int(getattr(args, "class_max_dist", -1))
@@ -904,6 +925,9 @@ class sggan(object):
             s = M.scores_from_hist(class_hist)
             log("Class Overall Accuracy: %f Class Mean Accuracy: %f Class Frequency Weighted Accuracy: %f Class Mean IoU: %f"
                 % (s["Overall Acc"], s["Mean Acc"], s["FreqW Acc"], s["Mean IoU"]))
+        if image_acc:
+            q = M.scores_from_quality(image_acc)
+            log("Image MAE: %f Image PSNR: %f Image SSIM: %f" % (q["MAE"], q["PSNR"], q["SSIM"]))
         return out
 
     def train(self, args, batches, log=print, test_samples=None, sink=None):
