@@ -792,63 +792,24 @@ __global__ __launch_bounds__(NW * 64) void conv_gemm_glds_kernel(ConvArgs a_in) 
 #ifndef H3_HALO_HALF
 #define H3_HALO_HALF 1                                 // ... and which half the halo-row DMAs (the other half measured 3-6 % slower:
 #endif                                                 //     the non-issuers' early MFMAs are what covers the issuers' DMA phase)
-#ifndef H3_ROT
-#define H3_ROT 1                                       // halo rows: 16-byte chunk c of row r sits at position (c + (r & 6)) & 7 (a rotation) instead of c ^ ((r >> 1) & 7)
-#endif
-#ifndef SGG_NT_ADDEND
-#define SGG_NT_ADDEND 0         // 1: the 3x3 halo data gradient reads its skip-gradient addend (its last use) with the streaming cache policy
-#endif
-#ifndef H3_EARLY_FRAGS
-#define H3_EARLY_FRAGS 0 // 1: issuer waves put their first fragment reads of the tile in flight BEFORE the tile's DMA issue (main loop).  OFF: data gradient 3 % slower, forward equal (profiles/r04_persistent_halo_gemm.txt item 8)
-#endif
-#ifndef H3_LATE_HALO
-#define H3_LATE_HALO 0   // 1: halo-row DMAs by the non-issuer waves after their MFMAs, waited for one tile later (main loop).  OFF: 2-3.5 % slower (profiles/r04_persistent_halo_gemm.txt item 7)
-#endif
-#ifndef H3_NT
-#define H3_NT 0          // streaming (nt) LDS-DMA of the halo rows: 1 forward (x), 2 data gradient (dy)
-#endif
-#ifndef H3_STAGGER
-#define H3_STAGGER 0                                   // 1: waves of one half run half a tile behind their SIMD partners (main loop header).  OFF: forward +1 % at best, data gradient spills (profiles/r04_persistent_halo_gemm.txt)
-#endif
-#ifndef H3_LAG_HALF
-#define H3_LAG_HALF 1                                  // which half lags (1: waves 4-7)
-#endif
-#ifndef H3_PERSIST
-#define H3_PERSIST 0                                   // 1: one block per CU walking consecutive tiles, the next tile's prologue issued under the epilogue (kernel header).  OFF: measured flat forward, slower data gradient (profiles/r04_persistent_halo_gemm.txt)
-#endif
-#ifndef H3_PRIME_FIRST
-#define H3_PRIME_FIRST 1                               // persistent form: the next tile's prologue DMAs go out at the HEAD of the epilogue (in front of the addend loads: fewer live registers)
-#endif
-#ifndef H3_PRIMED_WAIT
-#define H3_PRIMED_WAIT 0                               // > 0: at a primed tile's head wait until <= this many vector-memory operations are outstanding (the epilogue's stores) instead of for all
-#endif
-#ifndef H3_PATCH_ROT
-#define H3_PATCH_ROT 0                                 // 1: FOLD column patches laid out so that a patch lane reads the bank slot its halo read would have taken (below): SQ_LDS_BANK_CONFLICT 13 % -> 0, kernel time +0.7-1.5 % -- off
-#endif
-#ifndef H3_WIDE
-#define H3_WIDE 1                                      // epilogue: two pixel fragments' 8-byte (pixel, 4 channels) pieces exchanged between lane rows into 16-byte stores / addend loads
-#endif
 #ifndef H3_GJ
 #define H3_GJ 4                                        // pixel fragments per MFMA group of the main loop (x 4 weight fragments = 16 MFMAs)
 #endif
 #ifndef H3_NORM_AT
 #define H3_NORM_AT 1                                   // NORM: after which MFMA group of the step (0..3) the row transform runs
 #endif
-// DMA addressing of the halo kernel per source-padding mode (SRC 0 / 1 / 2): 0 = a 64-bit address per lane and piece,
-// 1 = uniform base in an SGPR pair + 32-bit lane offset, 2 = buffer descriptor (out-of-range lanes read zeros).  All three give
-// the same bits (tests/test_gpu_exact.py passes with each); the defaults are what measured fastest in the step.
-#ifndef H3_ADDR0
-#define H3_ADDR0 0
-#endif
-#ifndef H3_ADDR1
-#define H3_ADDR1 0
-#endif
-#ifndef H3_ADDR2
-#define H3_ADDR2 1
-#endif
-#ifndef H3_NORM_ABL
-#define H3_NORM_ABL 0                                  // timing experiments only (wrong results): 1 no store of the normalised rows, 2 no in-loop transform, 4 no prologue transform
-#endif
+// Forms of this kernel that were built, measured bit-identical and slower (or no faster), and then REMOVED from the source --
+// the numbers stay under profiles/:
+//   persistent blocks walking consecutive tiles, next prologue under the epilogue: forward flat, data gradient spills and is
+//       15 % slower; one half of the waves lagging half a tile: forward -1 % at best, data gradient 2x slower; halo rows
+//       issued late by the non-issuer waves: 2-3.5 % slower; issuers' fragment reads ahead of their DMA issue: data gradient
+//       3 % slower; column patches laid out like the halo rows: no bank conflicts, 0.7-1.5 % slower
+//       (profiles/r04_persistent_halo_gemm.txt items 1-5, 7, 8, 3; raw lines in profiles/r04_raw_ab_*.txt)
+//   8-byte epilogue stores instead of 16-byte ones: 5-9 % slower (profiles/r04_ab_wide_stores_patch_rotation.txt)
+//   XOR-keyed halo rows instead of rotated ones: 31-34 % LDS conflict replays (profiles/r03_ab_rotation_swizzle.txt)
+//   streaming (nt) halo DMAs / addend loads: the step does not move (profiles/r04_nt_loads.txt)
+//   SGPR-base and buffer-descriptor DMA addressing for every source: slower than per-lane addresses
+//       (profiles/r03_ab_dma_addressing.txt; see the DMA addressing note in the kernel)
 #define H3_PITCH 136                                   // halo row pitch in pixels (130 used; multiple of 8 = one DMA)
 #define H3_HALO_BYTES (4 * H3_PITCH * 128)
 #define H3_PATCH_ROWS 40                               // 2 tile rows x 2 sides x 9 taps = 36, rounded to whole DMAs
@@ -904,10 +865,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
         const int q = nm >> 3, rr = nm & 7, xcd = b & 7;
         lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (b >> 3);
     }
-    // PERSISTENT form (H3_PERSIST): the grid is one block per CU and a block walks `tpb` CONSECUTIVE tiles (rows of one image:
-    // neighbouring halos, one weight set); the next tile's prologue -- four halo rows, patch, weight tile 0: ~100 KB per block --
-    // is issued under the current tile's epilogue (between its addend loads and its stores), so only the first tile of a block
-    // pays for an exposed prologue and there is no second wave of block launches.  Same tiles, same arithmetic per tile.
     struct Tile { int n0, img, h0, w0, tw, th; const char* wmat_n; bool hasL, hasR; };
     auto tile_of = [&](int id) {
         Tile c;
@@ -921,15 +878,10 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
         c.hasL = FOLD && c.tw == 0; c.hasR = FOLD && c.tw == tilesW - 1;
         return c;
     };
-    constexpr int ADDR = SRC == 0 ? H3_ADDR0 : (SRC == 1 ? H3_ADDR1 : H3_ADDR2);
-    constexpr bool PERSIST = H3_PERSIST && SRC != 2 && ADDR == 0 && STATS != 2;
-    const int total_tiles = tilesN * tilesW * tilesH * a.N;
-    const int tpb = PERSIST ? (total_tiles + (int)gridDim.x - 1) / (int)gridDim.x : 1;
-    bool primed = false;                               // this tile's prologue DMAs were issued under the previous tile's epilogue
+    const int tpb = 1;
+    bool primed = false;
   for (int it = 0; it < tpb; ++it) {
-    const int tile_id = PERSIST ? lid * tpb + it : lid;
-    if (PERSIST && tile_id >= total_tiles) break;
-    const Tile cur = tile_of(tile_id);
+    const Tile cur = tile_of(lid);
     const int n0 = cur.n0, tw = cur.tw, th = cur.th, img = cur.img, h0 = cur.h0, w0 = cur.w0;
     const char* const wmat_n = cur.wmat_n;
     const bool dbg_clk = SGG_ABLATE_OF(a) == 9 && lid == 0 && tid == 0;
@@ -941,29 +893,14 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
     // ---- halo DMA: one wave-instruction = 8 halo pixels x 128 B; a halo row is 17 of them (wave, wave+8, wave+16)
     const int hpos = lane & 7, hsub = lane >> 3;
     constexpr bool mirror = SRC != 0;                                      // (the data gradient always zero-pads dy)
-    // DMA addressing (ADDR), three forms measured against each other in the step (profiles/r03_ab_dma_addressing.txt):
-    // 0 -- a 64-bit address per lane and piece; zero-padded sources select against the zero page.  ~12 instructions per piece on
-    //      the issuer waves, and hipcc keeps every piece's lane mask (an SGPR pair) and base (a VGPR pair) live across the main
-    //      loop: ~90 SGPRs parked in VGPR lanes in the data gradient, ~50 v_readlane per step to get them back.
-    // 1 -- a uniform base in an SGPR pair + a 32-bit lane offset (REFLECT sources / weight tiles): ~16 VGPRs fewer.
-    // 2 -- buffer descriptors: base and size in four SGPRs per operand, the scalar part of a piece's address in the
-    //      instruction's soffset, the lane part one loop-invariant VGPR per piece position, lanes outside the buffer read ZEROS:
-    //      no zero page, no masks, no vector instruction per piece (issue part of a step: 201 -> 29 VALU, no v_readlane).
-    // Form 0 is the FASTEST: paired forward 0.495 of peak against 0.484 (form 1) and 0.473 -> 0.454 (form 2, another box);
-    // paired data gradient 0.451 against 0.415 (form 1 for the weight tiles) and 0.434 -> 0.422 (form 2).  An LDS-DMA piece
-    // costs the issuing wave 60-180 cycles whatever surrounds it (the CU's vector-memory path into LDS), so the address
-    // arithmetic of form 0 runs in time the wave would wait anyway, and the denser issue of forms 1 / 2 only bunches the LDS
-    // writes against the other waves' fragment reads.  Only the normalise-on-load variant uses form 1: it needs the registers.
-    // (What did pay is the padding mode as a template parameter: 0.472 -> 0.495.)
-    static_assert(ADDR != 1 || SRC != 0, "the SGPR-base form has no zero padding");
-    constexpr bool SADDR = ADDR == 1, BUFA = ADDR == 2;
+    // DMA addressing: a 64-bit address per lane and piece, zero-padded sources selecting against the zero page.  It costs ~12
+    // instructions per piece and parks lane masks in VGPR lanes, and still measured FASTEST in the step: an LDS-DMA piece costs
+    // the issuing wave 60-180 cycles whatever surrounds it, so the arithmetic runs in time the wave would wait anyway, and the
+    // denser issue of the cheaper forms (uniform SGPR base + 32-bit lane offset; buffer descriptors) only bunches the LDS
+    // writes against the other waves' fragment reads (profiles/r03_ab_dma_addressing.txt).  Only the normalise-on-load variant
+    // takes the SGPR-base form (SADDR): it needs the ~16 registers.  (What did pay is the padding mode as a template parameter.)
+    constexpr bool SADDR = SRC == 2;
     const char* vrows = FOLD ? a.fold + (size_t)a.N * a.H * 18 * SC * 2 : nullptr;   // [N][2][W][SC] after the patches
-    const uint32_t rowbytes = (uint32_t)(a.W * SC * 2);
-    sgg_rsrc_t rsS, rsV, rsW;                              // this image of the source, its two virtual rows (FOLD), this tile's weight rows
-    if constexpr (BUFA) {
-        rsS = sgg_make_rsrc(a.src + (size_t)img * a.H * rowbytes, (uint32_t)a.H * rowbytes);
-        rsV = sgg_make_rsrc(FOLD ? vrows + (size_t)img * 2 * rowbytes : a.src, FOLD ? 2 * rowbytes : 0u);
-    }
     // (Walking the channel chunks in a per-block rotated order -- so that the blocks of one XCD do not all want the
     // same weight tile at the same moment -- measured 1-2 % slower: first-touch L2 misses are not what the tiles wait for.)
     // (vw, nw): this wave acts as issuer vw of nw -- all 8 waves in the prologue, 4 issuer waves in the main loop
@@ -978,22 +915,13 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
         if (mirror) hi = hi < 0 ? -hi : (hi >= a.H ? 2 * (a.H - 1) - hi : hi);
         else rowok = (unsigned)hi < (unsigned)a.H;
         const char* rowp = a.src + ((size_t)img * a.H + (rowok ? hi : 0)) * a.W * SC * 2 + chunk * 128;
-        // BUFA: the row's descriptor and scalar offset -- the image, one of the two virtual rows (FOLD), or an EMPTY buffer for a
-        // row above / below the image (every lane out of range: zeros) -- so that each piece is the same single instruction
-        sgg_rsrc_t rs = rsS;
-        uint32_t soff = (uint32_t)(rowok ? hi : 0) * rowbytes + chunk * 128;
         if (FOLD) {
-            if (h0 == 0 && k == 3) { rowp = vrows + ((size_t)img * 2 + 0) * a.W * SC * 2 + chunk * 128; rs = rsV; soff = chunk * 128; }
-            if (h0 == a.H - 2 && k == 0) { rowp = vrows + ((size_t)img * 2 + 1) * a.W * SC * 2 + chunk * 128; rs = rsV; soff = rowbytes + chunk * 128; }
+            if (h0 == 0 && k == 3) rowp = vrows + ((size_t)img * 2 + 0) * a.W * SC * 2 + chunk * 128;
+            if (h0 == a.H - 2 && k == 0) rowp = vrows + ((size_t)img * 2 + 1) * a.W * SC * 2 + chunk * 128;
         }
-        if (!rowok) rs[2] = 0;
-        // (the issuer index once more through an opaque asm, for the SCALAR parts of a piece -- LDS destination, soffset: as
-        // loop invariants hipcc parks them in VGPR lanes, 90 spilled SGPRs and ~50 v_readlane per step in the data gradient)
-        int vws = vw;
-        if (BUFA) asm volatile("" : "+s"(vws));
 #pragma unroll
         for (int qi = 0; qi < 5; ++qi) {
-            const int q = vw + nw * qi, qs = vws + nw * qi;
+            const int q = vw + nw * qi;
             if (q >= 17) break;
             const int hp = q * 8 + hsub;                                   // halo column 0..135
             int wi = w0 - 1 + hp;
@@ -1006,22 +934,17 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
             // (fragment base = halo column + 0 / 1 / 2).  With the XOR key (r >> 1) & 7 those eight positions are distinct only
             // for even m0 -- the 31-34 % conflict replays of round 2 (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE) on two tap columns
             // of three.  Rotating instead, position = (c + 2 * (r >> 1)) & 7, gives 2 m0 + {0,2,4,6} and 2 m0 + 1 + {4,6,0,2}:
-            // all evens and all odds, distinct for EVERY m0.  The DMA writes LDS linearly, so the rotation goes on the source
-            // address: position hpos of row r holds chunk (hpos - (r & 6)) & 7.
+            // all evens and all odds, distinct for EVERY m0 (profiles/r03_ab_rotation_swizzle.txt).  The DMA writes LDS linearly,
+            // so the rotation goes on the source address: position hpos of row r holds chunk (hpos - (r & 6)) & 7.
             const int hrow_ = k * H3_PITCH + hp;
-            const int schunk = H3_ROT ? ((hpos - (hrow_ & 6)) & 7) : (hpos ^ ((hrow_ >> 1) & 7));
-            __attribute__((address_space(3))) void* const ldst = (__attribute__((address_space(3))) void*)(lH + (k * H3_PITCH + qs * 8) * 128);
-            if (BUFA) {
-                // lane part: a loop invariant per piece position (H3_PITCH is a multiple of 8: the rotation does not depend on k);
-                // REFLECT: every halo pixel is an image pixel (the six filler columns read mirrored pixels nobody uses)
-                const bool colok = mirror || (hp < H3_TW + 2 && (unsigned)wi < (unsigned)a.W);
-                const uint32_t voff = colok ? (uint32_t)(wi * SC * 2 + (schunk << 4)) : SGG_BUF_OOB;
-                dma16_buf_to_lds(voff, rs, soff, ldst);
-            } else if (SADDR) {
+            const int schunk = (hpos - (hrow_ & 6)) & 7;
+            __attribute__((address_space(3))) void* const ldst = (__attribute__((address_space(3))) void*)(lH + (k * H3_PITCH + q * 8) * 128);
+            if (SADDR) {
+                // (REFLECT: every halo pixel is an image pixel -- the six filler columns read mirrored pixels nobody uses)
                 dma16_to_lds_s(rowp, (uint32_t)(wi * SC * 2 + (schunk << 4)), ldst);
             } else {
                 const char* src = ok ? rowp + (size_t)wi * SC * 2 + (schunk << 4) : zero;
-                if (H3_NT & (MODE == MODE_FWD ? 1 : 2)) dma16_to_lds_nt(src, ldst); else dma16_to_lds(src, ldst);
+                dma16_to_lds(src, ldst);
             }
         }
     };
@@ -1038,24 +961,10 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
             const int pw = vw + nw * qi;                                   // patch DMA 0..4
             if (pw >= H3_PATCH_ROWS / 8) break;
             const int pe = pw * 8 + hsub;
-            int tap_h, side, tr, schunk;
-            if (H3_PATCH_ROT && H3_ROT) {
-                // Patch row of (tile row tr, tap row r): 6 LDS rows, even ones for the entries whose halo read sits in an even halo
-                // row -- (L, sx 1), (R, sx 0), (R, sx 2) -- odd ones for (L, sx 0), (L, sx 2), (R, sx 1); chunk c at position
-                // (c + rot) & 7 with rot = the halo rotation of the row the lane would have read: L (1 + sx) & 6, R (14 + sx) & 6.
-                // The patch lane of a fragment read then hits exactly the bank slot (row parity, position) of the halo read it
-                // replaces, and the ds_read_b128 stays conflict-free (with the XOR-keyed patch rows 13 % of the data gradient's LDS
-                // cycles were conflict replays: at W = 128 every tile is both a left and a right edge).
-                const int grp = pe / 6, slot = pe - 6 * grp;
-                side = (0x34 >> slot) & 1;
-                const int sx = (0x681 >> (2 * slot)) & 3;
-                tr = grp / 3;
-                tap_h = (grp - 3 * tr) * 3 + sx;
-                schunk = (hpos - ((0x6c90 >> (3 * (side * 3 + sx))) & 7)) & 7;
-            } else {
-                tap_h = pe % 9; side = (pe / 9) & 1; tr = pe / 18;
-                schunk = hpos ^ ((pe >> 1) & 7);
-            }
+            // (XOR-keyed rows: 13 % of the data gradient's LDS cycles are conflict replays where a patch lane replaces a halo lane;
+            // rows laid out like the halo's removed them and measured 0.7-1.5 % slower, profiles/r04_persistent_halo_gemm.txt item 3)
+            const int tap_h = pe % 9, side = (pe / 9) & 1, tr = pe / 18;
+            const int schunk = hpos ^ ((pe >> 1) & 7);
             const bool ok = pe < 36 && (side ? hasR : hasL);
             // a.fold first part: [N][H][2 sides][9 weight taps][SC]; halo tap t pairs with weight tap 8 - t
             const char* src = ok ? a.fold + (((((size_t)img * a.H + h0 + tr) * 2 + side) * 9 + (8 - tap_h)) * SC + chunk * 64) * 2 + (schunk << 4)
@@ -1071,7 +980,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
     const int wl = lane >> 3;
     const int wsw = ((lane & 7) ^ ((lane >> 4) & 7)) << 4;
     const uint32_t wvoff0 = (uint32_t)(wl * wrow * 2 + wsw), wvoff1 = (uint32_t)(wl * wrow * 2 + (wsw ^ 64));
-    if constexpr (BUFA) rsW = sgg_make_rsrc(wmat_n + (size_t)n0 * wrow * 2, (uint32_t)((DC - n0 < BN ? DC - n0 : BN) * wrow * 2));
     auto load_w = [&](const Tile& c, int stg, int chunk, int tap, int vw, int nw, int ln) {
         const int wl = ln >> 3;
         const int wsw = ((ln & 7) ^ ((ln >> 4) & 7)) << 4;
@@ -1081,20 +989,12 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
         const char* const tbase = wmat_n + ((size_t)n0 * wrow + tap * SC + chunk * 64) * 2;
         const uint32_t wvoff = (vw & 1) ? wvoff1 : wvoff0;
         lds_char* sQ = lB + stg * (256 * 128);
-        int vws = vw;
-        if (BUFA) asm volatile("" : "+s"(vws));          // (see load_halo_row)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int d = vw + nw * j, ds = vws + nw * j;
+            const int d = vw + nw * j;
             if (d >= 32) break;
-            __attribute__((address_space(3))) void* const ldst = (__attribute__((address_space(3))) void*)(sQ + ds * 8 * 128);
-            if (BUFA) {
-                // rows past DC: the descriptor ends at the matrix (or at the tile), and so that the outcome does not hang on how
-                // the range check treats soffset, such a group is asked for with an out-of-range LANE offset
-                const uint32_t so = (uint32_t)(ds * 8 * wrow * 2 + (tap * SC + chunk * 64) * 2);
-                if (n0 + ds * 8 < DC) dma16_buf_to_lds(wvoff, rsW, so, ldst);
-                else dma16_buf_to_lds(SGG_BUF_OOB, rsW, 0u, ldst);
-            } else if (!SADDR) {
+            __attribute__((address_space(3))) void* const ldst = (__attribute__((address_space(3))) void*)(sQ + d * 8 * 128);
+            if (!SADDR) {
                 const bool ok = n0 + d * 8 + wl < DC;
                 const char* src = ok ? wmat_n + (size_t)(n0 + wl) * wrow * 2 + d * ((size_t)8 * wrow * 2) + (tap * SC + chunk * 64) * 2 + (wsw ^ ((d & 1) << 6)) : zero;
                 dma16_to_lds(src, ldst);
@@ -1126,7 +1026,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
             char* const orow = a.nout + ((((size_t)img * a.H + h0 + k - 1) * a.W + w0) * SC + chunk * 64 + c8 * 8) * 2;
             auto piece_ptr = [&](int q) -> char* {
                 const int hrow_ = k * H3_PITCH + q * 8 + hsub;
-                const int pos = H3_ROT ? ((c8 + (hrow_ & 6)) & 7) : (c8 ^ ((hrow_ >> 1) & 7));
+                const int pos = (c8 + (hrow_ & 6)) & 7;
                 return sH + hrow_ * 128 + (pos << 4);
             };
             // up to five pieces per lane and row (17 pixel groups over 4 waves), in batches of <= 3 with the batch's reads issued
@@ -1150,7 +1050,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                     for (int e = 0; e < 8; ++e) { const float t = xv[e] * A[e] + B[e]; o[e] = t > 0.f ? t : 0.f; }
                     const u32x4 pk = ET<bf16>::pack(o);
                     st16(piece_ptr(q), pk);
-                    if (!(H3_NORM_ABL & 1) && own_row && hp >= 1 && hp <= H3_TW) st16(orow + (size_t)(hp - 1) * SC * 2, pk);
+                    if (own_row && hp >= 1 && hp <= H3_TW) st16(orow + (size_t)(hp - 1) * SC * 2, pk);
                 }
             }
         }
@@ -1178,17 +1078,14 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
     // prologue: whole halo of chunk 0 + weight tile 0
     if (!primed) {
         int lop = lane;
-        if (PERSIST) asm volatile("" : "+v"(lop));
 #pragma unroll
         for (int k = 0; k < 4; ++k) load_halo_row(cur, k, 0, wave, 8, lop);
         load_patch(cur, 0, wave, 8, lop);
         load_w(cur, 0, 0, MODE == MODE_FWD ? 0 : 8, wave, 8, lop);
     }
-    // (primed: the DMAs are older than the previous tile's stores, and vector-memory operations complete in issue order --
-    // waiting until at most the stores issued after them are outstanding leaves those in flight under this tile's first steps)
-    if (PERSIST && primed && H3_PRIMED_WAIT > 0) sgg_wait_vm<H3_PRIMED_WAIT>(); else SGG_WAIT_VM0();
+    SGG_WAIT_VM0();
     __builtin_amdgcn_s_barrier();
-    if constexpr (NORM && !(H3_NORM_ABL & 4)) {
+    if constexpr (NORM) {
         // the tile's own rows (1, 2: stored to a.nout) by the waves that issue no DMAs in the main loop, the neighbours' rows by
         // the DMA issuers: those wait for vmcnt(0) at the end of every step and would sit out the stores' round trip to memory
         // there (with the rows dealt to all eight waves the prologue cost 4.7 us per tile)
@@ -1206,21 +1103,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
 #else
 #define H3_STAMP(pt) do {} while (0)
 #endif
-    // STAGGER (H3_STAGGER): one half of the waves -- one wave of every SIMD pair -- runs half a tile behind the other.  Both halves
-    // run the same tiles between the same barriers and read a tile's fragments from LDS inside the tile (so every LDS hazard is the
-    // one-barrier-per-tile scheme's), but the lagging half multiplies k-step 1 of a tile AFTER the tile's barrier, from registers:
-    // when the barrier opens it has 32 MFMAs ready while its partner waits for LDS, and near the end of the tile its k-step 0
-    // finishes early and the partner has the pipe.  Same MFMAs into the same accumulators in the same order: bit-identical.
-    // Two copies of the loop (the carried fragments must not count against the other half's registers).
-    constexpr bool STAG = H3_STAGGER && !NORM && STATS != 2;     // (the STATS == 2 build of the staggered form aborted on the GPU: fenced off, not debugged)
-    auto main_loop = [&](auto lag_c) {
-        constexpr bool LAG = decltype(lag_c)::value;
-        u32x4 cw[NI], cp[MI];                            // LAG: k-step 1's weight / pixel fragments of the tile before
-        // LATE_HALO: the halo rows (and patches) are issued by the waves that issue no weight DMAs, AFTER their MFMAs -- in the ~1 200
-        // cycles they otherwise wait at the barrier for their SIMD partners, whose serial path (weight DMAs, then 64 MFMAs) paces the
-        // tile -- and waited for one tile LATER with a counted vmcnt (a row is first read three or more tiles after its issue), so
-        // that their landing time is on nobody's path.  (Round 2 tried the placement with a full drain in the same tile: 2-3 % slower.)
-        constexpr bool LATE_HALO = H3_LATE_HALO && !NORM && !LAG && !STAG;
+    auto main_loop = [&]() {
         auto issue_halo = [&](int vw) -> int {            // returns the number of halo rows issued this tile (0 .. 2); row 0 brings the patch
             int rows = 0;
             if (tap == 0 && chunk > 0) { load_halo_row(cur, 2, chunk, vw, 4, lane); ++rows; }
@@ -1233,69 +1116,49 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
         };
         for (int t = 0; t < ntiles; ++t) {
             H3_STAMP(0);
-            if constexpr (LAG) {
-                // k-step 1 of the tile before, from the fragments carried across its barrier: the matrix pipe has work the moment the
-                // barrier opens, while the SIMD partner (not lagging) waits for this tile's first fragments to come back from LDS
-                if (t > 0) {
-#pragma unroll
-                    for (int j = 0; j < MI; ++j)
-#pragma unroll
-                        for (int i = 0; i < NI; ++i)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cw[i]), __builtin_bit_cast(bf16x8, cp[j]), acc[i][j], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);           // (the carried fragments are dead from here on: nothing of the DMA issue above them)
-            }
             // refill: next weight tile, and the halo rows whose slots are free (see header).  ISSUER WAVES: the CU's vector-memory
             // path takes ~16 cycles per 1 KB DMA instruction, so the ~40 of a tile keep it busy for ~640 cycles; with every wave
             // issuing its share at the head of the tile, all eight sat in issue stalls for that long with the matrix pipes idle
             // (tools/halo_phases.py).  Now waves 4-7 issue ALL the DMAs while waves 0-3 -- their SIMD partners -- go straight to
             // their MFMAs.  (Not the same as splitting each wave's issue in time: waves 4-7 issuing their own share half way
             // through the tile measured 7 % slower; waves 0-3 issuing the halo rows, or 2-4 of the 8 weight DMAs per SIMD pair,
-            // AFTER their MFMAs -- in the ~1 000 cycles they wait at the barrier -- measured 2-3 % slower.)
-            // EARLY_FRAGS: an issuer wave first puts its OWN first fragment reads (4 weight + GJ pixel fragments of this tile, landed since
-            // the last barrier) in flight and issues its DMAs behind them, so that its first MFMA group does not start with an LDS round
-            // trip after ~1 000 cycles of DMA issue -- the issuer's serial path paces the tile.
-            constexpr bool EARLY_FRAGS = H3_EARLY_FRAGS && !LAG && !NORM;
-            auto issue_dmas = [&]() {
-                if (abl == 0 || abl == 2) {
-                    const int vw = wave & 3;
-                    if ((wave >> 2) == H3_ISSUER_HALF) {           // the weight tile: 8 DMA instructions per issuer wave and tile
-                        int ntap = tap + 1, nchk = chunk;
-                        if (ntap == 9) { ntap = 0; ++nchk; }
-                        if (t + 1 < ntiles) load_w(cur, (t + 1) & 1, nchk, MODE == MODE_FWD ? ntap : 8 - ntap, vw, 4, lane);
-                    }
-                    if (!LATE_HALO && (wave >> 2) == H3_HALO_HALF) issue_halo(vw);   // the halo rows (17 instructions each, ~1 row per tile on average)
+            // AFTER their MFMAs -- in the ~1 000 cycles they wait at the barrier -- measured 2-3 % slower, and so did the same with
+            // the wait for them relaxed to one tile later; the issuers' first fragment reads put ahead of their DMA issue cost the
+            // data gradient 3 %: profiles/r04_persistent_halo_gemm.txt items 7 and 8.)
+            if (abl == 0 || abl == 2) {
+                const int vw = wave & 3;
+                if ((wave >> 2) == H3_ISSUER_HALF) {           // the weight tile: 8 DMA instructions per issuer wave and tile
+                    int ntap = tap + 1, nchk = chunk;
+                    if (ntap == 9) { ntap = 0; ++nchk; }
+                    if (t + 1 < ntiles) load_w(cur, (t + 1) & 1, nchk, MODE == MODE_FWD ? ntap : 8 - ntap, vw, 4, lane);
                 }
-            };
-            if (!EARLY_FRAGS || abl == 2) issue_dmas();
+                if ((wave >> 2) == H3_HALO_HALF) issue_halo(vw);   // the halo rows (17 instructions each, ~1 row per tile on average)
+            }
             H3_STAMP(1);
             const int r = tap / 3, sx = tap - 3 * r;
             // halo offset (r, sx) pairs with weight tap (r, sx) forward and with the flipped tap (2-r, 2-sx) = 8 - tap in
             // the data gradient, so both modes walk the halo rows in the same order (the refill schedule relies on it)
             const int hr = wm + r;                                             // halo row of this wave's output row
             const int hc = frow + sx;                                          // halo column of fragment 0
-            const int fswP = H3_ROT ? ((hr * H3_PITCH + hc) & 6) : (((hr * H3_PITCH + hc) >> 1) & 7);   // same for every fragment (16 | fragment step)
+            const int fswP = (hr * H3_PITCH + hc) & 6;                         // same for every fragment (16 | fragment step)
             const char* bP = sH + (hr * H3_PITCH + hc) * 128;
             const char* bQ = sB + (t & 1) * (256 * 128) + (wn * WN + frow) * 128;
             // FOLD: the lanes holding pixel column 1 (fragment 0) / W-2 (fragment MI-1) read their patch row instead
-            constexpr bool PROT = H3_PATCH_ROT && H3_ROT;
-            // PROT: row (wm * 3 + r) * 6 + slot, slot L = {1, 0, 3}[sx], R = {2, 5, 4}[sx]; rotation L = {0, 2, 2}[sx], R = {6, 6, 0}[sx] (load_patch)
-            const int peL = PROT ? (wm * 3 + r) * 6 + ((0x31 >> (2 * sx)) & 3) : (wm * 2 + 0) * 9 + tap;
-            const int peR = PROT ? (wm * 3 + r) * 6 + 2 + ((0x2c >> (2 * sx)) & 3) : (wm * 2 + 1) * 9 + tap;
+            const int peL = (wm * 2 + 0) * 9 + tap;
+            const int peR = (wm * 2 + 1) * 9 + tap;
             const char* pL = sPatch + ((chunk & 1) * H3_PATCH_ROWS + peL) * 128;
             const char* pR = sPatch + ((chunk & 1) * H3_PATCH_ROWS + peR) * 128;
-            const int keyL = PROT ? ((0x90 >> (3 * sx)) & 7) : (peL >> 1) & 7, keyR = PROT ? ((0x36 >> (3 * sx)) & 7) : (peR >> 1) & 7;
+            const int keyL = (peL >> 1) & 7, keyR = (peR >> 1) & 7;
             const bool isL = hasL && frow == 1, isR = hasR && frow == 14;
             auto ldP = [&](int j, int kk) -> u32x4 {
-                const char* p = bP + j * 16 * BKB + ((H3_ROT ? ((fq + 4 * kk + fswP) & 7) : ((fq + 4 * kk) ^ fswP)) << 4);
+                const char* p = bP + j * 16 * BKB + (((fq + 4 * kk + fswP) & 7) << 4);
                 if (FOLD) {
-                    if (j == 0 && isL) p = pL + ((PROT ? ((fq + 4 * kk + keyL) & 7) : ((fq + 4 * kk) ^ keyL)) << 4);
-                    if (j == MI - 1 && isR) p = pR + ((PROT ? ((fq + 4 * kk + keyR) & 7) : ((fq + 4 * kk) ^ keyR)) << 4);
+                    if (j == 0 && isL) p = pL + (((fq + 4 * kk) ^ keyL) << 4);
+                    if (j == MI - 1 && isR) p = pR + (((fq + 4 * kk) ^ keyR) << 4);
                 }
                 return ld16(p);
             };
             if (abl != 2) {
-              if constexpr (!LAG) {
                 // Fragment pipeline: the reads are issued in the order the MFMA groups consume them -- k-step 0's weight fragments and the
                 // first GJ pixel fragments, then (while group 0 multiplies) the next pixel group and k-step 1's weight fragments -- so the
                 // first MFMA waits for 4 + GJ reads, not for the whole burst, and every later group finds its fragments landed.
@@ -1307,11 +1170,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                 u32x4 fp[2][GJ];
     #pragma unroll
                 for (int jj = 0; jj < GJ; ++jj) fp[0][jj] = ldP(jj, 0);
-                if constexpr (EARLY_FRAGS) {
-                    __builtin_amdgcn_sched_barrier(0);           // (the eight reads above go out first)
-                    issue_dmas();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
     #pragma unroll
                 for (int g = 0; g < NG; ++g) {
                     const int kk = g / GPK, jb = (g % GPK) * GJ;
@@ -1338,7 +1196,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                         // DMAs (about half of the step's 64 MFMAs), then share it.  The ~1 300 cycles of VALU / LDS work of a row go
                         // in the MIDDLE -- the partner wave, on the critical path, takes the whole pipe meanwhile; after the last
                         // MFMA the same work measured fully exposed (paired launch +20 us).
-                        if (!(H3_NORM_ABL & 2) && g == H3_NORM_AT && (wave >> 2) != H3_HALO_HALF) {
+                        if (g == H3_NORM_AT && (wave >> 2) != H3_HALO_HALF) {
                             __builtin_amdgcn_sched_barrier(0);
                             const int vw = wave & 3;
                             if (tap == 1 && chunk > 0) norm_row(2, chunk, vw, 4);
@@ -1349,62 +1207,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                         }
                     }
                 }
-              } else {
-                // lagging half: k-step 0 now (two groups of GJ pixel fragments), k-step 1's fragments only LOADED -- into registers the
-                // k-step 0 fragments have vacated -- and multiplied after the barrier (above / the tail behind the loop)
-                static_assert(MI == 2 * H3_GJ && KK == 2, "lagging pipeline: two pixel groups, two k-steps");
-                constexpr int GJ = H3_GJ;
-                u32x4 fw0[NI], fp[2][GJ];
-#pragma unroll
-                for (int i = 0; i < NI; ++i) fw0[i] = ld16(bQ + i * 16 * BKB + (((fq + 0) ^ fswQ) << 4));
-#pragma unroll
-                for (int jj = 0; jj < GJ; ++jj) fp[0][jj] = ldP(jj, 0);
-#pragma unroll
-                for (int jj = 0; jj < GJ; ++jj) fp[1][jj] = ldP(GJ + jj, 0);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int jj = 0; jj < GJ; ++jj)
-#pragma unroll
-                    for (int i = 0; i < NI; ++i)
-                        acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fw0[i]), __builtin_bit_cast(bf16x8, fp[0][jj]), acc[i][jj], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);           // (the loads below reuse the first group's registers: not above its MFMAs)
-#pragma unroll
-                for (int i = 0; i < NI; ++i) cw[i] = ld16(bQ + i * 16 * BKB + (((fq + 4) ^ fswQ) << 4));
-#pragma unroll
-                for (int jj = 0; jj < GJ; ++jj) cp[jj] = ldP(jj, 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int jj = 0; jj < GJ; ++jj)
-#pragma unroll
-                    for (int i = 0; i < NI; ++i)
-                        acc[i][GJ + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fw0[i]), __builtin_bit_cast(bf16x8, fp[1][jj]), acc[i][GJ + jj], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int jj = 0; jj < GJ; ++jj) cp[GJ + jj] = ldP(GJ + jj, 1);
-              }
             }
             H3_STAMP(2);
-            if (LATE_HALO && (wave >> 2) != H3_ISSUER_HALF) {
-                // this tile's pieces stay in flight; everything older (the pieces of the tile before) must have landed
-                int mine = 0;
-                if (abl == 0 || abl == 2) {
-                    const int vw = wave & 3;
-                    const bool patch = FOLD && tap == 3 && chunk + 1 < nchunk;
-                    const int rows = issue_halo(vw);
-                    mine = rows * (vw == 0 ? 5 : 4) + (patch ? (vw == 0 ? 2 : 1) : 0);
-                }
-                switch (mine) {
-                    case 0: sgg_wait_vm<0>(); break;
-                    case 4: sgg_wait_vm<4>(); break;
-                    case 5: sgg_wait_vm<5>(); break;
-                    case 7: sgg_wait_vm<7>(); break;
-                    case 8: sgg_wait_vm<8>(); break;
-                    case 9: sgg_wait_vm<9>(); break;
-                    case 10: sgg_wait_vm<10>(); break;
-                    case 12: sgg_wait_vm<12>(); break;
-                    default: sgg_wait_vm<0>(); break;
-                }
-            } else
             if (!NORM || (wave >> 2) == H3_HALO_HALF || (wave >> 2) == H3_ISSUER_HALF) SGG_WAIT_VM0();   // (NORM: the other waves only have stores in flight)
             H3_STAMP(3);
             SGG_WAIT_LGKM0();
@@ -1413,37 +1217,12 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
             H3_STAMP(5);
             if (++tap == 9) { tap = 0; ++chunk; }
         }
-        if constexpr (LAG) {
-            if (ntiles > 0 && abl != 2) {
-#pragma unroll
-                for (int j = 0; j < MI; ++j)
-#pragma unroll
-                    for (int i = 0; i < NI; ++i)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cw[i]), __builtin_bit_cast(bf16x8, cp[j]), acc[i][j], 0, 0, 0);
-            }
-        }
     };
-    if (STAG && (wave >> 2) == H3_LAG_HALF) main_loop(std::true_type{}); else main_loop(std::false_type{});
+    main_loop();
 
     if (dbg_clk) { g_dbg_clk[2] = clock64(); g_dbg_clk[3] = wall_clock64(); }
     if (abl == 6) return;
-    // the next tile's prologue (PERSIST): every wave past the main loop's last barrier, so the halo, patch buffer 0 and weight
-    // stage 0 are free.  Called once per tile from the epilogue, behind its loads and in front of its stores.
-    auto prime_next = [&]() {
-        primed = false;
-        if constexpr (PERSIST) {
-            if (it + 1 < tpb && tile_id + 1 < total_tiles && abl == 0) {
-                int lop = lane, nid = tile_id + 1;
-                asm volatile("" : "+v"(lop), "+s"(nid));             // (nothing of the next tile's addresses is computed ahead of this point)
-                const Tile nx = tile_of(nid);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) load_halo_row(nx, k, 0, wave, 8, lop);
-                load_patch(nx, 0, wave, 8, lop);
-                load_w(nx, 0, 0, MODE == MODE_FWD ? 0 : 8, wave, 8, lop);
-                primed = true;
-            }
-        }
-    };
+    auto prime_next = [&]() { primed = false; };
     // Epilogue, one 16-channel group at a time.  STATS 1 (forward): per-channel (sum, sumsq) of the STORED output for the
     // instance norm that follows the conv.  STATS 2 (data gradient): the first pass of the instance-norm BACKWARD that
     // consumes this gradient, (sum g, sum g*xhat) with g = dx * act'(gamma*xhat + beta) and xhat from that norm's input
@@ -1451,7 +1230,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
     // (registers -> 16-lane butterfly, fixed order) and writes one row per channel as pixel chunk (tile, wave row) of the
     // image, so the norm skips its own statistics pass over the tensor.
     const size_t prow = ((size_t)img * a.H + h0 + wm) * a.W + w0;
-    if constexpr (PERSIST && H3_PRIME_FIRST) prime_next();
     if constexpr (STATS != 2) {
         // pixel-major store order: the four 16-channel groups of a pixel go out back to back, so the 128 bytes a wave
         // writes per pixel merge into whole lines in L2 (channel-group-major order cost +47 MB of HBM fetches per launch:
@@ -1469,7 +1247,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
         // are dead here.  (With the tests inside the unrolled loops every load was followed by s_waitcnt vmcnt(0): 32 dependent
         // round trips at the tail of a grid that has nothing else to overlap them with.)
         const bool plain = a.act == SGG_ACT_NONE && !(MODE != MODE_FWD && (a.dst_f32 || a.addend_f32));
-        if (plain && H3_WIDE) {
+        if (plain) {
             // A lane holds 4 consecutive channels of one pixel per fragment: 8-byte stores, 32 per lane, and the tail of a grid
             // whose blocks all store at once is store-ISSUE bound.  Fragments 2 jp and 2 jp + 1 trade their halves between lane
             // rows (row_swap16) so that every lane owns 8 consecutive channels of ONE pixel -- lanes of rows 0 / 2 a pixel of the
@@ -1480,10 +1258,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                 const int jo = fq & 1, cb = (fq >> 1) * 8;
                 const size_t e0 = (prow + jo * 16 + frow) * DC + n0 + wn * WN + cb;   // element (fragment pair 0, group 0) of this lane
                 const size_t ej2 = (size_t)32 * DC;
-                // (persistent form: the addend in two halves of 8 loads -- with all 16 in flight next to the accumulators and the
-                // tile loop's state the data gradient spilled 30-130 registers)
-                constexpr int NH = (ADD && PERSIST) ? 2 : 1, JH = MI / 2 / NH;
-                if constexpr (!(PERSIST && H3_PRIME_FIRST)) { if constexpr (!ADD) prime_next(); }
+                constexpr int NH = 1, JH = MI / 2 / NH;
+                if constexpr (!ADD) prime_next();
 #pragma unroll
                 for (int hb = 0; hb < NH; ++hb) {
                     u32x4 adv[JH][NI];
@@ -1495,10 +1271,10 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                                 adv[jq][i] = zero16();
                                 if (n0 + wn * WN + i * 16 + cb < DC) {
                                     const bf16* ap = reinterpret_cast<const bf16*>(a.addend) + e0 + (hb * JH + jq) * ej2 + i * 16;
-                                    adv[jq][i] = SGG_NT_ADDEND ? ld16_nt(ap) : ld16(ap);
+                                    adv[jq][i] = ld16(ap);
                                 }
                             }
-                        if constexpr (!(PERSIST && H3_PRIME_FIRST)) { if (hb == 0) prime_next(); }
+                        if (hb == 0) prime_next();
                     }
 #pragma unroll
                     for (int jq = 0; jq < JH; ++jq) {
@@ -1519,7 +1295,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                                 const bf16x4 p0 = {(bf16)v0[0], (bf16)v0[1], (bf16)v0[2], (bf16)v0[3]}, p1 = {(bf16)v1[0], (bf16)v1[1], (bf16)v1[2], (bf16)v1[3]};
                                 if (STATS == 1) {
 #pragma unroll
-                                    for (int e = 0; e < 4; ++e) {           // (fragment order as in the 8-byte form: 2 jp, then 2 jp + 1)
+                                    for (int e = 0; e < 4; ++e) {           // (fragment order: 2 jp, then 2 jp + 1)
                                         const float r0 = (float)p0[e]; s1[i][e] += r0; s2[i][e] += r0 * r0;
                                     }
 #pragma unroll
@@ -1538,48 +1314,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
                 }
             };
             if (MODE != MODE_FWD && a.addend) run(std::true_type{}); else run(std::false_type{});
-        } else if (plain) {
-            auto run = [&](auto has_add) {
-                constexpr bool ADD = decltype(has_add)::value;
-                const size_t e0 = (prow + frow) * DC + n0 + wn * WN + fq * 4;      // element (pixel j = 0, group i = 0) of this lane
-                const size_t ej = (size_t)16 * DC;
-                bf16x4 adv[MI][NI];
-                if constexpr (ADD) {
-#pragma unroll
-                    for (int j = 0; j < MI; ++j)
-#pragma unroll
-                        for (int i = 0; i < NI; ++i) {
-                            const int dc = n0 + wn * WN + i * 16 + fq * 4;
-                            adv[j][i] = (bf16x4){(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
-                            if (dc < DC) adv[j][i] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16*>(a.addend) + e0 + j * ej + i * 16);
-                        }
-                }
-                if constexpr (!(PERSIST && H3_PRIME_FIRST)) prime_next();
-#pragma unroll
-                for (int j = 0; j < MI; ++j) {
-#pragma unroll
-                    for (int i = 0; i < NI; ++i) {
-                        const int dc = n0 + wn * WN + i * 16 + fq * 4;
-                        if (dc >= DC) continue;
-                        float v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + bv[i][e];
-                        if constexpr (ADD) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] += (float)adv[j][i][e];
-                        }
-                        bf16x4 pk = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-                        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(a.dst) + e0 + j * ej + i * 16) = pk;
-                        if (STATS == 1) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) { const float vr = (float)pk[e]; s1[i][e] += vr; s2[i][e] += vr * vr; }
-                        }
-                    }
-                }
-            };
-            if (MODE != MODE_FWD && a.addend) run(std::true_type{}); else run(std::false_type{});
         } else {
-            if constexpr (!(PERSIST && H3_PRIME_FIRST)) prime_next();
+            prime_next();
 #pragma unroll
             for (int j = 0; j < MI; ++j) {
                 const size_t dpix = prow + j * 16 + frow;
@@ -1819,7 +1555,7 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
             const bool ok = hp < S2_TJ + 2 && (unsigned)hi < (unsigned)a.Ho && (unsigned)wi < (unsigned)a.Wo;
             // rotation swizzle of the halo rows (conflict-free fragment reads for every tap shift; see conv3x3_halo_gemm_kernel)
             const int hrow_ = k * S2_PITCH + hp;
-            const int schunk = H3_ROT ? ((hpos - (hrow_ & 6)) & 7) : (hpos ^ ((hrow_ >> 1) & 7));
+            const int schunk = (hpos - (hrow_ & 6)) & 7;
             const char* src = ok ? a.src + ((((size_t)T.img * a.Ho + hi) * a.Wo + wi) * SC + chunk * 64) * 2 + (schunk << 4) : zero;
             dma16_to_lds(src, (__attribute__((address_space(3))) void*)(dstb + (k * S2_PITCH + cg * 8) * 128));
         }
@@ -1876,7 +1612,7 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
                 const int bs = (sx + PL) & 1, ds = (bs + PL - sx) / 2;
                 const int cls = ar * 2 + bs;
                 const int hrow = (wave + dr + 1) * S2_PITCH + (ds + 1) + frow;   // halo pixel of fragment 0, this lane
-                const int fswP = H3_ROT ? (hrow & 6) : ((hrow >> 1) & 7);
+                const int fswP = hrow & 6;
                 const char* bP = hb + hrow * 128;
                 const int wr = sx * 64 + frow;
                 const int fswQ = (wr >> 1) & 7;
@@ -1887,7 +1623,7 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
 #pragma unroll
                     for (int i = 0; i < 4; ++i) fw[kk][i] = ld16(bQ + i * 16 * 128 + (((fq + 4 * kk) ^ fswQ) << 4));
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) fp[kk][j] = ld16(bP + j * 16 * 128 + ((H3_ROT ? ((fq + 4 * kk + fswP) & 7) : ((fq + 4 * kk) ^ fswP)) << 4));
+                    for (int j = 0; j < 2; ++j) fp[kk][j] = ld16(bP + j * 16 * 128 + (((fq + 4 * kk + fswP) & 7) << 4));
                 }
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
@@ -2084,8 +1820,10 @@ static bool halo3_ok(const ConvArgs& a, int mode, bool is_bf16) {
     if (a.W % H3_TW || (a.H & 1) || a.H < 4) return false;
     const int SC = mode == MODE_FWD ? a.C : a.K;
     if (SC % 64) return false;
-    // buffer-descriptor DMAs: one image of the source and one tile's weight rows must stay below SGG_BUF_OOB bytes
-    if ((int64_t)a.H * a.W * SC * 2 >= (int64_t)SGG_BUF_OOB || (int64_t)256 * 9 * SC * 2 >= (int64_t)SGG_BUF_OOB) return false;
+    // one image of the source and one tile's weight rows below 1 GiB.  The bound dates from a DMA addressing form that is gone
+    // (the kernel's addresses are 64-bit); it stays because it decides which kernel a shape is dispatched to
+    constexpr int64_t kMaxBytes = (int64_t)1 << 30;
+    if ((int64_t)a.H * a.W * SC * 2 >= kMaxBytes || (int64_t)256 * 9 * SC * 2 >= kMaxBytes) return false;
     return mode == MODE_FWD || mode == MODE_DGRAD;
 }
 
@@ -2097,12 +1835,6 @@ static int launch_halo3(const ConvArgs& a, hipStream_t s) {
     SGG_LDS_ATTR(kern, lds);
     const int DC = MODE == MODE_FWD ? a.K : a.C;
     int64_t blocks = (int64_t)a.N * (a.H / 2) * (a.W / H3_TW) * ((DC + 255) / 256);
-    // persistent form: one block per CU (one fits: >= 134 KB of LDS), each walking ceil(tiles / blocks) consecutive tiles
-    constexpr int ADDR = SRC == 0 ? H3_ADDR0 : (SRC == 1 ? H3_ADDR1 : H3_ADDR2);
-    if (H3_PERSIST && SRC != 2 && ADDR == 0 && STATS != 2 && SGG_ABLATE_OF(a) == 0) {
-        const int64_t cus = sgg_num_cus();
-        if (blocks > cus) { const int64_t tpb = (blocks + cus - 1) / cus; blocks = (blocks + tpb - 1) / tpb; }
-    }
     sgg_launch_timed(kern, dim3((unsigned)blocks), dim3(512), (unsigned)lds, s, a);
     return sgg_check_launch();
 }
@@ -3931,9 +3663,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_glds_kernel(WgradArgs a) {
 #ifndef SGG_NT_SLABS
 #define SGG_NT_SLABS 1          // 1: the reducer reads the split slabs (their last use) with the streaming cache policy
 #endif
-#ifndef SGG_NT_ADDEND
-#define SGG_NT_ADDEND 0         // 1: the 3x3 halo data gradient reads its skip-gradient addend (its last use) with the streaming policy
-#endif
 // dw[tap][c<Cr][k<Kr] (+)= sum_split ws[split][tap*C + c][k]   (fixed summation tree -> deterministic)
 // One thread per 4 consecutive k (K is a multiple of 8): 16-byte slab reads, 4 independent partial sums in flight.
 // dw2 != nullptr: two networks in one launch -- slabs [splits, 2 * splits) of ws sum into dw2
@@ -4293,9 +4022,7 @@ struct W9Args {
 // already selects the half line, bits 1 and 3 pick one of the four 32-byte column pairs.
 __device__ inline int w9_xkey(int row) { return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1; }
 
-#ifndef W9_NT
-#define W9_NT 0          // streaming (nt) LDS-DMA of the operands: 1 the x halo (saved forward activations: their last use), 2 the dy tiles
-#endif
+// (streaming (nt) LDS-DMA of the x halo / the dy tiles: the step does not move, profiles/r04_nt_loads.txt)
 __global__ __launch_bounds__(512) void conv3x3_wgrad_halo_kernel(W9Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages of { X halo [4][72][128 B], DY [128][256 B] }
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave index as a scalar
@@ -4339,8 +4066,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_halo_kernel(W9Args a) {
             const int key = wg2_key<bf16>(px) & 15;
             const int trow = px >> 6, tcol = px & 63;
             const char* src = dys + ((((size_t)n * a.H + h0 + trow) * a.W + w0 + tcol) * a.K + n0) * 2 + ((pos ^ key) << 4);
-            if (W9_NT & 2) dma16_to_lds_nt(src, (__attribute__((address_space(3))) void*)(sD + d * 1024));
-            else dma16_to_lds(src, (__attribute__((address_space(3))) void*)(sD + d * 1024));
+            dma16_to_lds(src, (__attribute__((address_space(3))) void*)(sD + d * 1024));
         }
         // x halo: 36 wave-instructions of 8 pixels x 128 B (row k = q / 9, column group q % 9); wave w issues w, w+8, ...
 #pragma unroll
@@ -4357,8 +4083,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_halo_kernel(W9Args a) {
                 wi = wi < 0 ? -wi : (wi >= a.W ? 2 * (a.W - 1) - wi : wi);
             } else ok = ok && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
             const char* src = ok ? xs + ((((size_t)n * a.H + hi) * a.W + wi) * a.C + c0) * 2 + ((pos ^ key) << 4) : zero;
-            if (W9_NT & 1) dma16_to_lds_nt(src, (__attribute__((address_space(3))) void*)(sX + (k * W9_PITCH + cg * 8) * 128));
-            else dma16_to_lds(src, (__attribute__((address_space(3))) void*)(sX + (k * W9_PITCH + cg * 8) * 128));
+            dma16_to_lds(src, (__attribute__((address_space(3))) void*)(sX + (k * W9_PITCH + cg * 8) * 128));
         }
     };
 

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "sg-gan-tf2_amd"))
 
 # mangled-name fragments of the kernels that must not spill (production tile configurations)
 MUST_NOT_SPILL = [
-    # conv3x3_halo_gemm_kernel<MODE, FOLD, STATS, PAIR>: every instantiation the library dispatches
+    # conv3x3_halo_gemm_kernel<MODE, FOLD, STATS, PAIR, SRC>: a fragment up to PAIR covers every SRC of it the library dispatches
     "conv3x3_halo_gemm_kernelILi0ELb0ELi0ELb0E",               # 3x3 forward, halo resident
     "conv3x3_halo_gemm_kernelILi0ELb0ELi1ELb0E",               # ... with the norm-statistics epilogue
     "conv3x3_halo_gemm_kernelILi0ELb0ELi0ELb1E",               # ... on a stacked pair of networks
@@ -27,8 +27,10 @@ MUST_NOT_SPILL = [
     "conv3x3_halo_gemm_kernelILi1ELb1ELi0ELb0E",               # 3x3 data gradient, REFLECT fold
     "conv3x3_halo_gemm_kernelILi1ELb0ELi0ELb1E", "conv3x3_halo_gemm_kernelILi1ELb1ELi0ELb1E",   # ... paired
     # (<DGRAD, *, STATS=2>: the data gradient with the norm-backward sums in its epilogue -- opt-in (fuse_in_bwd), off by default, measured
-    # "no gain" at the step's launch size in round 3 -- sat at 249-250 VGPRs then; round 4's restructured kernel body (tile loop, two loop
-    # copies for the staggered form) tips it into 29-41 spilled VGPRs.  Numerically tested (test_conv_dgrad_norm_bwd_epilogue), not guarded here.)
+    # "no gain" at the step's launch size in round 3 -- sat at 249-250 VGPRs then; the kernel body as round 4 restructured it (a tile loop
+    # that runs once, the main loop as a lambda) spills 29 (FOLD: 38) VGPRs, 112 (124) bytes of scratch.  Without that structure both build
+    # with 0 spills at 249 / 250 VGPRs, but that form changes the code of all 16 instantiations and waits for a timing against this one.
+    # Numerically tested (test_conv_dgrad_norm_bwd_epilogue), not guarded here.)
     "conv3x3_wgrad_halo_kernel",                               # 3x3 weight gradient, all taps per block
     "conv3x3_wgrad_halo_s2_kernel",                            # the same for stride 2
     "deconv_s2_halo_kernel",                                   # stride-2 data gradient / Conv2DTranspose forward

@@ -654,6 +654,34 @@ def test_group2_launches_equal_two_single_calls(sg, cfg):
             same(dwt[k], ref, ("deconv wgrad", k))
 
 
+@pytest.mark.parametrize("pad", ["REFLECT-1", "SAME"])
+def test_conv_pair_launches_equal_two_single_calls(sg, pad):
+    """sgg_conv2d_fwd_stats_pair / sgg_conv2d_bwd_data_pair -- the 3x3 halo GEMM's PAIR instantiations, a stacked batch with
+    per-image weights -- must be BIT-IDENTICAL to the single-network calls on each image with that image's weights: a tile's
+    arithmetic does not depend on PAIR.  Output, statistics rows, and the data gradient with its skip-gradient addend (REFLECT:
+    the folded form).  Two column tiles (left and right mirror patches in different tiles), two source-channel chunks in the
+    forward (halo refill), a channel tail over two output tiles."""
+    from sggan_amd import kernels as K
+    N, H, W, Ci, Co = 2, 4, 256, 128, 320
+    dt = torch.bfloat16
+    padding, refl = ("VALID", 1) if pad.startswith("REFLECT") else (pad, 0)
+    g = K.conv_geom(N, H, W, Ci, Co, 3, 3, 1, padding, refl, dt)
+    g1 = K.conv_geom(1, H, W, Ci, Co, 3, 3, 1, padding, refl, dt)
+    assert g.pair_ok
+    gen = torch.Generator().manual_seed(17)
+    r = lambda *sh: torch.randn(sh, generator=gen).cuda()
+    x, dy, add = r(*g.x_shape).to(dt), r(*g.y_shape).to(dt), r(*g.x_shape).to(dt)
+    ws_ = [K.pack_weights(r(3, 3, Ci, Co) / (9 * Ci) ** 0.5, Ci, Co, dt) for _ in range(2)]
+    bs = [r(Co), r(Co)]
+    y2, p2 = K.conv_fwd_stats_pair(g, x, ws_[0][0], bs[0], ws_[1][0], bs[1], 1)
+    dx2 = K.conv_dgrad_pair(g, dy, ws_[0][1], ws_[1][1], 1, add)
+    for k in range(2):
+        y1, p1 = K.conv_fwd_stats(g1, x[k:k + 1], ws_[k][0], bs[k])
+        assert torch.equal(y2[k:k + 1], y1), ("forward output", k)
+        assert torch.equal(p2[k:k + 1], p1), ("statistics rows", k)
+        assert torch.equal(dx2[k:k + 1], K.conv_dgrad(g1, dy[k:k + 1], ws_[k][1], add[k:k + 1])), ("data gradient + addend", k)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", [
     ("bench: residual-block shape, 8 images", 8, 64, 128, 256, 256),
