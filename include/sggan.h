@@ -517,6 +517,37 @@ int sgg_class_boundary_band(const uint8_t* cls, uint8_t* band, int N, int H, int
 size_t sgg_image_quality_workspace(int N, int H, int W);
 int sgg_image_quality(const void* a, int kind_a, int cstride_a, const void* b, int kind_b, int cstride_b,
                       int N, int H, int W, double* out, void* ws, size_t ws_bytes, void* stream);
+/* ---- differentiable augmentation of the discriminators' input (Zhao et al. 2020, policies colour + cutout) ----
+ * x, y, dy, dx, addend: dtype [rows][H][W][Cpad], Cpad == SGG_CPAD, 16-byte aligned.  params: float [rows][8] on the DEVICE,
+ * 16-byte aligned, one row [b, s, c, y0, x0, ch, cw, 0] per image.  With C = C_real, per pixel p = (y, x) and channel k < C, in f32:
+ *     x1 = x + b;   m = (x1[p,0] + ... + x1[p,C-1]) / C;   x2 = x1 + (s - 1) * (x1 - m)
+ *     M  = (float)(b + S / (C*H*W)),  S = the sum of x over the image's real channels, in double
+ *     x3 = x2 + (c - 1) * (x2 - M);   y = 0 if y0 <= y < y0+ch and x0 <= x < x0+cw (a select), else x3
+ *   sgg_diffaug_fwd writes y (out of place: y == x is SGG_EINVAL).  sgg_diffaug_bwd writes the adjoint for the gradient dy of y:
+ *     g3 = 0 inside the rectangle, else dy;   Gs = the sum of g3 over the image's real channels, in double;   g2 = c * g3
+ *     dx = g2 + (s - 1) * (g2 - mean_k g2[p,:]) + (float)((1 - c) * Gs / (C*H*W))  (+ addend[p,k] when addend != NULL)
+ *   Padded channels of y and dx are written as 0.  The row [0, 1, 1, 0, 0, 0, 0, 0] reproduces the values of x (and of dy + addend).
+ *   Two launches each (2048-pixel partial sums in a fixed order, then the apply pass, whose every block folds the image's
+ *   partials again in the same order): no atomics, nothing allocated, no host sync, the same bits every run.
+ *   ws: sgg_diffaug_workspace(rows, H, W) bytes (0: not supported), 8-byte aligned; need not be initialised.
+ * sgg_diffaug_draw fills `rows` parameter rows from Philox4x32-10 (Random123's constants), ONE launch: key (seed, 0), counter
+ *   (t_lo, t_hi, g, 4 * stream_id + j) with t = *iterations, int64 on the DEVICE and read when the launch RUNS (the call can be
+ *   captured; a step counter that advances between replays gives new draws), g = (uint32)(sample_offset + row), j the draw block;
+ *   u = (word >> 8) * 2^-24.  j = 0 (policy bit SGG_DIFFAUG_COLOR): b = (u0 - 0.5) * brightness, s = 2 * u1, c = u2 + 0.5, else
+ *   b, s, c = 0, 1, 1.  j = 1 (SGG_DIFFAUG_CUTOUT): ch = H / 2, cw = W / 2, y0 = floor(u0 * (H + 1 - ch % 2)) - ch / 2 and x0
+ *   likewise from u1 and W (f32 products), else y0 = x0 = ch = cw = 0.
+ * Before any launch -- SGG_EINVAL: a NULL or misaligned buffer, rows / H / W <= 0, C_real outside 1..Cpad, a bad dtype, unknown
+ *   policy bits, a negative stream_id or sample_offset; SGG_EUNSUPPORTED: Cpad != SGG_CPAD, H*W > 2^26, rows * ceil(H*W / 2048)
+ *   >= 2^24 (a launch holds fewer than 2^32 threads, 256 per block); SGG_EWORKSPACE: a short ws. */
+#define SGG_DIFFAUG_COLOR 1
+#define SGG_DIFFAUG_CUTOUT 2
+size_t sgg_diffaug_workspace(int rows, int H, int W);
+int sgg_diffaug_draw(float* params, int rows, const int64_t* iterations, uint32_t seed, int64_t sample_offset, int stream_id,
+                     int H, int W, int policy_bits, float brightness, void* stream);
+int sgg_diffaug_fwd(const void* x, void* y, const float* params, int rows, int H, int W, int C_real, int Cpad, int dtype,
+                    void* ws, size_t ws_bytes, void* stream);
+int sgg_diffaug_bwd(const void* dy, const float* params, const void* addend, void* dx, int rows, int H, int W, int C_real,
+                    int Cpad, int dtype, void* ws, size_t ws_bytes, void* stream);
 /* f32 [P][Cs] -> dtype [P][Cd] with zero fill (Cd >= Cs), and back (drops padded channels). */
 int sgg_pad_channels(const float* src, void* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);
 int sgg_unpad_channels(const void* src, float* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);

@@ -132,6 +132,10 @@ SIGNATURES = {
     "sgg_class_boundary_band": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "sgg_image_quality_workspace": (_sz, [_i, _i, _i]),
     "sgg_image_quality": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "sgg_diffaug_workspace": (_sz, [_i, _i, _i]),
+    "sgg_diffaug_draw": (_i, [_vp, _i, _vp, C.c_uint32, _i64, _i, _i, _i, _i, _f, _vp]),
+    "sgg_diffaug_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "sgg_diffaug_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_pad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "sgg_unpad_channels": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
 }

@@ -15,6 +15,7 @@ class GradExchange:
     def __init__(self, process_group=None):
         self.group = process_group if process_group is not None else dist.group.WORLD
         self.world = dist.get_world_size(self.group)
+        self.rank = dist.get_rank(self.group)
         self.grad_scale = 1.0 / self.world
 
     def broadcast_(self, flat_params, src_rank_in_group=0):

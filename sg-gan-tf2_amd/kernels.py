@@ -1044,3 +1044,62 @@ def image_quality(a, b, out=None, workspace=None):
     A.check(A.lib().sgg_image_quality(_p(a), kind_a, Ca, _p(b), kind_b, b.shape[3], N, H, W, _p(out), _p(workspace), workspace.numel(),
                                       _s()), "image_quality")
     return out
+
+
+# ----------------------------------------------------------------------------- differentiable augmentation (csrc/diffaug.hip)
+DIFFAUG_COLOR, DIFFAUG_CUTOUT = 1, 2
+DIFFAUG_CHUNK = 2048             # pixels per block of the partial-sum and apply passes (DA_CHUNK, csrc/diffaug.hip)
+
+
+def diffaug_policy_bits(policy) -> int:
+    """'color,cutout' | 'color' | 'cutout' -> policy bits; None / '' -> 0 (off)."""
+    bits = 0
+    for word in (policy or "").replace(" ", "").split(","):
+        if word == "color":
+            bits |= DIFFAUG_COLOR
+        elif word == "cutout":
+            bits |= DIFFAUG_CUTOUT
+        elif word:
+            raise ValueError(f"diffaug policy '{policy}': unknown word '{word}' (color, cutout)")
+    return bits
+
+
+def diffaug_draw(params, iterations, seed, sample_offset, stream_id, H, W, policy_bits, brightness=0.25):
+    """sgg_diffaug_draw: fill the (rows, 8) f32 device table ``params`` with the rows of samples sample_offset .. + rows for the
+    draw stream ``stream_id`` (2 * which_D + role) at the step ``iterations`` (a 1-element int64 DEVICE tensor) holds when the
+    launch runs.  One launch, no host state."""
+    assert params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == 8
+    assert iterations.dtype == torch.int64 and iterations.is_cuda
+    A.check(A.lib().sgg_diffaug_draw(_p(params), params.shape[0], C.c_void_p(iterations.data_ptr()), int(seed) & 0xffffffff,
+                                     int(sample_offset), int(stream_id), int(H), int(W), int(policy_bits), float(brightness), _s()),
+            "diffaug_draw")
+    return params
+
+
+def _diffaug_ws(rows, H, W, device):
+    need = int(A.lib().sgg_diffaug_workspace(rows, H, W))
+    if need == 0:
+        A.check(A.EUNSUPPORTED, f"diffaug {rows}x{H}x{W}")
+    return workspace(need, device)
+
+
+def diffaug(x, params, C_real, out=None):
+    """sgg_diffaug_fwd: x internal (rows,H,W,8) -> the augmented copy (never in place), one parameter row per image."""
+    rows, H, W, Cp = x.shape
+    assert params.dtype == torch.float32 and tuple(params.shape) == (rows, 8)
+    out = _out(out, tuple(x.shape), x.dtype, x.device)
+    ws = _diffaug_ws(rows, H, W, x.device)
+    A.check(A.lib().sgg_diffaug_fwd(_p(x), _p(out), _p(params), rows, H, W, int(C_real), Cp, dt(x), _p(ws), ws.numel(), _s()), "diffaug")
+    return out
+
+
+def diffaug_bwd(dy, params, C_real, addend=None, out=None):
+    """sgg_diffaug_bwd: the adjoint of diffaug for the gradient dy of its output (+ addend, joined once)."""
+    rows, H, W, Cp = dy.shape
+    assert params.dtype == torch.float32 and tuple(params.shape) == (rows, 8)
+    assert addend is None or (addend.shape == dy.shape and addend.dtype == dy.dtype)
+    out = _out(out, tuple(dy.shape), dy.dtype, dy.device)
+    ws = _diffaug_ws(rows, H, W, dy.device)
+    A.check(A.lib().sgg_diffaug_bwd(_p(dy), _p(params), _p(addend), _p(out), rows, H, W, int(C_real), Cp, dt(dy), _p(ws), ws.numel(),
+                                    _s()), "diffaug_bwd")
+    return out

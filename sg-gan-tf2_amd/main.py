@@ -85,6 +85,14 @@ def build_parser():
            "the ramp min(decay, (1 + t) / (10 + t)) over applied updates, so it works under --graph, leaves the average alone when "
            "an update is skipped, and goes on after --continue_train")
     # (absent from the namespace unless given, like the guard flags)
+    a("--diffaug", dest="diffaug", metavar="POLICY", default=argparse.SUPPRESS,
+      help="differentiable augmentation of everything the discriminators see (Zhao et al. 2020): 'color', 'cutout' or "
+           "'color,cutout' (default: off).  The same random transform family is applied to reals and fakes in front of D and the "
+           "generator's adversarial gradient flows back through it; the parameters are drawn on the device from D's step counter "
+           "and the global sample index, so it works under --graph, with data parallelism and after --continue_train.  "
+           "Translation is not offered (D's class mask cannot follow a shift); not with --use_pool")
+    a("--diffaug_brightness", dest="diffaug_brightness", type=float, default=argparse.SUPPRESS,
+      help="--diffaug color: width of the brightness shift, b = (u - 0.5) * this (default 0.25: images live in [0,1])")
     a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
       help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "
            "class map) pairs and score it against the class map: 'Class Overall Accuracy' ... 'Class Mean IoU' scalars, "

@@ -33,7 +33,8 @@ def default_args(**over):
              dtype="bf16", device="cuda", n_blocks=9, seed=19, graph=False, mixed=False, paired=None,
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
-             crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None)
+             crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
+             diffaug_brightness=0.25)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -96,6 +97,21 @@ class sggan(object):
         # hands back older ones) stays the default of the eager path
         self.pool_static = bool(g("pool_static", False)) or (self.use_pool and bool(g("graph", False)))
         self.pool = (StaticImagePool if self.pool_static else ImagePool)(g("max_size", 50), rng=g("pool_rng", None))
+        # diffaug (off by default): every image a discriminator sees -- reals and fakes -- goes through ONE random,
+        # differentiable transform first (Zhao et al. 2020: colour and cutout; translation is left out, the mask D multiplies
+        # into its last map cannot follow a pixel shift).  D reads an augmented COPY of its stacked input, the generators' loss
+        # backpropagates through the transform's adjoint, which also takes over the gradient join (``addend``).  The rows of
+        # parameters are drawn on the device from D's own step counter and the global sample index (K.diffaug_draw), so there is
+        # no new state: graph replay, checkpoints and data parallelism see the draws of the plain single-device run.
+        self.diffaug = K.diffaug_policy_bits(g("diffaug", None))
+        self.diffaug_brightness = float(g("diffaug_brightness", 0.25))
+        # (_diffaug_bits: the policy bits handed to the draw launches, apart from ``diffaug``, which gates the wiring, for ONE reason:
+        # the wiring test sets it to 0 on a built model, so that the option's own launches write neutral rows.  Nothing else writes it.)
+        self._diffaug_bits, self._diffaug_seed = self.diffaug, int(seed)
+        if self.diffaug and self.use_pool:
+            raise NotImplementedError("diffaug with use_pool: the draws are keyed by (discriminator step, global sample index), and a "
+                                      "fake handed back by the image pool carries no sample identity (nor the step it was made at); "
+                                      "train with one of the two")
         self.pair_wgrads = bool(g("pair_wgrads", True))   # cycle step: one weight-gradient launch per layer for both applications of a G
         self.batch_d_real_fake = bool(g("batch_d_real_fake", True))   # pool mode: D(real) and D(pooled fakes) as one 2N pass
         self.d_quad = bool(g("d_quad", True))             # reals and fakes through the discriminator(s) as ONE stacked pass (both step flavours)
@@ -347,6 +363,23 @@ class sggan(object):
             buf = bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.device)
         return buf
 
+    def _diffaug_table(self, n, H, W, streams):
+        """The step's parameter table, n rows per entry of ``streams`` = ((discriminator, which_D, role), ...) in the row order of
+        the batch it augments; role 0: reals, 1: fakes.  One draw launch per entry: each reads ITS discriminator's device step
+        counter when it runs, and is keyed by the global sample index (rank * n + row), not by the row of the stacked buffer."""
+        par = self._stacked("da_par", (len(streams) * n, 8), torch.float32)
+        off = (self._dp.rank if self._dp is not None else 0) * n
+        for i, (Dn, which, role) in enumerate(streams):
+            K.diffaug_draw(par[i * n:(i + 1) * n], Dn.P.iterations, self._diffaug_seed, off, 2 * which + role, H, W, self._diffaug_bits,
+                           self.diffaug_brightness)
+        return par
+
+    @property
+    def diffaug_params(self):
+        """The last step's parameter table (rows x 8, f32, on the device), in the row order of the discriminators' stacked input:
+        reference step [real; fake], cycle step [D_B real; D_B fake; D_A fake; D_A real].  None before the first step."""
+        return self._stack_bufs.get("da_par")
+
     def train_step(self, args=None):
         """model.py:169-200.  Reads ``real_A, seg_A`` (N,H,W,3) in [0,1] and ``mask_A`` (N,mh,mw,C);
         writes ``fake_A, gen_loss, disc_loss``; updates G, D and both Adam states."""
@@ -377,13 +410,23 @@ class sggan(object):
         D.P.zero_grad()
 
         fake, tG = G.forward(real, out=d_in[N:] if stack else None)         # :175-179 (D2)
+        aug = bool(self.diffaug)
+        d_seg, d_fake = seg, fake
+        if aug:         # D judges augmented copies; ``seg`` and ``fake`` themselves stay as the L1 term reads them
+            par = self._diffaug_table(N, real.shape[1], real.shape[2], ((D, 0, 0), (D, 0, 1)))
+            d_aug = self._stacked("d_aug", (2 * N,) + tuple(real.shape[1:]), real.dtype)
+            if stack:
+                K.diffaug(d_in, par, self.output_c_dim, out=d_aug)
+            else:
+                d_seg = K.diffaug(seg, par[:N], self.output_c_dim, out=d_aug[:N])
+                d_fake = K.diffaug(fake, par[N:], self.output_c_dim, out=d_aug[N:])
         if stack:
-            da_both, tDq = D.forward(d_in, mask2)
+            da_both, tDq = D.forward(d_aug if aug else d_in, mask2)
             da_real, da_fake = da_both[:N], da_both[N:]
             tDr, tDf = None, D.slice_tape(tDq, N, 2 * N)
         else:
-            da_real, tDr = D.forward(seg, mask)                             # :186
-            da_fake, tDf = D.forward(fake, mask)                            # :187 (= :188)
+            da_real, tDr = D.forward(d_seg, mask)                           # :186
+            da_fake, tDf = D.forward(d_fake, mask)                          # :187 (= :188)
 
         # losses + their logit gradients, all on device (no host sync)
         gl, dl = self._loss[0:1], self._loss[1:2]
@@ -404,7 +447,10 @@ class sggan(object):
             D.backward(tDf, d_fake_d, want_dx=False, param_grads=True)
         hD = self._allreduce(D)
         # gen_tape.gradient(gen_loss, G vars)    (:196): through D's data path, then G
-        dfake = D.backward(tDf, d_fake_g, want_dx=True, param_grads=False, addend=dfake_l1)   # (the join rides on h0's data-gradient store)
+        if aug:         # ... and back through the transform's adjoint, which takes over the join
+            dfake = K.diffaug_bwd(D.backward(tDf, d_fake_g, want_dx=True, param_grads=False), par[N:], self.output_c_dim, addend=dfake_l1)
+        else:
+            dfake = D.backward(tDf, d_fake_g, want_dx=True, param_grads=False, addend=dfake_l1)   # (the join rides on h0's data-gradient store)
         hook, (hG,) = self._bucketed_allreduce((G,))
         G.backward(tG, dfake, want_dx=False, param_grads=True, on_unit_done=hook)
 
@@ -509,8 +555,16 @@ class sggan(object):
         cyc_A, t4 = Gba.forward(fake_B)
         fake_A, t3 = Gba.forward(rB)
         cyc_B, t2 = Gab.forward(fake_A)
-        DB_fake, tDBf = Db.forward(fake_B, mA)
-        DA_fake, tDAf = Da.forward(fake_A, mB)
+        aug = bool(self.diffaug)
+        aBf, aAf, aAr, aBr = fake_B, fake_A, rA, rB                      # what the discriminators judge
+        if aug:         # (never with the pool: refused by the constructor)
+            n = rA.shape[0]
+            par = self._diffaug_table(n, rA.shape[1], rA.shape[2], ((Db, 1, 0), (Db, 1, 1), (Da, 0, 1), (Da, 0, 0)))
+            pBr, pBf, pAf, pAr = par[:n], par[n:2 * n], par[2 * n:3 * n], par[3 * n:]
+            aBf, aAf = K.diffaug(fake_B, pBf, C), K.diffaug(fake_A, pAf, C)
+            aAr, aBr = K.diffaug(rA, pAr, C), K.diffaug(rB, pBr, C)
+        DB_fake, tDBf = Db.forward(aBf, mA)
+        DA_fake, tDAf = Da.forward(aAf, mB)
         wA, wB = K.seg_edge_weight(sA, C), K.seg_edge_weight(sB, C)
 
         crit = K.mse_const if self.use_lsgan else K.bce_logits
@@ -556,13 +610,13 @@ class sggan(object):
         if pooled_A and self.batch_d_real_fake:
             d_loss_pass(Da, rA, mA, None, None, True, pfA, smB, None, None, True)
         else:
-            DA_real, tDAr = Da.forward(rA, mA)
+            DA_real, tDAr = Da.forward(aAr, mA)
             d_loss_pass(Da, rA, mA, DA_real, tDAr, pooled_A, pfA if pooled_A else None, smB if pooled_A else None, DA_fake, tDAf, True)
         hDa = self._allreduce(Da)
         if pooled_B and self.batch_d_real_fake:
             d_loss_pass(Db, rB, mB, None, None, True, pfB, smA, None, None, False)
         else:
-            DB_real, tDBr = Db.forward(rB, mB)
+            DB_real, tDBr = Db.forward(aBr, mB)
             d_loss_pass(Db, rB, mB, DB_real, tDBr, pooled_B, pfB if pooled_B else None, smA if pooled_B else None, DB_fake, tDBf, False)
         hDb = self._allreduce(Db)
         # generator gradients: cycle terms first (they reach the other generator through the fakes).  Each generator is
@@ -571,8 +625,12 @@ class sggan(object):
         # (the gradient joins ride on the first layer's data-gradient store -- ``addend`` -- instead of separate passes)
         d_fB = Gba.backward(t4, d_cycA, want_dx=True, addend=d_fB)
         d_fA = Gab.backward(t2, d_cycB, want_dx=True, addend=d_fA)
-        d_fB = Db.backward(tDBf, gB_g, want_dx=True, param_grads=False, addend=d_fB)
-        d_fA = Da.backward(tDAf, gA_g, want_dx=True, param_grads=False, addend=d_fA)
+        if aug:         # through the transform's adjoint, which takes over the join
+            d_fB = K.diffaug_bwd(Db.backward(tDBf, gB_g, want_dx=True, param_grads=False), pBf, C, addend=d_fB)
+            d_fA = K.diffaug_bwd(Da.backward(tDAf, gA_g, want_dx=True, param_grads=False), pAf, C, addend=d_fA)
+        else:
+            d_fB = Db.backward(tDBf, gB_g, want_dx=True, param_grads=False, addend=d_fB)
+            d_fA = Da.backward(tDAf, gA_g, want_dx=True, param_grads=False, addend=d_fA)
         hook, (hGba,) = self._bucketed_allreduce((Gba,))
         Gba.backward(t3, d_fA, on_unit_done=hook)               # second application: the paired weight gradients run here
         Gba.flush_wgrads(); Gba.pair_wgrads = False             # (nothing is left to flush unless a partner never came)
@@ -628,11 +686,15 @@ class sggan(object):
         C = self.output_c_dim
         f1, t1 = Gp1.forward(x1, out=dq[n:3 * n] if quad else None)   # [fake_B; fake_A]
         c2, t2 = Gp2.forward(f1)                              # [cyc_A; cyc_B]
+        aug = bool(self.diffaug)
+        if aug:         # the discriminators judge augmented copies, rows in the stacked pass's order [real_B; fake_B | fake_A; real_A]
+            par = self._diffaug_table(n, shp[1], shp[2], ((Db, 1, 0), (Db, 1, 1), (Da, 0, 1), (Da, 0, 0)))
+            dq_aug = self._stacked("dq_aug", ((4 if quad else 2) * n,) + act_shape, self.dtype)
         if quad:
-            Dq, tDq = Dpf.forward(dq, mq)
+            Dq, tDq = Dpf.forward(K.diffaug(dq, par, C, out=dq_aug) if aug else dq, mq)
             Df, tDf = Dq[n:3 * n], Dpf.slice_tape(tDq, n, 3 * n)
         else:
-            Df, tDf = Dpf.forward(f1, m_ab)                   # [D_B(fake_B | mask_A); D_A(fake_A | mask_B)]
+            Df, tDf = Dpf.forward(K.diffaug(f1, par[n:3 * n], C, out=dq_aug) if aug else f1, m_ab)   # [D_B(fake_B | mask_A); D_A(fake_A | mask_B)]
         wA, wB = K.seg_edge_weight(sA, C), K.seg_edge_weight(sB, C)
 
         crit = K.mse_const if self.use_lsgan else K.bce_logits
@@ -658,7 +720,11 @@ class sggan(object):
             crit(Dq[n:2 * n], 0.0, dl, g_q[n:2 * n], weight=0.5, accumulate_loss=True)
             Dpf.backward(tDq, g_q)
         else:
-            Dr, tDr = Dpr.forward(x1, m_ab)                   # [D_A(real_A | mask_A); D_B(real_B | mask_B)]
+            x1d = x1
+            if aug:
+                x1d = self._stacked("x1_aug", (2 * n,) + act_shape, self.dtype)
+                K.diffaug(x1[lo], par[3 * n:], C, out=x1d[lo]); K.diffaug(x1[hi], par[:n], C, out=x1d[hi])
+            Dr, tDr = Dpr.forward(x1d, m_ab)                  # [D_A(real_A | mask_A); D_B(real_B | mask_B)]
             g_r, g_fk = e(Dr), e(Df)
             crit(Dr[lo], 1.0, dl, g_r[lo], weight=0.5, accumulate_loss=False)
             crit(Df[hi], 0.0, dl, g_fk[hi], weight=0.5, accumulate_loss=True)
@@ -672,7 +738,10 @@ class sggan(object):
         Gab.pair_wgrads = Gba.pair_wgrads = self.pair_wgrads
         # (the gradient joins ride on the first layer's data-gradient store -- ``addend`` -- instead of separate passes)
         d_f = Gp2.backward(t2, d_cyc, want_dx=True, addend=d_f)
-        d_f = Dpf.backward(tDf, g_g, want_dx=True, param_grads=False, addend=d_f)
+        if aug:         # through the transform's adjoint, which takes over the join
+            d_f = K.diffaug_bwd(Dpf.backward(tDf, g_g, want_dx=True, param_grads=False), par[n:3 * n], C, addend=d_f)
+        else:
+            d_f = Dpf.backward(tDf, g_g, want_dx=True, param_grads=False, addend=d_f)
         # second application of both generators: every deferred weight gradient runs inside this pass, and each layer group's
         # all-reduce is launched as soon as the group is complete -- only the last group's exchange has no backward work left
         # to hide behind (the four Adam launches run under it)

@@ -140,6 +140,24 @@ class _ActFn(torch.autograd.Function):
         return K.act_bwd(dy, y, ctx.act, ctx.leak)[..., :ctx.Cr], None, None
 
 
+class _DiffAugmentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params):
+        Cr = x.shape[-1]
+        xp = _padc(x, K.cpad(Cr)).contiguous()
+        par = params.detach().to(torch.float32).contiguous()
+        ctx.Cr = Cr
+        ctx.save_for_backward(par)
+        y = K.diffaug(xp, par, Cr)
+        return y[..., :Cr] if y.shape[-1] != Cr else y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (par,) = ctx.saved_tensors
+        dy = _padc(dy, K.cpad(ctx.Cr)).contiguous()
+        return K.diffaug_bwd(dy, par, ctx.Cr)[..., :ctx.Cr], None
+
+
 _ACTS = {None: A.ACT_NONE, "none": A.ACT_NONE, "relu": A.ACT_RELU, "lrelu": A.ACT_LRELU, "tanh": A.ACT_TANH}
 
 
@@ -171,3 +189,10 @@ def relu(x):
 
 def tanh(x):
     return _ActFn.apply(x, A.ACT_TANH, 0.0)
+
+
+def diff_augment(x, params):
+    """Differentiable augmentation in front of a discriminator (Zhao et al. 2020, colour + cutout): x (N,H,W,C)
+    with C <= 8, params (N,8) f32 rows [b, s, c, y0, x0, ch, cw, 0] (kernels.diffaug_draw fills them on the device).  The
+    transform is affine in x for fixed rows; the gradient w.r.t. x is its adjoint, params get none."""
+    return _DiffAugmentFn.apply(x, params)
