@@ -548,6 +548,47 @@ int sgg_diffaug_fwd(const void* x, void* y, const float* params, int rows, int H
                     void* ws, size_t ws_bytes, void* stream);
 int sgg_diffaug_bwd(const void* dy, const float* params, const void* addend, void* dx, int rows, int H, int W, int C_real,
                     int Cpad, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* ---- sliced Wasserstein distance of Laplacian-pyramid patches (Karras et al. 2018, section 5; the semantics of
+ * PGGAN's metrics/sliced_wasserstein.py [3P-recall]): an unpaired realism score of two image sets.  The sort between
+ * sgg_swd_project and sgg_swd_distance is the caller's.
+ * sgg_swd_pyramid: img (N,H,W,cstride), the first three channels taken as 8-bit colours exactly as sgg_image_quality takes them
+ *   (SGG_U8 with cstride 3 | 4, the byte; SGG_F32 / SGG_BF16 with cstride >= 3, q = (int)(((x + 1.f) * 0.5f) * 255.f) in f32 clamped
+ *   to 0..255, NaN -> 0; cstride = SGG_CPAD with a 16-byte aligned base takes one 16-byte load per pixel).  With t = [1,4,6,4,1]/16
+ *   and the mirror border without edge repeat (index -1 -> 1, n -> n-2):
+ *     G_0 = the image;  G_k = down(G_{k-1}): filter with t (x) t, keep every second row and column starting at 0;
+ *     up(x): Z[2i,2j] = x[i,j], other entries 0, filtered with 4 (t (x) t) under the same mirror rule applied to Z;
+ *     Lap_{k-1} = G_{k-1} - up(G_k),  Lap_{levels-1} = G_{levels-1}.
+ *   pyr: float per image sgg_swd_pyramid_elems(H, W, levels) values, the levels concatenated finest first, each planar
+ *   [3][H >> l][W >> l].  The Gaussian chain lives in ws as double; with 8-bit inputs every intermediate is an exact dyadic
+ *   rational of at most 47 bits (8 per down, 6 for up), so no sum depends on its order and the float store is the one rounding:
+ *   image n of a batch gets the bits of the call on that image alone.  2 * levels launches.
+ *   ws: sgg_swd_pyramid_workspace(N, H, W, levels) bytes, 8-byte aligned; need not be initialised.
+ * sgg_swd_descriptors: rows [(i * patches + p)][147] of desc, float: the 7x7x3 patch of level `level` of image i around
+ *   (cy, cx), flattened (channel, y, x).  cy = 3 + mulhi32(w_y, h - 6), cx = 3 + mulhi32(w_x, w - 6) with h, w the level's size and
+ *   mulhi32(a, b) = ((uint64)a * b) >> 32; the words are Philox4x32-10 (the constants of sgg_diffaug_draw) with key (seed, 1) and
+ *   counter (g, level, p / 2, 0), g = (uint32)(image_offset + i): words 0, 1 are (w_y, w_x) of patch 2 (p / 2), words 2, 3 those of
+ *   patch 2 (p / 2) + 1.  desc points at the first row of this batch inside the set-wide buffer.  One launch.
+ * sgg_swd_project: desc [M][147] -> moments double [3][2] = per colour channel (mean, population standard deviation) over all
+ *   M * 49 values of the channel (the sum, then the sum of squared deviations from the mean: 256-row partials in double, folded in
+ *   index order), and proj double [D][M], proj[d][m] = sum_k z_k dirs[k][d], k ascending, z_k = (desc[m][k] - mean_c) / std_c in
+ *   double, 0 where std_c == 0.  dirs: float [147][D].  Five launches.  ws: sgg_swd_project_workspace(M) bytes, 8-byte aligned.
+ * sgg_swd_distance: sa, sb double [D][M] (each row sorted by the caller) -> out[d] = sum_m |sa[d][m] - sb[d][m]|, double, thread
+ *   t of the row's block takes m = t, t + 256, ..., then a fixed tree.  One launch.
+ * All sums have a fixed order (no floating-point atomics), nothing is allocated, no host sync: every call can be captured.
+ * Before any launch -- SGG_EINVAL: a NULL or misaligned buffer, a bad kind, cstride outside its kind's range, N / patches / M / D
+ *   <= 0, level outside 0..levels-1, a negative image_offset; SGG_EUNSUPPORTED: levels outside 1..5, H or W not divisible by
+ *   2^(levels-1), a coarsest level under 7x7, H*W > 2^22, a grid past the launch limits (more than 21845 images in a pyramid call,
+ *   65535 in a descriptor call); SGG_EWORKSPACE: a short ws.  The size functions return 0 for unsupported shapes. */
+size_t sgg_swd_pyramid_elems(int H, int W, int levels);
+size_t sgg_swd_pyramid_workspace(int N, int H, int W, int levels);
+size_t sgg_swd_project_workspace(int64_t M);
+int sgg_swd_pyramid(const void* img, int kind, int cstride, int N, int H, int W, int levels, float* pyr, void* ws,
+                    size_t ws_bytes, void* stream);
+int sgg_swd_descriptors(const float* pyr, int N, int H, int W, int levels, int level, int patches, uint32_t seed,
+                        int64_t image_offset, float* desc, void* stream);
+int sgg_swd_project(const float* desc, int64_t M, const float* dirs, int D, double* proj, double* moments, void* ws,
+                    size_t ws_bytes, void* stream);
+int sgg_swd_distance(const double* sa, const double* sb, int D, int64_t M, double* out, void* stream);
 /* f32 [P][Cs] -> dtype [P][Cd] with zero fill (Cd >= Cs), and back (drops padded channels). */
 int sgg_pad_channels(const float* src, void* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);
 int sgg_unpad_channels(const void* src, float* dst, int64_t P, int Cs, int Cd, int dtype, void* stream);

@@ -612,6 +612,29 @@ def directory_test_samples(args, cache):
     return gen
 
 
+def directory_images(args, root, split, count, device):
+    """``images()`` yielding the first ``count`` files of ``<root>/<split>`` in sorted order as (H,W,3) float32 in [0,1] at the test
+    size, through the resize of ``directory_test_samples`` -- the unpaired reals of the test pass's SWD.  The
+    files are decoded once and held on the device as uint8."""
+    import torch
+    from . import kernels as K
+    dev = torch.device(device)
+    files = list_files(root, split)[:int(count)]
+    if not files:
+        raise FileNotFoundError(f"no files under {os.path.join(root, split)}")
+    stacks = [torch.as_tensor(np.array(decode(f, "image"))[None]).to(dev) for f in files]       # (a copy: a decoded PNG is read-only)
+
+    def gen():
+        H, W = args.image_height, args.image_width
+        zero = torch.zeros(1, dtype=torch.int32, device=dev)
+        out = torch.empty((1, H, W, K.cpad(3)), dtype=torch.float32, device=dev)
+        for st in stacks:
+            rows, cols = _device_tables(test_tables(st.shape[1], st.shape[2], H, W), dev)
+            K.resample_u8(st, zero, zero, rows, cols, out, 3)
+            yield K.unpad_channels(out, 3)[0].cpu().numpy()
+    return gen
+
+
 def resolve_root(dataset_dir, split="trainA"):
     """The reference reads ``./datasets/<dataset_dir>/<split>`` (model.py:220); a path that holds ``<split>`` itself wins.
     None: neither exists (the caller keeps its synthetic sources)."""

@@ -1103,3 +1103,71 @@ def diffaug_bwd(dy, params, C_real, addend=None, out=None):
     A.check(A.lib().sgg_diffaug_bwd(_p(dy), _p(params), _p(addend), _p(out), rows, H, W, int(C_real), Cp, dt(dy), _p(ws), ws.numel(),
                                     _s()), "diffaug_bwd")
     return out
+
+
+# ----------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
+SWD_K = 147                      # values of a descriptor: a 7x7 patch of three channels, (channel, y, x)
+SWD_CHUNK = 256                  # descriptor rows per partial sum of the statistics (SW_CHUNK, csrc/swd.hip)
+SWD_MAX_LEVELS = 5
+
+
+def swd_default_levels(H, W):
+    """The largest L <= 5 for which H and W divide by 2^(L-1) and min(H, W) >> (L-1) >= 16 (5 at 512x256, 4 at 128x128);
+    0 where even one level is too small."""
+    best = 0
+    for L in range(1, SWD_MAX_LEVELS + 1):
+        if H % (1 << (L - 1)) == 0 and W % (1 << (L - 1)) == 0 and (min(H, W) >> (L - 1)) >= 16:
+            best = L
+    return best
+
+
+def swd_pyramid_elems(H, W, levels):
+    """float32 values of one image's pyramid (levels concatenated, each [3][H >> l][W >> l]); 0: the shape is not supported."""
+    return int(A.lib().sgg_swd_pyramid_elems(int(H), int(W), int(levels)))
+
+
+def swd_pyramid(img, levels, out=None):
+    """sgg_swd_pyramid: a device image (N,H,W,Cs), f32 / bf16 (Cs >= 3, values in [-1,1]) or uint8 (Cs = 3 | 4) -> the Laplacian
+    pyramids (N, swd_pyramid_elems(H, W, levels)) float32 of its 8-bit colours.  2 * levels launches, no sync."""
+    img, kind = _pixel_input(img)
+    N, H, W, Cs = img.shape
+    E = swd_pyramid_elems(H, W, levels)
+    if E == 0:
+        A.check(A.EUNSUPPORTED, f"swd_pyramid {H}x{W}, {levels} levels")
+    out = _out(out, (N, E), torch.float32, img.device)
+    need = int(A.lib().sgg_swd_pyramid_workspace(N, H, W, int(levels)))
+    ws = workspace(need, img.device)
+    A.check(A.lib().sgg_swd_pyramid(_p(img), kind, Cs, N, H, W, int(levels), _p(out), _p(ws), ws.numel(), _s()), "swd_pyramid")
+    return out
+
+
+def swd_descriptors(pyr, H, W, levels, level, patches, seed, image_offset, desc):
+    """sgg_swd_descriptors: the pyramids (N, E) of images image_offset .. image_offset + N -> rows [i * patches + p] of ``desc``
+    (a contiguous (N * patches, 147) float32 slice of the set-wide buffer).  One launch."""
+    N = pyr.shape[0]
+    assert pyr.dtype == torch.float32 and pyr.shape[1] == swd_pyramid_elems(H, W, levels)
+    assert desc.dtype == torch.float32 and tuple(desc.shape) == (N * patches, SWD_K)
+    A.check(A.lib().sgg_swd_descriptors(_p(pyr), N, int(H), int(W), int(levels), int(level), int(patches), int(seed) & 0xffffffff,
+                                        int(image_offset), _p(desc), _s()), "swd_descriptors")
+    return desc
+
+
+def swd_project(desc, dirs, proj=None, moments=None):
+    """sgg_swd_project: desc (M,147) float32, dirs (147,D) float32 -> (proj (D,M) float64, moments (3,2) float64 = per channel
+    mean and population standard deviation).  Five launches, no sync."""
+    M, D = desc.shape[0], dirs.shape[1]
+    assert desc.dtype == torch.float32 and desc.shape[1] == SWD_K and dirs.dtype == torch.float32 and dirs.shape[0] == SWD_K
+    proj = _out(proj, (D, M), torch.float64, desc.device)
+    moments = _out(moments, (3, 2), torch.float64, desc.device)
+    ws = workspace(int(A.lib().sgg_swd_project_workspace(M)), desc.device)
+    A.check(A.lib().sgg_swd_project(_p(desc), M, _p(dirs), D, _p(proj), _p(moments), _p(ws), ws.numel(), _s()), "swd_project")
+    return proj, moments
+
+
+def swd_distance(sa, sb, out=None):
+    """sgg_swd_distance: two (D,M) float64 tensors with sorted rows -> out[d] = sum_m |sa[d][m] - sb[d][m]|, float64 (D,)."""
+    D, M = sa.shape
+    assert sa.dtype == torch.float64 and sb.dtype == torch.float64 and tuple(sb.shape) == (D, M)
+    out = _out(out, (D,), torch.float64, sa.device)
+    A.check(A.lib().sgg_swd_distance(_p(sa), _p(sb), D, M, _p(out), _s()), "swd_distance")
+    return out

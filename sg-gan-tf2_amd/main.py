@@ -109,6 +109,14 @@ def build_parser():
            "'Image PSNR' and 'Image SSIM' scalars (SSIM: 11x11 Gaussian window, sigma 1.5, the mean over the windows inside the "
            "image; computed in double on the GPU); with --cycle also 'Cycle MAE / PSNR / SSIM' of the reconstruction "
            "G_BA(G_AB(x)) against the input; images must be at least 11 pixels high and wide")
+    a("--swd", dest="swd", action="store_true", default=argparse.SUPPRESS,
+      help="test pass: the sliced Wasserstein distance of Laplacian-pyramid patches (Karras et al. 2018) between the translations "
+           "and a set of real images, both taken as 8-bit images: 'SWD <h>x<w>' per pyramid level and 'SWD Mean' scalars "
+           "(x 1e3, lower is closer).  An unpaired score: with --cycle on a dataset directory the reals are the first images "
+           "of testB (else trainB) of domain B, otherwise the label images of the test samples.  The level count is the largest "
+           "L <= 5 for which the test size divides by 2^(L-1) with min(H, W) >> (L-1) >= 16")
+    a("--swd_patches", dest="swd_patches", type=int, default=argparse.SUPPRESS,
+      help="--swd: 7x7 patches drawn per image and pyramid level (default 128)")
     a("--log_dir", dest="log_dir", default="./logs", help="scalar summaries (the reference writes tfevents under logs/<timestamp>/train)")
     return p
 
@@ -188,8 +196,35 @@ def directory_sources(model, args, log=print):
     batches = D.DirectoryBatches(model, args, cache_A, cache_B, augment=augment)
     tests = None
     if os.path.isdir(os.path.join(root, "testA")):
-        tests = D.directory_test_samples(args, class_test_cache(args, root, dev, with_class=bool(getattr(args, "crf", False))))
+        cache = class_test_cache(args, root, dev, with_class=bool(getattr(args, "crf", False)))
+        tests = D.directory_test_samples(args, cache)
+        set_swd_reals(args, dev, len(cache))
     return batches, tests
+
+
+def check_swd(args):
+    """--swd: the test size must give at least one pyramid level."""
+    from .kernels import swd_default_levels
+    if getattr(args, "swd", False) and swd_default_levels(args.image_height, args.image_width) == 0:
+        raise ValueError(f"--swd: {args.image_height}x{args.image_width} gives no pyramid level: the count is the largest L <= 5 for which "
+                         "--img_height and --img_width divide by 2^(L-1) and min(H, W) >> (L-1) >= 16 (a coarsest level under 7x7 "
+                         "could not hold one patch)")
+    if getattr(args, "swd_patches", 128) <= 0:
+        raise ValueError("--swd_patches must be positive")
+
+
+def set_swd_reals(args, device, count):
+    """--swd with --cycle on a dataset directory: ``args.swd_reals`` yields the first ``count`` images, in sorted order, of testB
+    (else trainB) of the domain-B root (--dataset_dir_B, else --dataset_dir), resampled to the test size like the test samples.
+    In every other case it stays unset and the reals are the test samples' label images."""
+    from . import data as D
+    if not (getattr(args, "swd", False) and args.cycle):
+        return
+    for split in ("testB", "trainB"):
+        root_B = D.resolve_root(args.dataset_dir_B or args.dataset_dir, split)
+        if root_B is not None:
+            args.swd_reals = D.directory_images(args, root_B, split, count, device)
+            return
 
 
 def class_test_cache(args, root, device, with_class=False):
@@ -219,6 +254,7 @@ def main(argv=None):
     model.py:263-268), ``--phase test`` the test pass of model.py:535-567 -- on the dataset directory ``--dataset_dir``
     names, or on synthetic data where it names none."""
     args = parse_args(argv)
+    check_swd(args)
     from . import data as D
     from .model import sggan
     from .utils import SummarySink
@@ -229,7 +265,9 @@ def main(argv=None):
     if args.phase == "test":          # main.py:58-60
         root = D.resolve_root(args.dataset_dir, "testA")
         if root is not None:
-            return model.test(args, D.directory_test_samples(args, class_test_cache(args, root, model.device))())
+            cache = class_test_cache(args, root, model.device)
+            set_swd_reals(args, model.device, len(cache))
+            return model.test(args, D.directory_test_samples(args, cache)())
         return model.test(args, synthetic_test_samples(args)())
     sink = SummarySink(os.path.join(getattr(args, "log_dir", "./logs"), "train", "scalars.jsonl"))
     src = directory_sources(model, args)

@@ -19,6 +19,10 @@ Paired image quality (not in the reference): ``image_quality`` giv
 taken as 8-bit colours -- the bytes ``save_images`` writes -- from integer sums and a double-precision SSIM map summed in a
 fixed order on the GPU (csrc/imgqual.hip).  ``scores_image_fake`` keeps the per-image sums of a test pass on the device,
 ``scores_from_quality`` reads them back once and pools them.
+
+Unpaired realism (not in the reference): ``SWD`` / ``sliced_wasserstein`` give the sliced Wasserstein distance of
+Laplacian-pyramid patches (Karras et al. 2018) between a set of fakes and a set of reals, taken as 8-bit colours: pyramid, patch
+gather, normalise-and-project and distance on the GPU (csrc/swd.hip), the sort by ``torch.sort``, one read-back.
 """
 from __future__ import annotations
 
@@ -290,3 +294,104 @@ def scores_from_quality(acc):
     pooled_mse = float(rows[:, 1].sum()) / count
     psnr = 10.0 * np.log10(255.0 ** 2 / pooled_mse) if pooled_mse > 0 else 10.0 * np.log10(255.0 ** 2 * count)
     return {"MAE": float(rows[:, 0].sum()) / count, "PSNR": float(psnr), "SSIM": float(np.mean(per["SSIM"])), "per_image": per}
+
+
+# ----------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
+def swd_directions(D, seed=19):
+    """The (147, D) float32 projection matrix: Gaussian columns from a seeded host generator, scaled to unit length in double."""
+    g = torch.randn((K.SWD_K, int(D)), generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float64)
+    return (g / g.norm(dim=0, keepdim=True)).to(torch.float32).contiguous()
+
+
+class SWD:
+    """Sliced Wasserstein distance of Laplacian-pyramid patches between a set of fakes and a set of reals of H x W, up to
+    ``n_max`` images each, taken as the 8-bit colours ``save_images`` writes.  Per level and image ``patches`` 7x7x3 descriptors
+    at positions keyed by (seed, image index, level, patch) -- image g of either set gets the same positions --, per set and
+    level normalised per colour channel, projected on ``repeats * dirs_per_repeat`` unit directions, sorted, and compared:
+    1e3 * mean |a_sorted - b_sorted|.  ``levels``: None takes kernels.swd_default_levels(H, W).  The descriptors of both sets
+    stay on the device; ``result`` reads back once."""
+
+    def __init__(self, H, W, n_max, patches=128, repeats=4, dirs_per_repeat=128, seed=19, levels=None, device="cuda"):
+        self.H, self.W, self.n_max, self.patches = int(H), int(W), int(n_max), int(patches)
+        self.levels = K.swd_default_levels(self.H, self.W) if levels is None else int(levels)
+        if self.levels == 0:
+            raise ValueError(f"SWD: {self.H}x{self.W} is too small: the level count is the largest L <= {K.SWD_MAX_LEVELS} for which H and W "
+                             "divide by 2^(L-1) and min(H, W) >> (L-1) >= 16, and the coarsest level must hold a 7x7 patch")
+        if K.swd_pyramid_elems(self.H, self.W, self.levels) == 0:
+            raise ValueError(f"SWD: {self.levels} levels at {self.H}x{self.W} are not supported (1..{K.SWD_MAX_LEVELS} levels, H and W "
+                             "divisible by 2^(levels-1), a coarsest level of at least 7x7, H*W <= 2^22)")
+        if self.n_max <= 0 or self.patches <= 0 or repeats <= 0 or dirs_per_repeat <= 0:
+            raise ValueError("SWD: n_max, patches, repeats and dirs_per_repeat must be positive")
+        self.seed, self.repeats, self.dirs_per_repeat = int(seed), int(repeats), int(dirs_per_repeat)
+        self.device = torch.device(device)
+        self.sizes = [(self.H >> l, self.W >> l) for l in range(self.levels)]
+        self.directions = swd_directions(self.repeats * self.dirs_per_repeat, self.seed)
+        # one contiguous (147, dirs_per_repeat) matrix per repeat: a repeat's projections are sorted on their own
+        self._dirs = [self.directions[:, r * self.dirs_per_repeat:(r + 1) * self.dirs_per_repeat].contiguous().to(self.device)
+                      for r in range(self.repeats)]
+        rows = self.n_max * self.patches
+        self._desc = {k: [torch.empty((rows, K.SWD_K), dtype=torch.float32, device=self.device) for _ in range(self.levels)]
+                      for k in ("fakes", "reals")}
+        self.count = {"fakes": 0, "reals": 0}
+
+    def _add(self, which, imgs):
+        t = _image_tensor(imgs).to(self.device)
+        N = t.shape[0]
+        if tuple(t.shape[1:3]) != (self.H, self.W):
+            raise ValueError(f"SWD: image {tuple(t.shape)} where {self.H}x{self.W} was announced")
+        at = self.count[which]
+        if at + N > self.n_max:
+            raise ValueError(f"SWD: more than n_max = {self.n_max} {which}")
+        pyr = K.swd_pyramid(t, self.levels)
+        P = self.patches
+        for l in range(self.levels):
+            K.swd_descriptors(pyr, self.H, self.W, self.levels, l, P, self.seed, at, self._desc[which][l][at * P:(at + N) * P])
+        self.count[which] = at + N
+
+    def add_fakes(self, imgs):
+        self._add("fakes", imgs)
+
+    def add_reals(self, imgs):
+        self._add("reals", imgs)
+
+    def add(self, fakes, reals):
+        self._add("fakes", fakes)
+        self._add("reals", reals)
+
+    def result(self):
+        """{"levels": [(h, w, value) ...] finest first, "mean": value} over the first min(fakes, reals) images of both sets."""
+        import math
+        n = min(self.count.values())
+        if n == 0:
+            raise ValueError("SWD: a set is empty")
+        M, dpr = n * self.patches, self.dirs_per_repeat
+        D = self.repeats * dpr
+        sums = torch.empty((self.levels, D), dtype=torch.float64, device=self.device)
+        pa, pb = (torch.empty((dpr, M), dtype=torch.float64, device=self.device) for _ in range(2))
+        mom = torch.empty((3, 2), dtype=torch.float64, device=self.device)
+        for l in range(self.levels):
+            a, b = self._desc["fakes"][l][:M], self._desc["reals"][l][:M]
+            for r, dirs in enumerate(self._dirs):
+                K.swd_project(a, dirs, pa, mom)
+                K.swd_project(b, dirs, pb, mom)
+                K.swd_distance(torch.sort(pa, dim=1).values, torch.sort(pb, dim=1).values, sums[l, r * dpr:(r + 1) * dpr])
+        host = sums.cpu().numpy()                                            # the one read-back
+        values = [1e3 * math.fsum(host[l]) / (float(D) * float(M)) for l in range(self.levels)]
+        return {"levels": [(h, w, v) for (h, w), v in zip(self.sizes, values)], "mean": math.fsum(values) / len(values)}
+
+
+def sliced_wasserstein(fakes, reals, batch=16, **kw):
+    """The one-shot form of ``SWD``: two image sets (N,H,W,C) as ``SWD.add`` takes them -> ``SWD.result()``."""
+    shape = lambda x: tuple(x.tensor().shape if hasattr(x, "tensor") else x.shape)
+    (nf, H, W), nr = shape(fakes)[:3], shape(reals)[0]
+    s = SWD(H, W, max(nf, nr), **kw)
+    for which, imgs, n in (("fakes", fakes, nf), ("reals", reals, nr)):
+        imgs = imgs.tensor() if hasattr(imgs, "tensor") else imgs
+        for i in range(0, n, batch):
+            s._add(which, imgs[i:i + batch])
+    return s.result()
+
+
+def swd_scalars(res):
+    """[(scalar name, value) ...] of an ``SWD.result()`` in the order the test pass logs them: the levels finest first, the mean."""
+    return [("SWD %dx%d" % (h, w), v) for h, w, v in res["levels"]] + [("SWD Mean", res["mean"])]

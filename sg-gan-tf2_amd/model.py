@@ -34,7 +34,7 @@ def default_args(**over):
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
              crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
-             diffaug_brightness=0.25)
+             diffaug_brightness=0.25, swd=False, swd_patches=128)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -845,7 +845,7 @@ class sggan(object):
             return image, np.expand_dims(M.dense_crf(image[0], lp), axis=0)
         return as_np(test_label).transpose(0, 3, 2, 1), as_np(pred_img).transpose(0, 3, 2, 1)
 
-    def test_during_train(self, epoch, args, samples, sink=None):
+    def test_during_train(self, epoch, args, samples, sink=None, swd_reals=None):
         """model.py:307-448 (the live part; of the CRF variants, commented out there, scores_mask_sample_crf runs with --crf): every
         test sample -- ``samples`` yields (name, sample_image (H,W,3) in [0,1], seg_image (H,W,3) in [0,1]); reading and
         resizing the files (utils.load_test_data) stays on the caller's side -- is rescaled like the reference does
@@ -868,6 +868,11 @@ class sggan(object):
         device and are read back once); 'Image MAE', 'Image PSNR' and 'Image SSIM' follow the scalars above and the returned
         scores gain "Image".  A cycle model also scores the reconstruction ``generator_BA(fake_A)`` against the 8-bit input,
         under the same weights as the translation: 'Cycle MAE', 'Cycle PSNR', 'Cycle SSIM' and "Cycle".
+        With ``args.swd`` every translation also goes, as that 8-bit image, into the fakes of a sliced Wasserstein
+        distance of Laplacian-pyramid patches (metric.SWD, ``args.swd_patches`` descriptors per level and image); the reals are
+        the samples' own 8-bit label images, or, where ``swd_reals`` is given, the (H,W,3) images in [0,1] it yields (a callable
+        is called first), converted like everything else -- an unpaired set, of which as many are used as there are fakes.
+        'SWD <h>x<w>' per pyramid level, finest first, and 'SWD Mean' follow the scalars above; the returned scores gain "SWD".
         A model built with ``ema_decay`` translates with the moving average of the generator's weights
         (ema_weights) and logs 'EMA Decay', the decay its last applied update used, after all the scalars above."""
         from . import metric as M
@@ -887,6 +892,12 @@ class sggan(object):
         image_scores = bool(getattr(args, "image_scores", False))
         image_acc, cycle_acc = [], []
         test_dir = getattr(args, "test_dir", None)
+        swd = None
+        if getattr(args, "swd", False):
+            if not hasattr(samples, "__len__"):     # the set-wide descriptor buffers are sized once
+                samples = list(samples)
+            swd = M.SWD(self.image_height, self.image_width, max(len(samples), 1), patches=int(getattr(args, "swd_patches", 128)),
+                        device=self.device)
         with self._test_weights():                  # (the moving average, where the model keeps one)
             for item in samples:
                 name, sample_image, seg_image = item[:3]
@@ -901,6 +912,10 @@ class sggan(object):
                     M.scores_image_fake(convert_image_dtype_uint8(np.asarray(seg_image)[None]).astype(np.uint8), fake_A, image_acc)
                     if self.cycle:
                         M.scores_image_fake(rescaled.astype(np.uint8), self.generator_BA(fake_A), cycle_acc)
+                if swd is not None:
+                    swd.add_fakes(fake_A)
+                    if swd_reals is None:
+                        swd.add_reals(convert_image_dtype_uint8(np.asarray(seg_image)[None]).astype(np.uint8))
                 lt, lp = M.scores_seg_fake(np.asarray(seg_image, dtype=np.float32)[None], torch.as_tensor(fake_img.astype(np.float32)))   # :373
                 preds += list(lp); gts += list(lt)
                 if crf:
@@ -948,9 +963,26 @@ class sggan(object):
                     sink.scalar(key + " MAE", q["MAE"], epoch)
                     sink.scalar(key + " PSNR", q["PSNR"], epoch)
                     sink.scalar(key + " SSIM", q["SSIM"], epoch)
+        if swd is not None and swd.count["fakes"]:
+            self._swd_add_reals(swd, swd_reals)
+            score["SWD"] = res = swd.result()
+            if sink is not None:
+                for key, value in M.swd_scalars(res):
+                    sink.scalar(key, value, epoch)
         if self.ema_decay is not None and sink is not None:     # the decay the generator's last applied update used
             sink.scalar("EMA Decay", float(self.generator.P._ema_state[0].item()), epoch)
         return (np.concatenate(outputs, axis=0) if outputs else None), score
+
+    @staticmethod
+    def _swd_add_reals(swd, swd_reals):
+        """The unpaired reals of a test pass: (H,W,3) images in [0,1], as many as there are fakes."""
+        from .utils import convert_image_dtype_uint8
+        if swd_reals is None:
+            return
+        for img in (swd_reals() if callable(swd_reals) else swd_reals):
+            if swd.count["reals"] >= swd.count["fakes"]:
+                break
+            swd.add_reals(convert_image_dtype_uint8(np.asarray(img)[None]).astype(np.uint8))
 
     @staticmethod
     def _class_scalars(sink, prefix, s, epoch):
@@ -964,12 +996,20 @@ class sggan(object):
         translation under ``args.test_dir``.  ``samples`` yields (name, sample_image (H,W,3) in [0,1]).  With
         ``args.class_scores`` and samples that carry the one-hot class mask as their fourth element, the four class-level scores
         of the translations are logged at the end; with ``args.image_scores`` and samples that carry their label
-        image as the third element, 'Image MAE / PSNR / SSIM' of the translations against it.  A model built with ``ema_decay`` translates with the moving
+        image as the third element, 'Image MAE / PSNR / SSIM' of the translations against it; with ``args.swd``
+        one line 'SWD <h>x<w>: ... SWD Mean: ...'  against ``args.swd_reals`` (images (H,W,3) in [0,1]) where that is
+        set, else against the label images of the samples that carry one.  A model built with ``ema_decay`` translates with the moving
         average of the generator's weights, as the checkpoint holds it."""
         from . import metric as M
         from .utils import convert_image_dtype_uint8, save_images
         import os
         class_hist, image_acc = None, []
+        swd, swd_reals = None, getattr(args, "swd_reals", None)
+        if getattr(args, "swd", False):
+            if not hasattr(samples, "__len__"):
+                samples = list(samples)
+            swd = M.SWD(self.image_height, self.image_width, max(len(samples), 1), patches=int(getattr(args, "swd_patches", 128)),
+                        device=self.device)
         log(" [*] Running Test ...")
         log(" [*] Load SUCCESS" if self.load(args.checkpoint_dir) else " [!] Load failed...")
         os.makedirs(args.test_dir, exist_ok=True)
@@ -983,6 +1023,10 @@ class sggan(object):
                 save_images(sample_image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(name)))
                 save_images(fake_A, [1, 1], os.path.join(args.test_dir, os.path.basename(name)))
                 out.append(fake_A)
+                if swd is not None:
+                    swd.add_fakes(fake_A)
+                    if swd_reals is None and len(item) >= 3:
+                        swd.add_reals(convert_image_dtype_uint8(np.asarray(item[2])[None]).astype(np.uint8))
                 if getattr(args, "image_scores", False) and len(item) >= 3:
                     M.scores_image_fake(convert_image_dtype_uint8(np.asarray(item[2])[None]).astype(np.uint8), fake_A, image_acc)
                 if getattr(args, "class_scores", False) and len(item) >= 4:
@@ -997,6 +1041,10 @@ class sggan(object):
         if image_acc:
             q = M.scores_from_quality(image_acc)
             log("Image MAE: %f Image PSNR: %f Image SSIM: %f" % (q["MAE"], q["PSNR"], q["SSIM"]))
+        if swd is not None and swd.count["fakes"]:
+            self._swd_add_reals(swd, swd_reals)
+            if swd.count["reals"]:
+                log(" ".join("%s: %f" % kv for kv in M.swd_scalars(swd.result())))
         return out
 
     def train(self, args, batches, log=print, test_samples=None, sink=None):
@@ -1034,7 +1082,9 @@ class sggan(object):
                     log("Epoch: [%2d] [%4d/%4d] time: %4.4f Gen_Loss: %f Disc_Loss: %f " % (epoch, idx, len(data), time.time() - start, gl, dl))
                 # epoch end (model.py:263-268): the test pass + image summary, then the two running-mean loss scalars
                 if test_samples is not None:
-                    fake, _ = self.test_during_train(epoch, args, test_samples(epoch) if callable(test_samples) else test_samples, sink)
+                    extra = {"swd_reals": args.swd_reals} if getattr(args, "swd", False) and getattr(args, "swd_reals", None) is not None else {}
+                    fake, _ = self.test_during_train(epoch, args, test_samples(epoch) if callable(test_samples) else test_samples, sink,
+                                                     **extra)
                     if sink is not None and fake is not None:
                         sink.image("Segmentation Epoch {}".format(epoch), fake, epoch)
                 if sink is not None:
