@@ -221,6 +221,25 @@ int sgg_deconv2d_bwd_data(const sgg_conv_desc* d, const void* dy, const void* w_
 int sgg_deconv2d_bwd_weight(const sgg_conv_desc* d, const void* x, const void* dy, float* dw,
                             int C_real, int K_real, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- route query: which kernel a plain call of this geometry launches (host only: nothing is launched, no device is touched)
+ * The code is computed by the selection functions the launchers themselves switch on.  It names the kernel family and, for
+ * the generic GEMMs, the block tile; SGG_ROUTE_SPLITK is OR-ed in when the GEMM planner splits the reduction (partial slabs
+ * + splitk_reduce_kernel).  "Plain": no addend, no paired weights, no statistics epilogue (an addend moves the data gradient
+ * of HALO_NARROW_IN / HALO_DGRAD_NARROW shapes to the generic GEMM); the weight-gradient query takes C_real <= 4 for an
+ * 8-channel input (S2N's condition -- the image input), as the workspace query does.
+ * op: 0 forward, 1 data gradient, 2 weight gradient.  Returns SGG_EINVAL for a bad descriptor or op. */
+typedef enum {
+    SGG_ROUTE_REG = 1,                 /* register-staged v1 GEMM: lab builds with the DMA kernels switched off only */
+    SGG_ROUTE_HALO3, SGG_ROUTE_S2HALO, SGG_ROUTE_S2N, SGG_ROUTE_N7, SGG_ROUTE_HALO_NARROW_IN, SGG_ROUTE_HALO_FWD,
+    SGG_ROUTE_HALO_DGRAD_NARROW,
+    SGG_ROUTE_GLDS_256x256, SGG_ROUTE_GLDS_256x128, SGG_ROUTE_GLDS_128x128, SGG_ROUTE_GLDS_128x64, SGG_ROUTE_GLDS_256x16,
+    SGG_ROUTE_W7, SGG_ROUTE_HALO_WGRAD, SGG_ROUTE_W9, SGG_ROUTE_W9S, SGG_ROUTE_WGRAD_V2_ROWFAST, SGG_ROUTE_WGRAD_V2,
+    SGG_ROUTE_WGRAD_128x128, SGG_ROUTE_WGRAD_128x64, SGG_ROUTE_WGRAD_128x16,
+    SGG_ROUTE_SPLITK = 256             /* bit 8 */
+} sgg_route;
+int sgg_conv2d_route(const sgg_conv_desc* d, int op);
+int sgg_deconv2d_route(const sgg_conv_desc* d, int op);
+
 /* bias gradient: db[c] (+)= sum_p dy[p][c], c < C_real (f32).  ws >= sgg_bias_grad_workspace(P, C) bytes. */
 size_t sgg_bias_grad_workspace(int64_t P, int C);
 int sgg_bias_grad(const void* dy, float* db, int64_t P, int C, int C_real, int accumulate, int dtype,

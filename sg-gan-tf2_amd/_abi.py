@@ -16,6 +16,20 @@ SGG_F32, SGG_BF16, SGG_U8 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT = 0, 1
 CPAD = 8
+# enum sgg_route (include/sggan.h): the kernel a plain call launches; ROUTE_SPLITK is OR-ed in when the GEMM planner splits K
+ROUTE_NAMES = ("REG", "HALO3", "S2HALO", "S2N", "N7", "HALO_NARROW_IN", "HALO_FWD", "HALO_DGRAD_NARROW",
+               "GLDS_256x256", "GLDS_256x128", "GLDS_128x128", "GLDS_128x64", "GLDS_256x16",
+               "W7", "HALO_WGRAD", "W9", "W9S", "WGRAD_V2_ROWFAST", "WGRAD_V2", "WGRAD_128x128", "WGRAD_128x64", "WGRAD_128x16")
+ROUTE = {n: i + 1 for i, n in enumerate(ROUTE_NAMES)}
+ROUTE_SPLITK = 256
+ROUTE_OP_FWD, ROUTE_OP_DGRAD, ROUTE_OP_WGRAD = 0, 1, 2
+
+
+def route_name(code: int) -> str:
+    """'GLDS_128x128+SPLITK' for a code of sgg_conv2d_route / sgg_deconv2d_route."""
+    if code <= 0:
+        raise SggError(f"route query failed: {code}")
+    return ROUTE_NAMES[(code & 255) - 1] + ("+SPLITK" if code & ROUTE_SPLITK else "")
 
 
 class ConvDesc(C.Structure):
@@ -77,6 +91,8 @@ SIGNATURES = {
     "sgg_deconv2d_bwd_data_workspace": (_sz, [_dp]),
     "sgg_deconv2d_bwd_data": (_i, [_dp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgg_deconv2d_bwd_weight": (_i, [_dp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "sgg_conv2d_route": (_i, [_dp, _i]),
+    "sgg_deconv2d_route": (_i, [_dp, _i]),
     "sgg_bias_grad_workspace": (_sz, [_i64, _i]),
     "sgg_bias_grad": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_bias_grad_group2": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),

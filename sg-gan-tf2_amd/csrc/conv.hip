@@ -3857,12 +3857,10 @@ static bool use_glds() { return sgg_config().glds != 0; }
                                                        // D.h1 forward) gather their pixel operand from HBM with 9 short K-tiles per block;
                                                        // two tiles in flight instead of one: 96.8 -> 93.4 us (c2), 26.4 -> 25.3 us (D.h1)
 #endif
-template <typename T, int MODE>
-static int launch_gemm(const ConvArgs& a, hipStream_t s) {
-    int DC, classes;
-    int64_t Mmax;
-    if (MODE == MODE_FWD) { DC = a.K; classes = 1; Mmax = (int64_t)a.N * a.Ho * a.Wo; }
-    else if (MODE == MODE_BORDER) {
+// rows, result channels and parity classes of the GEMM a launch of `mode` runs
+static void gemm_dims(const ConvArgs& a, int mode, int& DC, int& classes, int64_t& Mmax) {
+    if (mode == MODE_FWD) { DC = a.K; classes = 1; Mmax = (int64_t)a.N * a.Ho * a.Wo; }
+    else if (mode == MODE_BORDER) {
         DC = a.C; classes = 1;
         int p2 = 2 * a.pad_t;
         bool all = a.H <= p2 + 1 || a.W <= p2 + 1;
@@ -3871,6 +3869,38 @@ static int launch_gemm(const ConvArgs& a, hipStream_t s) {
         DC = a.C; classes = a.stride * a.stride;
         Mmax = (int64_t)a.N * ((a.H + a.stride - 1) / a.stride) * ((a.W + a.stride - 1) / a.stride);
     }
+}
+
+// The kernel launch_gemm() runs for these arguments (an sgg_route without the split-K bit): launch_gemm switches on it and
+// sgg_conv2d_route() reports it, so there is one copy of the conditions.
+static int gemm_route(const ConvArgs& a, int mode, bool is_bf16) {
+    if (mode == MODE_BORDER) return SGG_ROUTE_REG;     // few pixels, short K loops: the small register-path tiles
+    if (mode == MODE_DGRAD && s2halo_ok(a, is_bf16)) return SGG_ROUTE_S2HALO;
+    if (halo3_ok(a, mode, is_bf16)) return SGG_ROUTE_HALO3;
+    if (!use_glds()) return SGG_ROUTE_REG;
+    int DC, classes;
+    int64_t Mmax;
+    gemm_dims(a, mode, DC, classes, Mmax);
+    // big square tiles (8 waves, 1 block per CU) when there is enough work to fill the chip with them
+    // (a 4-stage ring of 64-byte K-slices was measured 3-5 % slower on the residual conv and is not built)
+    if (DC >= 256 && Mmax * ((DC + 255) / 256) >= 256 * 160) return SGG_ROUTE_GLDS_256x256;
+    // short reductions (<= 16 K-tiles: the 64-channel stride-2 layers c2 forward / d2 data gradient / D.h1 forward): a
+    // 256x128 block is alone on its CU and spends a third of its life in prologue and epilogue; two 128x128 blocks per
+    // CU cover each other: 93.7 -> 84.4 us (c2), 25.3 -> 22.7 us (D.h1); the 4-wave 128x64 tile (three blocks): 115 us
+    if (DC >= 128 && (mode == MODE_FWD ? a.R * a.S * a.C : a.R * a.S * a.K) <= 1024) return SGG_ROUTE_GLDS_128x128;
+    if (DC >= 128 && Mmax * ((DC + 127) / 128) >= 256 * 160) return SGG_ROUTE_GLDS_256x128;
+    // 128x128 with 8 waves (2 per SIMD, two blocks per CU): the 4-wave variant ran at one wave per SIMD with
+    // nothing to cover its LDS latencies (D.h3 data gradient 86 -> 60 us, D.h2 forward 36 -> 23 us)
+    if (DC >= 128) return SGG_ROUTE_GLDS_128x128;
+    if (DC > 16) return SGG_ROUTE_GLDS_128x64;
+    return SGG_ROUTE_GLDS_256x16;
+}
+
+template <typename T, int MODE>
+static int launch_gemm(const ConvArgs& a, hipStream_t s) {
+    int DC, classes;
+    int64_t Mmax;
+    gemm_dims(a, MODE, DC, classes, Mmax);
     if constexpr (MODE != MODE_BORDER && sizeof(T) == 2) {
         // grouped launch of a shape whose kernel takes a STACKED batch with per-image weights (the LDS-resident 3x3 / stride-2
         // halo kernels): the two groups are contiguous, so it is that kernel on 2N images with the split at N
@@ -3880,11 +3910,13 @@ static int launch_gemm(const ConvArgs& a, hipStream_t s) {
             return launch_gemm<T, MODE>(b, s);
         }
     }
-    if constexpr (MODE == MODE_DGRAD && sizeof(T) == 2) {
-        if (s2halo_ok(a, true)) return launch_s2halo(a, s);
-    }
-    if constexpr (MODE != MODE_BORDER && sizeof(T) == 2) {
-        if (halo3_ok(a, MODE, true)) {
+    const int route = gemm_route(a, MODE, sizeof(T) == 2);
+    switch (route) {
+    case SGG_ROUTE_S2HALO:
+        if constexpr (MODE == MODE_DGRAD && sizeof(T) == 2) return launch_s2halo(a, s);
+        break;
+    case SGG_ROUTE_HALO3:
+        if constexpr (MODE != MODE_BORDER && sizeof(T) == 2) {
             if constexpr (MODE == MODE_DGRAD) {
                 const bool pair = a.wmat2 != nullptr;
                 if (a.stats && (pair || a.dst_f32 || a.addend_f32)) return SGG_EUNSUPPORTED;   // (the norm-backward sums have no paired / mixed form)
@@ -3909,27 +3941,25 @@ static int launch_gemm(const ConvArgs& a, hipStream_t s) {
             }
             return launch_halo3<MODE, false>(a, s);
         }
+        break;
+    case SGG_ROUTE_GLDS_256x256:
+        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 256, 256, 2, 8, 128, 2>(a, Mmax, DC, classes, s);
+        break;
+    case SGG_ROUTE_GLDS_256x128:
+        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 256, 128, 4, 8, 128, GLDS_NS_256x128>(a, Mmax, DC, classes, s);
+        break;
+    case SGG_ROUTE_GLDS_128x128:
+        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, Mmax, DC, classes, s);
+        break;
+    case SGG_ROUTE_GLDS_128x64:
+        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 128, 64, 4, 4>(a, Mmax, DC, classes, s);
+        break;
+    case SGG_ROUTE_GLDS_256x16:
+        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 256, 16, 4, 4>(a, Mmax, DC, classes, s);
+        break;
+    default: break;
     }
-    if constexpr (MODE != MODE_BORDER) {
-        if (use_glds()) {
-            // big square tiles (8 waves, 1 block per CU) when there is enough work to fill the chip with them
-            // (a 4-stage ring of 64-byte K-slices was measured 3-5 % slower on the residual conv and is not built)
-            if (DC >= 256 && Mmax * ((DC + 255) / 256) >= 256 * 160)
-                return launch_glds_cfg<T, MODE, 256, 256, 2, 8, 128, 2>(a, Mmax, DC, classes, s);
-            // short reductions (<= 16 K-tiles: the 64-channel stride-2 layers c2 forward / d2 data gradient / D.h1 forward): a
-            // 256x128 block is alone on its CU and spends a third of its life in prologue and epilogue; two 128x128 blocks per
-            // CU cover each other: 93.7 -> 84.4 us (c2), 25.3 -> 22.7 us (D.h1); the 4-wave 128x64 tile (three blocks): 115 us
-            if (DC >= 128 && (MODE == MODE_FWD ? a.R * a.S * a.C : a.R * a.S * a.K) <= 1024)
-                return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, Mmax, DC, classes, s);
-            if (DC >= 128 && Mmax * ((DC + 127) / 128) >= 256 * 160)
-                return launch_glds_cfg<T, MODE, 256, 128, 4, 8, 128, GLDS_NS_256x128>(a, Mmax, DC, classes, s);
-            // 128x128 with 8 waves (2 per SIMD, two blocks per CU): the 4-wave variant ran at one wave per SIMD with
-            // nothing to cover its LDS latencies (D.h3 data gradient 86 -> 60 us, D.h2 forward 36 -> 23 us)
-            if (DC >= 128) return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, Mmax, DC, classes, s);
-            if (DC > 16) return launch_glds_cfg<T, MODE, 128, 64, 4, 4>(a, Mmax, DC, classes, s);
-            return launch_glds_cfg<T, MODE, 256, 16, 4, 4>(a, Mmax, DC, classes, s);
-        }
-    }
+    if (route != SGG_ROUTE_REG) return SGG_EUNSUPPORTED;   // (a route this instantiation has no kernel for: gemm_route never returns one)
     if constexpr (MODE == MODE_BORDER) {               // few pixels, short K loops: small tiles for parallelism
         if (DC >= 128) return launch_gemm_cfg<T, MODE, 64, 128, 2>(a, Mmax, DC, classes, s);
         if (DC > 16) return launch_gemm_cfg<T, MODE, 64, 64, 2>(a, Mmax, DC, classes, s);
@@ -3981,6 +4011,14 @@ static int run_gemm(const sgg_conv_desc* d, ConvArgs a, void* ws, size_t ws_byte
     hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(blocks, a.grp), dim3(256), 0, s, (const float*)ws, a.bias, a.addend, a.dst, nvec4, g.DC, g.ksplit,
                        g.pdst * g.DC, a.act, a.leak, SplitKGroup{a.bias2, a.net_part, a.net_dst, a.net_add});
     return sgg_check_launch();
+}
+
+// the route of a plain run_gemm() call: plan_gemm()'s split factor, then launch_gemm()'s choice for the arguments it is given
+static int run_gemm_route(const sgg_conv_desc* d, int mode) {
+    const GemmPlan g = plan_gemm(d, mode);
+    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
+    if (g.ksplit > 1) a.ksplit = g.ksplit;
+    return gemm_route(a, mode, d->dtype == SGG_BF16) | (g.ksplit > 1 ? SGG_ROUTE_SPLITK : 0);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -4408,6 +4446,24 @@ static int wgrad_splits(const sgg_conv_desc* d) {
     return (int)sp;
 }
 
+// The kernel run_wgrad() launches (an sgg_route): run_wgrad switches on it and sgg_conv2d_route() reports it.  Cr: the
+// real input channel count (the vector-ALU kernel of the 8-channel stride-2 layer holds four channels per pixel).
+static int wgrad_route(const sgg_conv_desc* d, int Cr) {
+    const bool bf = d->dtype == SGG_BF16;
+    if (bf && use_glds() && (w7_head_ok(d) || w7_stem_ok(d))) return SGG_ROUTE_W7;   // the two 7x7 layers with a 3-channel side
+    if (halo_wgrad_ok(d)) return SGG_ROUTE_HALO_WGRAD;
+    if (bf && w9_ok(d)) return SGG_ROUTE_W9;             // 3x3 s1: x halo resident, all taps per block
+    if (bf && w9s_ok(d)) return SGG_ROUTE_W9S;           // 3x3 s2: the same with a parity-de-interleaved halo
+    if (bf && s2n_wgrad_ok(d) && Cr <= 4) return SGG_ROUTE_S2N;   // D.h0: the vector-ALU kernel, one slab per block
+    if (wgrad_use_v2(d)) {
+        const int bkp = bf ? 64 : 32;                    // pixels per stage (BKP in the kernel)
+        return sgg_config().wgrad_rowfast && d->Wo % bkp == 0 ? SGG_ROUTE_WGRAD_V2_ROWFAST : SGG_ROUTE_WGRAD_V2;
+    }
+    if (d->K >= 128) return SGG_ROUTE_WGRAD_128x128;
+    if (d->K > 16) return SGG_ROUTE_WGRAD_128x64;
+    return SGG_ROUTE_WGRAD_128x16;
+}
+
 struct W9Net { const void* x; const void* dy; const void* x2; const void* dy2; float* dw; };
 // one network (nb == nullptr), or two networks of the same layer shape sharing the launch: each gets half the splits
 static int run_w9(const sgg_conv_desc* d, const W9Net& na, const W9Net* nb, int Cr, int Kr, int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
@@ -4447,14 +4503,15 @@ static int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, floa
     a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.Ho = d->Ho; a.Wo = d->Wo; a.reflect = d->pad_mode == SGG_PAD_REFLECT;
     a.P = d->N * d->Ho * d->Wo;
     a.xb = a.x; a.dyb = a.dy; a.splits_per_net = 1 << 30;
+    const int route = wgrad_route(d, Cr);
     if constexpr (sizeof(T) == 2) {                     // the two 7x7 layers with a 3-channel side
-        if (use_glds() && (w7_head_ok(d) || w7_stem_ok(d))) {
+        if (route == SGG_ROUTE_W7) {
             const bool stem = !w7_head_ok(d);
             int rc7 = run_w7(d, stem, x, dy, dw, Cr, Kr, accumulate, ws, ws_bytes, s);
             return (rc7 || !xb) ? rc7 : run_w7(d, stem, xb, dyb, dwb, Cr, Kr, accumulate, ws, ws_bytes, s);
         }
     }
-    if (halo_wgrad_ok(d)) {
+    if (route == SGG_ROUTE_HALO_WGRAD) {
         const int nb = halo_wgrad_blocks(d), ntiles = d->N * (d->H / HALO_TH) * (d->W / HALO_TW);
         size_t need = (size_t)nb * d->R * d->S * d->C * d->K * sizeof(float);
         if (ws_bytes < need * nets || !ws) return SGG_EWORKSPACE;
@@ -4475,7 +4532,7 @@ static int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, floa
         return sgg_check_launch();
     }
     if constexpr (sizeof(T) == 2) {
-        if (w9_ok(d)) {                                   // 3x3 s1: x halo resident, all taps per block
+        if (route == SGG_ROUTE_W9) {                      // 3x3 s1: x halo resident, all taps per block
             if (!xb) return run_w9(d, W9Net{x, dy, nullptr, nullptr, dw}, nullptr, Cr, Kr, accumulate, ws, ws_bytes, s);
             // two networks (grouped call): one launch, half the blocks and half the split slabs per network -- as for the stride-2
             // shapes below, the slabs are the kernel's main traffic (D.h3: 75 MB written + read per network); the result equals
@@ -4485,7 +4542,7 @@ static int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, floa
             int rc9 = run_w9(d, W9Net{x, dy, nullptr, nullptr, dw}, nullptr, Cr, Kr, accumulate, ws, ws_bytes, s);
             return rc9 ? rc9 : run_w9(d, second, nullptr, Cr, Kr, accumulate, ws, ws_bytes, s);
         }
-        if (w9s_ok(d)) {                                  // 3x3 s2: the same with a parity-de-interleaved halo
+        if (route == SGG_ROUTE_W9S) {                     // 3x3 s2: the same with a parity-de-interleaved halo
             // Two networks (grouped call): ONE launch of the single call's grid in which each network gets half the blocks, i.e.
             // half the slabs.  The split slabs are this kernel's main cost next to the operands -- 75 MB written and 75 MB read
             // again per network at the generator's four stride-2 layers, for 67 MB of x and dy -- so the two-launch form of the
@@ -4517,10 +4574,11 @@ static int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, floa
         }
     }
     int splits = wgrad_splits(d);
-    const bool s2n = sizeof(T) == 2 && s2n_wgrad_ok(d) && Cr <= 4;   // D.h0: the vector-ALU kernel, one slab per block
+    const bool s2n = route == SGG_ROUTE_S2N;                         // D.h0: the vector-ALU kernel, one slab per block
+    const bool v2 = route == SGG_ROUTE_WGRAD_V2_ROWFAST || route == SGG_ROUTE_WGRAD_V2;
     // grouped call of the LDS-DMA kernel: one launch, half the splits (= slabs: 8 MB each at D.h31) per network -- see the stride-2
     // halo branch above; equal to two single calls up to f32 summation order
-    const bool merged = xb && !s2n && wgrad_use_v2(d) && splits >= 2;
+    const bool merged = xb && v2 && splits >= 2;
     if (merged) splits /= 2;
     a.pix_per_split = (int)align_up((size_t)((a.P + splits - 1) / splits), 64);
     if (!s2n) splits = (a.P + a.pix_per_split - 1) / a.pix_per_split;
@@ -4531,20 +4589,24 @@ static int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, floa
     if (merged) { a.xb = (const char*)xb; a.dyb = (const char*)dyb; a.splits_per_net = splits; }
     for (int net = 0; net < (merged ? 1 : nets) && rc == SGG_OK; ++net) {
     if (net) { a.x = (const char*)xb; a.dy = (const char*)dyb; a.ws = (float*)((char*)ws + need); }
-    if (s2n) rc = launch_s2n_wgrad(d, a.x, a.dy, a.ws, Cr, s);
-    else if (wgrad_use_v2(d)) {
+    switch (route) {
+    case SGG_ROUTE_S2N: rc = launch_s2n_wgrad(d, a.x, a.dy, a.ws, Cr, s); break;
+    case SGG_ROUTE_WGRAD_V2_ROWFAST:
+    case SGG_ROUTE_WGRAD_V2: {
         constexpr size_t lds = 2 * 2 * (size_t)(sizeof(T) == 2 ? 64 : 32) * 256 * sizeof(T);
         SGG_LDS_ATTR((conv_wgrad_glds_kernel<T, false>), lds);
         SGG_LDS_ATTR((conv_wgrad_glds_kernel<T, true>), lds);
         dim3 grid((unsigned)(((d->R * d->S * d->C + 255) / 256) * ((d->K + 255) / 256) * splits * (merged ? 2 : 1)));
-        const int bkp = sizeof(T) == 2 ? 64 : 32;                      // pixels per stage (BKP in the kernel)
-        const int rf = sgg_config().wgrad_rowfast;
-        if (rf && d->Wo % bkp == 0) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, true>), grid, dim3(512), lds, s, a);
+        if (route == SGG_ROUTE_WGRAD_V2_ROWFAST) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, true>), grid, dim3(512), lds, s, a);
         else hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, false>), grid, dim3(512), lds, s, a);
         rc = sgg_check_launch();
-    } else if (d->K >= 128) rc = launch_wgrad_cfg<T, 128, 128, 2>(a, splits, s);
-    else if (d->K > 16) rc = launch_wgrad_cfg<T, 128, 64, 4>(a, splits, s);
-    else rc = launch_wgrad_cfg<T, 128, 16, 4>(a, splits, s);
+        break;
+    }
+    case SGG_ROUTE_WGRAD_128x128: rc = launch_wgrad_cfg<T, 128, 128, 2>(a, splits, s); break;
+    case SGG_ROUTE_WGRAD_128x64: rc = launch_wgrad_cfg<T, 128, 64, 4>(a, splits, s); break;
+    case SGG_ROUTE_WGRAD_128x16: rc = launch_wgrad_cfg<T, 128, 16, 4>(a, splits, s); break;
+    default: rc = SGG_EUNSUPPORTED; break;               // (wgrad_route returns nothing else once the branches above have returned)
+    }
     }
     if (rc) return rc;
     if (s2n) {
@@ -4557,6 +4619,23 @@ static int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, floa
     int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)ws, dw, d->R * d->S, d->C, d->K, Cr, Kr, splits, accumulate, dwb);
     return sgg_check_launch();
+}
+
+// Kernels taken AHEAD of the GEMM planner by sgg_conv2d_fwd / conv2d_bwd_data_impl (an sgg_route), 0: run_gemm() decides
+// (run_gemm_route).  The launchers switch on these; sgg_conv2d_route() reports them.
+static int conv_fwd_head_route(const sgg_conv_desc* d) {
+    if (halo_narrow_in_ok(d, d->C, d->K)) return SGG_ROUTE_HALO_NARROW_IN;   // narrow input (stem): halo + whole weight matrix resident in LDS
+    if (use_glds() && n7_fwd_ok(d)) return SGG_ROUTE_N7;                     // the 7x7 head: (channel, tap column) in the GEMM N dimension
+    if (use_glds() && halo_fwd_ok(d)) return SGG_ROUTE_HALO_FWD;             // narrow output at full resolution: input halo resident in LDS
+    return 0;
+}
+// addend: a skip gradient is joined in the epilogue; stats: the norm-backward sums are wanted
+static int conv_dgrad_head_route(const sgg_conv_desc* d, bool addend, bool stats) {
+    if (!addend && halo_narrow_in_ok(d, d->K, d->C)) return SGG_ROUTE_HALO_NARROW_IN;   // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
+    if (!stats && s2n_dgrad_ok(d)) return SGG_ROUTE_S2N;
+    if (!stats && use_glds() && n7_dgrad_ok(d)) return SGG_ROUTE_N7;         // (addend: joined in the fold pass, before its one rounding)
+    if (!addend && halo_dgrad_narrow_ok(d)) return SGG_ROUTE_HALO_DGRAD_NARROW;
+    return 0;
 }
 
 extern "C" {
@@ -4618,19 +4697,35 @@ int sgg_conv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const f
                    void* ws, size_t ws_bytes, void* stream) {
     if (!desc_ok(d) || !x || !w || !y) return SGG_EINVAL;
     ConvArgs a = make_args(d, x, w, bias, y, act, leak);
-    if (halo_narrow_in_ok(d, d->C, d->K))               // narrow input (stem): halo + whole weight matrix resident in LDS
+    switch (conv_fwd_head_route(d)) {
+    case SGG_ROUTE_HALO_NARROW_IN:
         return d->dtype == SGG_BF16 ? launch_halo_narrow_in<bf16>(d, a, 0, (hipStream_t)stream) : launch_halo_narrow_in<float>(d, a, 0, (hipStream_t)stream);
-    if (use_glds() && n7_fwd_ok(d)) {                    // the 7x7 head: (channel, tap column) in the GEMM N dimension
+    case SGG_ROUTE_N7: {
         N7Args q;
         q.src = (const char*)x; q.wmat = (const char*)w; q.bias = bias; q.dst = y;
         q.N = d->N; q.H = d->H; q.W = d->W; q.Ho = d->Ho; q.Wo = d->Wo; q.pt = 3; q.pl = 3; q.K = 3;
         q.reflect = d->pad_mode == SGG_PAD_REFLECT; q.flip = 0; q.act = act; q.leak = leak; q.dst_f32 = 0;
         return launch_n7(q, (hipStream_t)stream);
     }
-    if (use_glds() && halo_fwd_ok(d))                   // narrow output at full resolution: input halo resident in LDS
+    case SGG_ROUTE_HALO_FWD:
         return d->dtype == SGG_BF16 ? launch_halo_fwd<bf16>(d, a, (hipStream_t)stream) : launch_halo_fwd<float>(d, a, (hipStream_t)stream);
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    default:
+        return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
+                                    : run_gemm<float, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    }
+}
+
+int sgg_conv2d_route(const sgg_conv_desc* d, int op) {
+    if (!desc_ok(d) || op < 0 || op > 2) return SGG_EINVAL;
+    if (op == 2) return wgrad_route(d, 4);   // C_real <= 4 assumed where it matters (S2N), see include/sggan.h
+    const int head = op == 0 ? conv_fwd_head_route(d) : conv_dgrad_head_route(d, false, false);
+    return head ? head : run_gemm_route(d, op == 0 ? MODE_FWD : MODE_DGRAD);
+}
+// a transposed conv runs the conv's data-gradient GEMM forwards and its forward GEMM backwards, without the conv entry points' special kernels
+int sgg_deconv2d_route(const sgg_conv_desc* d, int op) {
+    if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || op < 0 || op > 2) return SGG_EINVAL;
+    if (op == 2) return wgrad_route(d, 4);   // C_real <= 4 assumed where it matters (S2N), see include/sggan.h
+    return run_gemm_route(d, op == 0 ? MODE_DGRAD : MODE_FWD);
 }
 
 // Pixel chunks per image of the (sum, sumsq) rows sgg_conv2d_fwd_stats() emits; 0 = this shape has no such epilogue
@@ -4681,14 +4776,16 @@ static int conv2d_bwd_data_impl(const sgg_conv_desc* d, const void* dy, const vo
         a.stats = nb->partial; a.nx = (const char*)nb->nx; a.nstats = nb->nstats; a.ngamma = nb->ngamma; a.nbeta = nb->nbeta;
         a.nact = nb->nact; a.nleak = nb->nleak;
     } else nb = nullptr;                                 // from here on `nb` means: norm-backward sums wanted
-    if (!addend && halo_narrow_in_ok(d, d->K, d->C)) {  // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
+    const int head = conv_dgrad_head_route(d, addend != nullptr, nb != nullptr);
+    switch (head) {
+    case SGG_ROUTE_HALO_NARROW_IN: {                     // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
         int rc0 = d->dtype == SGG_BF16 ? launch_halo_narrow_in<bf16>(d, a, 1, (hipStream_t)stream) : launch_halo_narrow_in<float>(d, a, 1, (hipStream_t)stream);
         if (rc0 || !a.reflect) return rc0;
         // REFLECT: add the mirrored (MirrorPadGrad) terms of the border pixels with the small register-path launch
         return d->dtype == SGG_BF16 ? launch_gemm<bf16, MODE_BORDER>(a, (hipStream_t)stream) : launch_gemm<float, MODE_BORDER>(a, (hipStream_t)stream);
     }
-    if (!nb && s2n_dgrad_ok(d)) return launch_s2n_dgrad(d, dy, w, nullptr, 0, addend, dx, (hipStream_t)stream);
-    if (!nb && use_glds() && n7_dgrad_ok(d)) {            // (addend: joined in the fold pass, before its one rounding)
+    case SGG_ROUTE_S2N: return launch_s2n_dgrad(d, dy, w, nullptr, 0, addend, dx, (hipStream_t)stream);
+    case SGG_ROUTE_N7: {                                 // (addend: joined in the fold pass, before its one rounding)
         // the stem: data gradient on the PADDED grid (a zero-padded "full" correlation of dy with the mirrored taps, f32),
         // then MirrorPadGrad as a fold of the 3-pixel frame onto the image -- one rounding, no separate border GEMM
         if (!ws || ws_bytes < n7_dgrad_ws(d)) return SGG_EWORKSPACE;
@@ -4703,12 +4800,14 @@ static int conv2d_bwd_data_impl(const sgg_conv_desc* d, const void* dy, const vo
         hipLaunchKernelGGL(pad3_fold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f32x4*)ws, (const char*)addend, (char*)dx, d->N, d->H, d->W);
         return sgg_check_launch();
     }
-    if (!addend && halo_dgrad_narrow_ok(d)) {
+    case SGG_ROUTE_HALO_DGRAD_NARROW: {
         ConvArgs h = a;                                  // the same computation written as a forward conv over dy
         h.C = d->K; h.K = d->C; h.reflect = 0;
         int rc0 = d->dtype == SGG_BF16 ? launch_halo_fwd<bf16>(d, h, (hipStream_t)stream, 1) : launch_halo_fwd<float>(d, h, (hipStream_t)stream, 1);
         if (rc0 || !a.reflect) return rc0;
         return d->dtype == SGG_BF16 ? launch_gemm<bf16, MODE_BORDER>(a, (hipStream_t)stream) : launch_gemm<float, MODE_BORDER>(a, (hipStream_t)stream);
+    }
+    default: break;                                      // the GEMM planner decides (run_gemm)
     }
     const size_t fb = fold_bytes(d);
     if (fb) {

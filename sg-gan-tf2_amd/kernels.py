@@ -93,7 +93,8 @@ def same_pads(n_in: int, k: int, s: int):
 
 class ConvGeom:
     """Geometry of one Conv2D / Conv2DTranspose call site, resolved to an sgg_conv_desc."""
-    __slots__ = ("desc", "x_shape", "y_shape", "ws_wgrad", "ws_dgrad", "ws_fwd", "dtype", "is_deconv", "stats_chunks", "wgrad_pair", "bwd_stats_chunks", "dgrad_mixed", "pair_ok", "normload_ok")
+    __slots__ = ("desc", "x_shape", "y_shape", "ws_wgrad", "ws_dgrad", "ws_fwd", "dtype", "is_deconv", "stats_chunks", "wgrad_pair", "bwd_stats_chunks", "dgrad_mixed", "pair_ok", "normload_ok",
+                 "route_fwd", "route_dgrad", "route_wgrad")
 
     def __init__(self, desc, x_shape, y_shape, dtype, is_deconv):
         self.desc, self.x_shape, self.y_shape, self.dtype, self.is_deconv = desc, x_shape, y_shape, dtype, is_deconv
@@ -113,6 +114,9 @@ class ConvGeom:
         # workspaces of the two GEMM directions; a deconv runs the conv's data-gradient kernel forwards
         self.ws_fwd = int((L.sgg_deconv2d_fwd_workspace if is_deconv else L.sgg_conv2d_fwd_workspace)(C.byref(desc)))
         self.ws_dgrad = int((L.sgg_deconv2d_bwd_data_workspace if is_deconv else L.sgg_conv2d_bwd_data_workspace)(C.byref(desc)))
+        # the kernel each plain call launches (A.route_name: 'HALO3', 'GLDS_128x128+SPLITK', ...), from the launchers' own selection code
+        route = L.sgg_deconv2d_route if is_deconv else L.sgg_conv2d_route
+        self.route_fwd, self.route_dgrad, self.route_wgrad = (int(route(C.byref(desc), op)) for op in (A.ROUTE_OP_FWD, A.ROUTE_OP_DGRAD, A.ROUTE_OP_WGRAD))
         if self.ws_wgrad == 0:
             raise A.SggError(f"invalid convolution geometry {[(f, getattr(desc, f)) for f, _ in desc._fields_]}")
 

@@ -1,0 +1,218 @@
+"""The convolution edge-case table shared by test_conv_edges_cpu.py (routes, exactness bounds, sensitivity -- no GPU) and
+test_gpu_conv_edges.py (bit-exact parity on the device), with the integer oracle and the exact comparison they both use.
+
+Every row is the smallest shape at which one route's index arithmetic can go wrong: a ragged last M tile, a channel tail
+of one 8-channel granule, an odd parity class, the minimum a predicate admits and the first shape on either side of it.
+Each row names the kernel every op runs on (sgg_conv2d_route / sgg_deconv2d_route, the code the launchers switch on), so
+a threshold edit that moves a row to another kernel fails the CPU suite instead of silently un-testing the kernel.
+
+Operands are drawn from {-1, 0, 1} (bias from [-2, 2]): every product and every partial sum in any order is an exact
+integer, y and dx stay within bf16's exact-integer range (|v| <= 256) and dw / db below 2^24, so NO rounding rule enters
+and any difference from the float64 oracle is an indexing bug.  The tolerance of test_gpu_ops.py (2e-2 of the tensor's
+maximum in bf16) cannot see what stays below 2 % of the maximum: a whole missing input channel of the 1x1 row at Cin = 512
+(1.6 %), one tap's share of a channel at Cin = 264 (a third of the 5.6 % the nine taps reach together), a handful of wrong
+pixels; the exact comparison sees each (test_conv_edges_cpu.py::test_exact_comparison_sees_what_the_bf16_tolerance_misses).
+"""
+import functools
+import zlib
+from types import SimpleNamespace as NS
+
+import numpy as np
+import torch
+
+from oracle import sggan_oracle as O
+
+DTYPES = {"bf16": torch.bfloat16, "f32": torch.float32}
+
+# (name, kind, R, stride, padding, Cin, Cout, N, H, W, {dtype: (forward, data-gradient, weight-gradient route)})
+# deconv rows: H, W are the transposed conv's INPUT size.  Padding LEAD-1: zero padding with a LEADING pad of 1 and no trailing
+# one -- a descriptor the library accepts and Keras 'SAME' never produces at an even size; run through kernels.py directly.
+# The dtype set of a row is the key set of its route dict: the bf16-only kernel families run in bf16 alone (their f32 shapes
+# take the generic routes other rows pin).  A comment above a row belongs to that row.
+ROWS = [
+    # generic GEMM tiles
+    # Mmax 20806: last M tile 70 rows, second channel tile 8 columns, ktot_max 3; dgrad: 256x16 with the same ragged M
+    ("glds_256x256_fwd_ragged", "conv", 3, 1, "SAME", 16, 264, 2, 101, 103, {"bf16": ("GLDS_256x256", "GLDS_256x16+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_256x256", "GLDS_256x16+SPLITK", "WGRAD_128x128")}),
+    # the 256x256 tile on the data-gradient side
+    ("glds_256x256_dgrad", "conv", 3, 1, "SAME", 264, 16, 2, 101, 103, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16"), "f32": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16")}),
+    # stride 2: four parity classes of unequal size (102x103, 102x102, 101x103, 101x102)
+    ("glds_256x256_dgrad_s2", "conv", 3, 2, "SAME", 264, 16, 2, 203, 205, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16"), "f32": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16")}),
+    # M tail 109, channel tail 8, 324 blocks: not split
+    ("glds_256x128_3stage", "conv", 3, 1, "SAME", 120, 392, 1, 79, 131, {"bf16": ("GLDS_256x128", "GLDS_128x64+SPLITK", "WGRAD_V2"), "f32": ("GLDS_256x128", "GLDS_128x64+SPLITK", "WGRAD_V2")}),
+    # 194 blocks: the in-kernel epilogue of a long reduction, not split
+    ("glds_128x128_long_k", "conv", 3, 1, "SAME", 120, 136, 1, 100, 123, {"bf16": ("GLDS_128x128", "GLDS_128x64", "WGRAD_128x128"), "f32": ("GLDS_128x128", "GLDS_128x64", "WGRAD_128x128")}),
+    # forward split: DC 40, K-tiles 22 (bf16) / 43 (f32) over 5 / 10 splits
+    ("splitk_fwd_dc40", "conv", 3, 1, "SAME", 152, 34, 1, 7, 9, {"bf16": ("GLDS_128x64+SPLITK", "GLDS_128x128", "WGRAD_128x64"), "f32": ("GLDS_128x64+SPLITK", "GLDS_128x128", "WGRAD_128x64")}),
+    # data gradient split: DC 40
+    ("splitk_dgrad_dc40", "conv", 3, 1, "SAME", 34, 152, 1, 7, 9, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_128x128")}),
+    # forward split: DC 264 (two full 128 tiles + 8), K-tiles 22 / 43 over 5 / 10
+    ("splitk_fwd_dc264", "conv", 3, 1, "SAME", 152, 264, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_V2"), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_V2")}),
+    # data gradient split: DC 264
+    ("splitk_dgrad_dc264", "conv", 3, 1, "SAME", 264, 152, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128")}),
+    # 1x1 window: one product per input channel (the sensitivity check's Cin >= 256 case); f32: 16 K-tiles over 4 splits
+    ("pointwise_c512", "conv", 1, 1, "SAME", 512, 136, 1, 8, 9, {"bf16": ("GLDS_128x128", "GLDS_128x128", "WGRAD_128x128"), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128", "WGRAD_128x128")}),
+    # halo3: forward and data gradient, bf16
+    ("halo3_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64")}),   # H = 4: the fold's virtual rows dy[2]+dy[0] and dy[H-3]+dy[H-1] overlap
+    ("halo3_min_same", "conv", 3, 1, "SAME", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64")}),
+    # odd batch, two column tiles, destination tail of 8 in the second 256 tile
+    ("halo3_n3_dtail_reflect", "conv", 3, 1, "REFLECT-1", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),
+    ("halo3_n3_dtail_same", "conv", 3, 1, "SAME", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),
+    # the destination tail on the data-gradient side (forward: 264 source channels, outside)
+    ("halo3_dgrad_dtail_reflect", "conv", 3, 1, "REFLECT-1", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_128x64")}),
+    ("halo3_dgrad_dtail_same", "conv", 3, 1, "SAME", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_128x64")}),
+    ("halo3_out_h5", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 5, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: odd H
+    ("halo3_out_h2_reflect", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 2, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: H = 2 < 4 (w9 admits it)
+    ("halo3_out_h2_same", "conv", 3, 1, "SAME", 64, 64, 1, 2, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),
+    ("halo3_out_w120", "conv", 3, 1, "SAME", 64, 64, 1, 4, 120, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: W one granule short of the tile
+    ("halo3_out_w136", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 4, 136, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: W one granule past the tile
+    ("halo3_out_c72", "conv", 3, 1, "REFLECT-1", 72, 72, 1, 4, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: 72 source channels in both directions
+    # s2halo: stride-2 data gradient / transposed conv forward, bf16
+    ("s2halo_min", "conv", 3, 2, "SAME", 64, 64, 1, 16, 64, {"bf16": ("GLDS_128x64", "S2HALO", "WGRAD_128x64")}),   # one 8 x 32 tile of dy
+    ("s2halo_min_deconv", "deconv", 3, 2, "SAME", 64, 64, 1, 8, 32, {"bf16": ("S2HALO", "GLDS_128x64", "WGRAD_128x64")}),   # the same geometry as a transposed conv forward
+    ("s2halo_out_ho12", "conv", 3, 2, "SAME", 64, 64, 1, 24, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: Ho = 12
+    ("s2halo_out_odd_h", "conv", 3, 2, "SAME", 64, 64, 1, 15, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: odd H (leading pad 1)
+    ("s2halo_out_c72", "conv", 3, 2, "SAME", 72, 72, 1, 16, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: 72 channels
+    # s2n: 3(8) -> 64 stride 2, data and weight gradient
+    ("s2n_wo5", "conv", 3, 2, "SAME", 3, 64, 1, 6, 10, {"bf16": ("GLDS_128x64", "S2N", "S2N"), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64")}),   # Wo = 5: less than one 16-pixel item
+    ("s2n_wo130", "conv", 3, 2, "SAME", 3, 64, 3, 4, 260, {"bf16": ("GLDS_128x64", "S2N", "S2N"), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64")}),   # Wo = 130: one 128-pixel segment plus 2
+    # 7x7 head / stem, 5x5 narrow output
+    ("head7_min", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 8, 8, {"bf16": ("N7", "GLDS_128x64", "W7")}),   # the n7 minimum
+    ("head7_ragged", "conv", 7, 1, "REFLECT-3", 64, 3, 2, 9, 65, {"bf16": ("N7", "GLDS_128x64", "W7")}),   # one row and one column past an 8 x 64 tile
+    ("head7_16x32", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 16, 32, {"bf16": ("N7", "HALO_NARROW_IN", "W7"), "f32": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD")}),
+    ("head7_out_7x9", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 7, 9, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16")}),   # outside: H < 8
+    # HALO_NARROW_IN forward, n7 data gradient
+    ("stem7_16x32", "conv", 7, 1, "REFLECT-3", 3, 64, 1, 16, 32, {"bf16": ("HALO_NARROW_IN", "N7", "W7"), "f32": ("HALO_NARROW_IN", "HALO_DGRAD_NARROW", "WGRAD_128x64")}),
+    ("stem7_17x33", "conv", 7, 1, "REFLECT-3", 3, 64, 1, 17, 33, {"bf16": ("GLDS_128x64", "N7", "W7")}),   # generic forward, n7 data gradient
+    ("stem7_min", "conv", 7, 1, "REFLECT-3", 3, 64, 2, 8, 8, {"bf16": ("GLDS_128x64", "N7", "W7")}),
+    # narrow output: HALO_FWD, HALO_WGRAD
+    ("narrow5_16x32", "conv", 5, 1, "SAME", 64, 8, 1, 16, 32, {"bf16": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD"), "f32": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD")}),
+    ("narrow5_17x32", "conv", 5, 1, "SAME", 64, 8, 1, 17, 32, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16")}),   # the same one row taller: generic
+    # narrow input: HALO_DGRAD_NARROW (the 64 -> 8 shape's data gradient is taken by HALO_NARROW_IN first)
+    ("narrow5_in16_16x32", "conv", 5, 1, "SAME", 16, 64, 1, 16, 32, {"bf16": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64"), "f32": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64")}),
+    ("narrow5_in16_17x32", "conv", 5, 1, "SAME", 16, 64, 1, 17, 32, {"bf16": ("GLDS_128x64", "GLDS_256x16+SPLITK", "WGRAD_128x64")}),   # one row taller: generic
+    # weight gradients
+    ("w9_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9")}),   # H = 2: row -1 mirrors to 1 and row 2 to 0
+    ("w9_min_same", "conv", 3, 1, "SAME", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9")}),
+    # 70 tiles over 35 splits; the odd split count has no two-network launch
+    ("w9_odd_splits", "conv", 3, 1, "REFLECT-1", 64, 128, 5, 4, 448, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9")}),
+    ("w9_out_odd_h", "conv", 3, 1, "SAME", 64, 256, 2, 5, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),   # outside: odd H -> the row-fast DMA kernel with zero padding
+    ("w9s_min", "conv", 3, 2, "SAME", 64, 128, 1, 2, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S")}),   # one output row
+    ("w9s_lead_pad", "conv", 3, 2, "LEAD-1", 64, 128, 1, 2, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S")}),   # pad_t = pad_l = 1 with H = 2 Ho: the halo's leading zero row / column
+    ("rowfast_valid", "conv", 3, 1, "VALID", 64, 256, 2, 6, 66, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),   # Wo = 64 on VALID padding
+    ("rowfast_7x7", "conv", 7, 1, "REFLECT-3", 8, 256, 1, 8, 64, {"bf16": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_V2_ROWFAST")}),   # row-fast on a 7x7 window
+    # f32 stages 32 pixels: row-fast at Wo = 32 (bf16: the gather form), odd H
+    ("rowfast_f32_wo32", "conv", 3, 1, "SAME", 32, 256, 2, 5, 32, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2"), "f32": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),
+    ("wgrad_v2_wo63", "conv", 3, 1, "SAME", 64, 256, 1, 4, 63, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2")}),   # gather form, one pixel short of a stage row
+    ("wgrad_v2_wo65", "conv", 3, 1, "SAME", 64, 256, 1, 4, 65, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2")}),   # gather form, one pixel past
+    # Cr 3 of 8 stored, K tail 8
+    ("wgrad_128x128_cr3", "conv", 3, 1, "SAME", 3, 136, 1, 9, 11, {"bf16": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_128x128")}),
+    ("wgrad_128x64_cr3", "conv", 3, 2, "VALID", 3, 24, 1, 9, 11, {"bf16": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64"), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64")}),   # Cr 3 of 8 stored
+    ("wgrad_128x16_kr3", "conv", 3, 1, "SAME", 24, 3, 1, 9, 11, {"bf16": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x16"), "f32": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x16")}),   # Kr 3 of 8 stored
+    # transposed conv
+    # outside s2halo: odd sizes, channel tails
+    ("deconv_ragged", "deconv", 3, 2, "SAME", 24, 40, 2, 5, 7, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64"), "f32": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),
+]
+# Rows whose dx passes bf16's exact-integer range: 49 taps x 256 output channels of +-1 products have a standard deviation of 75,
+# so no draw keeps 4000 of them within 256.  The row is there for its weight gradient; its dx (at most 2^24: exact in f32 in any
+# order) is compared after the ONE round-to-nearest-even to bf16 of store(), as test_gpu_exact.py compares the bench layers'.
+DX_ROUNDS_ONCE = {"rowfast_7x7"}
+ROW_IDS = [r[0] for r in ROWS]
+BY_NAME = {r[0]: r for r in ROWS}
+CASES = [(r, dt) for r in ROWS for dt in r[10]]                         # one row's dtypes adjacent: its oracle is evaluated once
+CASE_IDS = [f"{r[0]}-{dt}" for r, dt in CASES]
+
+
+def parse_padding(padding):
+    return ("VALID", int(padding.split("-")[1])) if padding.startswith("REFLECT") else (padding, 0)
+
+
+def geom(row, dtype):
+    """The ConvGeom ops.conv2d / ops.deconv2d resolve this row to (host only)."""
+    from sggan_amd import kernels as K
+    _, kind, R, stride, padding, Ci, Co, N, H, W, _ = row
+    if kind == "deconv":
+        return K.deconv_geom(N, H, W, K.cpad(Ci), K.cpad(Co), R, R, stride, DTYPES[dtype])
+    if padding == "LEAD-1":
+        from sggan_amd import _abi as A
+        Ho, Wo = (H + 1 - R) // stride + 1, (W + 1 - R) // stride + 1
+        d = A.ConvDesc(N, H, W, K.cpad(Ci), K.cpad(Co), R, R, stride, 1, 1, Ho, Wo, A.PAD_ZERO, K.dt(DTYPES[dtype]))
+        return K.ConvGeom(d, (N, H, W, K.cpad(Ci)), (N, Ho, Wo, K.cpad(Co)), DTYPES[dtype], False)
+    pad, refl = parse_padding(padding)
+    return K.conv_geom(N, H, W, K.cpad(Ci), K.cpad(Co), R, R, stride, pad, refl, DTYPES[dtype])
+
+
+def routes(g):
+    from sggan_amd import _abi as A
+    return tuple(A.route_name(c) for c in (g.route_fwd, g.route_dgrad, g.route_wgrad))
+
+
+def ints(rng, shape, lo=-1, hi=1):
+    return rng.integers(lo, hi + 1, shape).astype(np.float64)
+
+
+def inputs(row):
+    """x, b, w of a row, seeded by its name; w in the Keras layout (conv HWIO, transposed conv (kh, kw, out, in))."""
+    name, kind, R, _, _, Ci, Co, N, H, W, _ = row
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    x = ints(rng, (N, H, W, Ci))
+    b = ints(rng, (Co,), -2, 2)
+    w = ints(rng, (R, R, Ci, Co) if kind == "conv" else (R, R, Co, Ci))
+    return rng, x, b, w
+
+
+def run_oracle(row, x, b, w, rng=None, dy=None):
+    """Float64 oracle of the layer and its three gradients.  Per image where the im2col matrix would pass 0.5 GB (a convolution
+    has no cross-image term; dw / db are sums over images, exact in integers).  dy: drawn from rng where not given."""
+    _, kind, R, stride, padding, Ci, Co, N, H, W, _ = row
+    lead = padding == "LEAD-1"                            # explicit zero pad of 1 on top and left only: a VALID conv of the padded input
+    pad, refl = ("VALID", 0) if lead else parse_padding(padding)
+    if lead:
+        x = np.pad(x, ((0, 0), (1, 0), (1, 0), (0, 0)))
+    ho, wo = (-(-H // stride), -(-W // stride)) if kind == "conv" else (H, W)
+    chunk = N if N * ho * wo * R * R * Ci * 8 <= (1 << 29) else 1
+    ys, dxs, dys, dw, db = [], [], [], 0.0, 0.0
+    for n0 in range(0, N, chunk):
+        t = O.Tape()
+        vx, vb, vw = O.Var(x[n0:n0 + chunk]), O.Var(b), O.Var(w)
+        yk = O.conv2d(t, vx, vw, vb, stride, pad, refl) if kind == "conv" else O.deconv2d(t, vx, vw, vb, stride)
+        dyk = ints(rng, yk.v.shape) if dy is None else dy[n0:n0 + chunk]
+        t.backward([(yk, dyk)])
+        ys.append(yk.v); dxs.append(vx.g); dys.append(dyk)
+        dw, db = dw + vw.g, db + vb.g
+        del t, vx, yk
+    dx = np.concatenate(dxs)
+    return NS(y=np.concatenate(ys), dx=np.ascontiguousarray(dx[:, 1:, 1:]) if lead else dx, dw=dw, db=db, dy=np.concatenate(dys))
+
+
+@functools.lru_cache(maxsize=2)
+def expected(name):
+    """Inputs and exact results of a row: evaluated once, shared by the tests of the row, never written to."""
+    row = BY_NAME[name]
+    rng, x, b, w = inputs(row)
+    e = run_oracle(row, x, b, w, rng)
+    e.x, e.b, e.w = x, b, w
+    for a in vars(e).values():
+        a.setflags(write=False)
+    return e
+
+
+def store(a, dtype):
+    """What an exact real-valued result looks like after ONE round-to-nearest-even to the storage dtype."""
+    return torch.tensor(np.asarray(a, np.float64)).to(torch.float32).to(dtype).to(torch.float64).numpy()
+
+
+def mismatch(got, exp):
+    """The exact comparison: None where got equals exp element for element, else a description of the first difference."""
+    got = got.detach().to(torch.float64).cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
+    if got.shape != exp.shape:
+        return f"shape {got.shape}, expected {exp.shape}"
+    bad = got != exp
+    if not bad.any():
+        return None
+    return f"{int(bad.sum())} of {bad.size} elements differ, first at {np.argwhere(bad)[0].tolist()} " \
+           f"(got {got[bad][0]}, expected {exp[bad][0]}); max |diff| {np.abs(got - exp).max()}"
+
+
+def same(got, exp, what):
+    m = mismatch(got, exp)
+    assert m is None, f"{what}: {m}"

@@ -1,0 +1,164 @@
+"""Bit-exact parity of the convolution kernels at the route, tile and tail edges of tests/conv_edge_cases.py.
+
+test_gpu_exact.py pins the kernels at the bench workload's shapes, where every extent is a multiple of every tile;
+test_conv2d_fwd_bwd (test_gpu_ops.py) runs small and ragged shapes with a tolerance of 2e-2 of the tensor's maximum.  Here
+the integer technique of the first runs at the smallest shapes where each route's index arithmetic can go wrong, and every
+case asserts the route its shape takes (the CPU suite asserts the same: a threshold edit cannot move a row unnoticed).
+Operands in {-1, 0, 1}: y and dx are exact integers within bf16's range, dw and db within f32's, so any difference from
+the float64 oracle is an indexing bug, not a precision question."""
+import numpy as np
+import pytest
+import torch
+
+from tests import conv_edge_cases as E
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def sg():
+    import sggan_amd
+    import sggan_amd.kernels  # noqa: F401
+    return sggan_amd
+
+
+def dev(a, dtype=torch.float32):
+    return torch.tensor(np.asarray(a, np.float32)).to("cuda").to(dtype)
+
+
+def padc(a, cp):
+    """Zero channel padding to the stored channel count."""
+    a = np.asarray(a)
+    return a if a.shape[-1] == cp else np.concatenate([a, np.zeros(a.shape[:-1] + (cp - a.shape[-1],))], axis=-1)
+
+
+def operands(sg, row, dtype, e):
+    """The stored form of a row's tensors for the kernels.py launchers: channel-padded activations, packed weights, padded bias."""
+    K = sg.kernels
+    g = E.geom(row, dtype)
+    dt = E.DTYPES[dtype]
+    xc, yc = g.x_shape[3], g.y_shape[3]
+    if g.is_deconv:                                      # w (kh, kw, out, in) is the HWIO kernel of the equivalent conv
+        wf, wd = K.pack_weights(dev(e.w), yc, xc, dt)
+    else:
+        wf, wd = K.pack_weights(dev(e.w), xc, yc, dt)
+    return g, dev(padc(e.x, xc), dt), dev(padc(e.dy, yc), dt), wf, wd, dev(padc(e.b, yc))
+
+
+class Guarded:
+    """A tensor inside a larger buffer filled with a sentinel: the bytes before and after it must survive the launch."""
+    G = 4096
+
+    def __init__(self, shape, dtype, fill=None):
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        self.n = n
+        self.buf = torch.full((2 * self.G + n,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.t = self.buf[self.G:self.G + n].view(dtype).view(shape)
+        if fill is not None:
+            self.t.fill_(fill)
+
+    def check(self, what):
+        assert bool((self.buf[:self.G] == 0xA5).all()), f"{what}: bytes before the tensor were written"
+        assert bool((self.buf[self.G + self.n:] == 0xA5).all()), f"{what}: bytes after the tensor were written"
+
+
+@pytest.mark.parametrize("row,dtype", E.CASES, ids=E.CASE_IDS)
+def test_edge_row_fwd_bwd_bit_exact(sg, row, dtype):
+    name, kind, R, stride, padding = row[:5]
+    dt = E.DTYPES[dtype]
+    g = E.geom(row, dtype)
+    assert E.routes(g) == row[10][dtype]                 # on this device's library too: a lab build or a config difference cannot hide a moved shape
+    e = E.expected(name)
+    tag = f"{name}[{dtype}] {row[10][dtype]}"
+    if padding == "LEAD-1":                              # no Keras padding gives this descriptor: the launchers of kernels.py directly
+        K = sg.kernels
+        g, x, dy, wf, wd, b = operands(sg, row, dtype, e)
+        Cr, Kr = e.w.shape[2], e.w.shape[3]
+        E.same(K.conv_fwd(g, x, wf, b), E.store(padc(e.y, g.y_shape[3]), dt), tag + " y")
+        E.same(K.conv_dgrad(g, dy, wd), E.store(padc(e.dx, g.x_shape[3]), dt), tag + " dx")
+        dw = torch.empty((R, R, Cr, Kr), dtype=torch.float32, device="cuda")
+        K.conv_wgrad(g, x, dy, dw)
+        E.same(dw, e.dw, tag + " dw")
+        db = torch.empty(Kr, dtype=torch.float32, device="cuda")
+        K.bias_grad(dy, db)
+        E.same(db, e.db, tag + " db")
+        return
+    tx = dev(e.x, dt).requires_grad_(True)
+    tw = dev(e.w).requires_grad_(True)
+    tb = dev(e.b).requires_grad_(True)
+    ty = sg.conv2d(tx, tw, tb, stride=stride, padding=padding) if kind == "conv" else sg.deconv2d(tx, tw, tb, stride=stride)
+    E.same(ty, E.store(e.y, dt), tag + " y")
+    ty.backward(dev(e.dy, dt))
+    E.same(tx.grad, E.store(e.dx, dt), tag + " dx")
+    E.same(tw.grad, e.dw, tag + " dw")
+    E.same(tb.grad, e.db, tag + " db")
+
+
+# Rows run through kernels.py for the fused forms of their routes -- forward + activation, data gradient + addend, weight
+# gradient accumulated onto dw -- with every result inside sentinel guard cells: the ragged (or minimum) row of each family.
+FUSED = ["glds_256x256_fwd_ragged", "glds_256x256_dgrad", "glds_256x128_3stage", "splitk_fwd_dc40", "splitk_dgrad_dc40",
+         "splitk_fwd_dc264", "splitk_dgrad_dc264", "halo3_min_reflect", "halo3_n3_dtail_same", "halo3_dgrad_dtail_reflect",
+         "s2halo_min", "s2halo_min_deconv", "s2n_wo130", "head7_ragged", "stem7_16x32", "stem7_17x33", "narrow5_16x32",
+         "narrow5_in16_16x32", "w9_min_reflect", "w9_odd_splits", "w9s_min", "rowfast_valid", "rowfast_f32_wo32", "wgrad_v2_wo65",
+         "wgrad_128x128_cr3", "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged"]
+FUSED_CASES = [(E.BY_NAME[n], dt) for n in FUSED for dt in E.BY_NAME[n][10]]
+
+
+@pytest.mark.parametrize("row,dtype", FUSED_CASES, ids=[f"{r[0]}-{dt}" for r, dt in FUSED_CASES])
+def test_edge_row_fused_forms_in_guard_cells(sg, row, dtype):
+    from sggan_amd import _abi as A
+    K = sg.kernels
+    name, R = row[0], row[2]
+    dt = E.DTYPES[dtype]
+    e = E.expected(name)
+    g, x, dy, wf, wd, b = operands(sg, row, dtype, e)
+    tag = f"{name}[{dtype}]"
+    xc, yc = g.x_shape[3], g.y_shape[3]
+    fwd = (lambda act, leak, out: K.deconv_fwd(g, x, wd, b, act, leak, out=out)) if g.is_deconv else \
+          (lambda act, leak, out: K.conv_fwd(g, x, wf, b, act, leak, out=out))
+    yp = padc(e.y, yc)
+    for act, leak, f in ((A.ACT_NONE, 0.0, lambda v: v), (A.ACT_RELU, 0.0, lambda v: np.maximum(v, 0.0)),
+                         (A.ACT_LRELU, 0.5, lambda v: np.where(v > 0, v, 0.5 * v))):     # halves of integers: exact in f32, one rounding to bf16
+        y = Guarded(g.y_shape, dt)
+        fwd(act, leak, y.t)
+        E.same(y.t, E.store(f(yp), dt), f"{tag} y act {act}")
+        y.check(f"{tag} y act {act}")
+    # data gradient, plain and with an addend joined in the epilogue (conv only: the transposed conv has no such form)
+    dxp = padc(e.dx, xc)
+    dx = Guarded(g.x_shape, dt)
+    if g.is_deconv:
+        K.deconv_dgrad(g, dy, wf, out=dx.t)
+    else:
+        K.conv_dgrad(g, dy, wd, out=dx.t)
+    E.same(dx.t, E.store(dxp, dt), tag + " dx")
+    dx.check(tag + " dx")
+    if not g.is_deconv:
+        rng = np.random.default_rng(len(name))
+        add = padc(E.ints(rng, e.x.shape, -3, 3), xc)    # (padding channels are zero in every stored tensor)
+        dx = Guarded(g.x_shape, dt)
+        K.conv_dgrad(g, dy, wd, dev(add, dt), out=dx.t)
+        E.same(dx.t, E.store(dxp + add, dt), tag + " dx + addend")
+        dx.check(tag + " dx + addend")
+    # weight gradient written, then accumulated onto an integer-valued dw
+    wshape = tuple(e.w.shape)
+    for accumulate, base in ((False, 0.0), (True, 5.0)):
+        dw = Guarded(wshape, torch.float32, fill=base if accumulate else None)
+        (K.deconv_wgrad if g.is_deconv else K.conv_wgrad)(g, x, dy, dw.t, accumulate=accumulate)
+        E.same(dw.t, e.dw + base, f"{tag} dw accumulate={accumulate}")
+        dw.check(f"{tag} dw accumulate={accumulate}")
+
+
+def test_odd_split_count_has_no_two_network_weight_gradient(sg):
+    """w9_odd_splits: 70 pixel tiles over 35 splits.  The two-network launch gives each network half the splits, so an odd
+    count has no such form: conv_wgrad_pair2 reports it and launches nothing."""
+    K = sg.kernels
+    row = E.BY_NAME["w9_odd_splits"]
+    e = E.expected(row[0])
+    g, x, dy, _, _, _ = operands(sg, row, "bf16", e)
+    assert g.wgrad_pair and g.ws_wgrad // (9 * 64 * 128 * 4) == 35          # one f32 slab of dW per split
+    dwa = torch.full(tuple(e.w.shape), 3.0, device="cuda")
+    dwb = torch.full(tuple(e.w.shape), -7.0, device="cuda")
+    assert K.conv_wgrad_pair2(g, (x, dy, x, dy, dwa), (x, dy, x, dy, dwb)) is False
+    assert bool((dwa == 3.0).all()) and bool((dwb == -7.0).all())
+    K.conv_wgrad_pair(g, x, dy, x, dy, dwa, accumulate=True)                  # the one-network pair form does exist
+    E.same(dwa, 2 * e.dw + 3.0, "w9_odd_splits pair")
