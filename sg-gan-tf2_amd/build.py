@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsggan.so")
-SOURCES = ["conv.hip", "norm.hip", "misc.hip", "resample.hip", "warp.hip", "crf.hip", "evalseg.hip", "imgqual.hip", "diffaug.hip", "swd.hip"]
+SOURCES = ["conv_halo3.hip", "conv.hip", "norm.hip", "misc.hip", "resample.hip", "warp.hip", "crf.hip", "evalseg.hip", "imgqual.hip", "diffaug.hip", "swd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-Wno-inline-asm"]
 
 
@@ -52,7 +52,7 @@ def build_lib(force=False, verbose=False, lab=False, variant=None, defines=()):
                 sys.stderr.write(r.stderr[-4000:])
         return obj
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+    with ThreadPoolExecutor(max_workers=min(16, len(SOURCES))) as ex:
         objs = list(ex.map(cc, SOURCES))
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT, *objs], check=True)
     return OUT

@@ -1,0 +1,69 @@
+// conv_internal.h -- what the conv translation units (conv.hip, conv_halo3.hip) share; only they include it.  Every kernel is
+// defined and launched in exactly one of them; what crosses files is the plain host functions declared at the end.
+#pragma once
+#include <type_traits>
+#include "common.h"
+#include <stdlib.h>
+
+#ifdef SGG_LAB
+#define SGG_ABLATE_OF(a) ((a).ablate)
+#else
+#define SGG_ABLATE_OF(a) 0      // the shipped kernels carry no ablation branches
+#endif
+
+enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_BORDER = 2 };   // BORDER: dgrad of the REFLECT border pixels only
+
+struct ConvArgs {
+    const char* src;     // FWD: x (N,H,W,C)    DGRAD: dy (N,Ho,Wo,K)
+    const char* wmat;    // FWD: [K][R*S*C]     DGRAD: [C][R*S*K]
+    const float* bias;   // per destination channel or nullptr
+    char* dst;           // FWD: y (N,Ho,Wo,K)  DGRAD: dx (N,H,W,C)
+    const char* addend;  // optional tensor added to the result (same layout as dst): the skip-connection gradient
+    const char* fold;    // REFLECT DGRAD (v2): pre-folded gather rows of the border pixels [pixel][tap][K], else nullptr
+    float* stats;        // halo 3x3 kernels only: per-(image, pixel chunk, channel) partial sums for the instance norm next to
+                         // the conv, [N][chunks][DC][2] f32; nullptr = not wanted.  Forward: (sum, sumsq) of the output.
+                         // Data gradient: (sum g, sum g*xhat) of the norm backward that consumes dx, which needs:
+    const char* nx;      //   that norm's input (same shape as dst)
+    const float* nstats; //   its (mean, rstd)[N][DC]
+    const float* ngamma; //   gamma, beta [DC]
+    const float* nbeta;
+    int nact; float nleak;   // and the activation fused behind it
+    // Forward, "normalise on load" (NORM variant of the halo 3x3 kernel): src is the RAW output of the conv before the instance
+    // norm in front of this conv; the kernel applies relu(x * A + B) (A = gamma * rstd, B = beta - mean * A, from nstats /
+    // ngamma / nbeta; second network of a pair: ngamma2 / nbeta2) to the landed halo rows in LDS and writes the normalised
+    // tensor -- which the backward pass needs as this conv's weight-gradient operand -- to nout on the way.
+    char* nout;
+    const float* ngamma2;
+    const float* nbeta2;
+    float* partial;      // split-K (v2): f32 slabs [ksplit][pdst][DC]
+    int ksplit;          // 1 = no split
+    const char* wmat2;   // halo 3x3 kernels, two networks on one stacked batch: images >= nsplit use wmat2 / bias2
+    const float* bias2;
+    int nsplit;          //   (INT_MAX: one network)
+    // Generic GEMM kernel, GROUPED launch of two networks' call sites of one shape (sgg_*_group2): grp = 2 doubles the grid's z
+    // dimension; the second group reads / writes at these byte offsets from the pointers above and uses wmat2 / bias2.  Each
+    // group is exactly the single-network launch (same tiles, same split-K), so results are bit-identical to two launches.
+    int grp;
+    size_t net_src, net_dst, net_add, net_part;
+    int dst_f32;         // halo 3x3 data gradient, mixed mode: dst is f32 (the gradient chain between instance norms keeps f32)
+    int addend_f32;      //   ... and so is the addend
+    int ablate;          // lab build only (SGG_ABLATE; always 0 and compiled out otherwise): 1 no in-loop DMA, 2 no LDS reads/MFMAs, 3 = 1 + no barrier,
+                         // 5 prologue + epilogue only, 6 prologue only (results in DESIGN.md section 7)
+    size_t pdst;         // destination pixels (slab stride)
+    int N, H, W, C, K, R, S, stride, pad_t, pad_l, Ho, Wo, reflect;
+    int act;
+    float leak;
+};
+
+// 16 zero bytes that out-of-range DMA lanes read instead of branching.  Internal linkage, one copy per file that uses it: the
+// library is built without relocatable device code, so a device global cannot be shared across translation units.
+static __device__ __attribute__((aligned(16))) uint32_t g_zero_page[4] = {0u, 0u, 0u, 0u};
+
+// SGG_CONV_IMPL=reg selects the v1 register-staged kernels (kept for A/B runs); default = v2 direct-to-LDS
+static inline bool use_glds() { return sgg_config().glds != 0; }
+
+// ---- conv_halo3.hip: the LDS-resident 3x3 stride-1 GEMM
+bool halo3_ok(const ConvArgs& a, int mode, bool is_bf16);
+int launch_halo3(const ConvArgs& a, int mode, hipStream_t s);                          // picks FOLD / STATS / PAIR / SRC from the arguments
+size_t halo3_stats_chunks(const sgg_conv_desc* d);                                     // statistics rows per image: one per (2 x 128 tile, tile row)
+int halo3_norm_maxc();                                                                 // most source channels "normalise on load" takes

@@ -2,14 +2,15 @@
 
 The 8-wave kernels run at 2 waves/SIMD, i.e. a 256-VGPR budget they use almost completely; a source change that tips
 one of them into scratch spills costs 2-5x at run time without failing any numerical test (seen while developing the
-all-taps weight-gradient kernel).  This test recompiles csrc/conv.hip with -Rpass-analysis=kernel-resource-usage and
-requires zero VGPR spills and the expected occupancy for the production configurations.
+all-taps weight-gradient kernel).  This test recompiles the conv sources of build.SOURCES with -Rpass-analysis=kernel-resource-usage
+and requires zero VGPR spills and the expected occupancy for the production configurations, and one owner file per kernel.
 """
 import os
 import re
 import shutil
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
@@ -48,13 +49,20 @@ def test_gemm_kernels_do_not_spill(tmp_path):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not (os.path.exists(hipcc) or shutil.which(hipcc)):
         pytest.skip("hipcc not available")
-    src = os.path.join(B.CSRC, "conv.hip")
-    r = subprocess.run([hipcc, *B.FLAGS, "-c", src, "-o", str(tmp_path / "conv.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    srcs = [s for s in B.SOURCES if s.startswith("conv")]
+    assert "conv.hip" in srcs and len(srcs) > 1, srcs
+    with ThreadPoolExecutor(max_workers=min(16, len(srcs))) as ex:
+        runs = list(ex.map(lambda s: subprocess.run([hipcc, *B.FLAGS, "-c", os.path.join(B.CSRC, s), "-o", str(tmp_path / (s + ".o")),
+                                                     "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True), srcs))
+    owner = {}
+    for s, r in zip(srcs, runs):
+        assert r.returncode == 0, f"{s}: {r.stderr[-2000:]}"
+        for n in re.findall(r"Function Name: (\S+)", r.stderr):
+            assert owner.setdefault(n, s) == s, f"device function {n} is built by {owner[n]} and by {s}"
+    merged = "\n".join(r.stderr for r in runs)
     # remarks come in blocks: "Function Name: X", ..., "VGPRs Spill: N", ..., "Occupancy [waves/SIMD]: M"
     usage, name = {}, None
-    for line in r.stderr.splitlines():
+    for line in merged.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             name = m.group(1)
