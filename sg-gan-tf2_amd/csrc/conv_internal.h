@@ -1,5 +1,5 @@
-// conv_internal.h -- what the conv translation units (conv.hip, conv_halo3.hip) share; only they include it.  Every kernel is
-// defined and launched in exactly one of them; what crosses files is the plain host functions declared at the end.
+// conv_internal.h -- what the conv translation units (conv.hip, conv_halo3.hip, conv_wgrad.hip) share; only they include it.
+// Every kernel is defined and launched in exactly one of them; what crosses files is the plain host functions declared at the end.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -62,8 +62,39 @@ static __device__ __attribute__((aligned(16))) uint32_t g_zero_page[4] = {0u, 0u
 // SGG_CONV_IMPL=reg selects the v1 register-staged kernels (kept for A/B runs); default = v2 direct-to-LDS
 static inline bool use_glds() { return sgg_config().glds != 0; }
 
+// output tile and largest window of the kernels that keep a narrow layer's input halo in LDS (forward, narrow input, weight gradient)
+#define HALO_TH 16
+#define HALO_TW 32
+#define HALO_MAXR 7
+
+// The two 7x7 layers with a 3-channel side (bf16), each shape stated once: the head's forward and the stem's data gradient run
+// conv7_narrow_out_kernel (conv.hip), both weight gradients wgrad7_kernel (conv_wgrad.hip).
+static inline bool conv7_head_ok(const sgg_conv_desc* d) {      // 64 -> <= 3 (stored 8), 7x7, pad 3
+    return sgg_config().n7 && d->dtype == SGG_BF16 && d->R == 7 && d->S == 7 && d->stride == 1 && d->C == 64 && d->K == 8 &&
+           d->Ho == d->H && d->Wo == d->W && d->pad_t == 3 && d->pad_l == 3 && d->H >= 8 && d->W >= 8;
+}
+static inline bool conv7_stem_ok(const sgg_conv_desc* d) {      // <= 3 (stored 8) -> 64, 7x7, REFLECT 3
+    return sgg_config().n7 && d->dtype == SGG_BF16 && d->R == 7 && d->S == 7 && d->stride == 1 && d->C == 8 && d->K == 64 &&
+           d->Ho == d->H && d->Wo == d->W && d->pad_t == 3 && d->pad_l == 3 && d->pad_mode == SGG_PAD_REFLECT && d->H >= 8 && d->W >= 8;
+}
+
 // ---- conv_halo3.hip: the LDS-resident 3x3 stride-1 GEMM
 bool halo3_ok(const ConvArgs& a, int mode, bool is_bf16);
 int launch_halo3(const ConvArgs& a, int mode, hipStream_t s);                          // picks FOLD / STATS / PAIR / SRC from the arguments
 size_t halo3_stats_chunks(const sgg_conv_desc* d);                                     // statistics rows per image: one per (2 x 128 tile, tile row)
 int halo3_norm_maxc();                                                                 // most source channels "normalise on load" takes
+
+// ---- conv_wgrad.hip: the weight gradients.  One plan (plan_wgrad) decides the three answers below for a descriptor.
+int wgrad_route(const sgg_conv_desc* d);                                               // the kernel run_wgrad launches (an sgg_route)
+size_t wgrad_ws_bytes(const sgg_conv_desc* d);                                         // workspace of a single call; two networks: twice that
+// (xb, dyb, dwb): the same call site of a SECOND network (sgg_*_bwd_weight_group2), nullptr: one network
+int run_wgrad(const sgg_conv_desc* d, const void* x, const void* dy, float* dw, int Cr, int Kr, int accumulate, void* ws, size_t ws_bytes, hipStream_t s,
+              const void* xb = nullptr, const void* dyb = nullptr, float* dwb = nullptr);
+// the all-taps 3x3 kernel sums TWO applications (x, dy), (x2, dy2) of one layer into one dw (sgg_conv2d_bwd_weight_pair / pair2)
+struct W9Net { const void* x; const void* dy; const void* x2; const void* dy2; float* dw; };
+bool w9_ok(const sgg_conv_desc* d);                                                    // the shape runs that kernel: the pair form exists
+bool w9_pair2_ok(const sgg_conv_desc* d);                                              // ... with an even split count: so does the two-network form
+int run_w9(const sgg_conv_desc* d, const W9Net& na, const W9Net* nb, int Cr, int Kr, int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
+#ifdef SGG_LAB
+int wgrad_debug_occupancy();                                                           // sgg_debug_occupancy's entry for conv_wgrad_kernel<bf16, 128, 128, 2>
+#endif

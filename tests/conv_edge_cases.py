@@ -24,7 +24,9 @@ from oracle import sggan_oracle as O
 
 DTYPES = {"bf16": torch.bfloat16, "f32": torch.float32}
 
-# (name, kind, R, stride, padding, Cin, Cout, N, H, W, {dtype: (forward, data-gradient, weight-gradient route)})
+# (name, kind, R, stride, padding, Cin, Cout, N, H, W, {dtype: (forward, data-gradient, weight-gradient route, weight-gradient workspace)})
+# The workspace is what sgg_conv2d_bwd_weight_workspace reports, in bytes: slab count x slab size, so it pins the planner's split
+# count next to its route (recorded from the library before its launch layer was given one plan).
 # deconv rows: H, W are the transposed conv's INPUT size.  Padding LEAD-1: zero padding with a LEADING pad of 1 and no trailing
 # one -- a descriptor the library accepts and Keras 'SAME' never produces at an even size; run through kernels.py directly.
 # The dtype set of a row is the key set of its route dict: the bf16-only kernel families run in bf16 alone (their f32 shapes
@@ -32,86 +34,96 @@ DTYPES = {"bf16": torch.bfloat16, "f32": torch.float32}
 ROWS = [
     # generic GEMM tiles
     # Mmax 20806: last M tile 70 rows, second channel tile 8 columns, ktot_max 3; dgrad: 256x16 with the same ragged M
-    ("glds_256x256_fwd_ragged", "conv", 3, 1, "SAME", 16, 264, 2, 101, 103, {"bf16": ("GLDS_256x256", "GLDS_256x16+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_256x256", "GLDS_256x16+SPLITK", "WGRAD_128x128")}),
+    ("glds_256x256_fwd_ragged", "conv", 3, 1, "SAME", 16, 264, 2, 101, 103, {"bf16": ("GLDS_256x256", "GLDS_256x16+SPLITK", "WGRAD_128x128", 12469248), "f32": ("GLDS_256x256", "GLDS_256x16+SPLITK", "WGRAD_128x128", 12469248)}),
     # the 256x256 tile on the data-gradient side
-    ("glds_256x256_dgrad", "conv", 3, 1, "SAME", 264, 16, 2, 101, 103, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16"), "f32": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16")}),
+    ("glds_256x256_dgrad", "conv", 3, 1, "SAME", 264, 16, 2, 101, 103, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16", 8211456), "f32": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16", 8211456)}),
     # stride 2: four parity classes of unequal size (102x103, 102x102, 101x103, 101x102)
-    ("glds_256x256_dgrad_s2", "conv", 3, 2, "SAME", 264, 16, 2, 203, 205, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16"), "f32": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16")}),
+    ("glds_256x256_dgrad_s2", "conv", 3, 2, "SAME", 264, 16, 2, 203, 205, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16", 8211456), "f32": ("GLDS_256x16+SPLITK", "GLDS_256x256", "WGRAD_128x16", 8211456)}),
     # M tail 109, channel tail 8, 324 blocks: not split
-    ("glds_256x128_3stage", "conv", 3, 1, "SAME", 120, 392, 1, 79, 131, {"bf16": ("GLDS_256x128", "GLDS_128x64+SPLITK", "WGRAD_V2"), "f32": ("GLDS_256x128", "GLDS_128x64+SPLITK", "WGRAD_V2")}),
+    ("glds_256x128_3stage", "conv", 3, 1, "SAME", 120, 392, 1, 79, 131, {"bf16": ("GLDS_256x128", "GLDS_128x64+SPLITK", "WGRAD_V2", 42336000), "f32": ("GLDS_256x128", "GLDS_128x64+SPLITK", "WGRAD_V2", 42336000)}),
     # 194 blocks: the in-kernel epilogue of a long reduction, not split
-    ("glds_128x128_long_k", "conv", 3, 1, "SAME", 120, 136, 1, 100, 123, {"bf16": ("GLDS_128x128", "GLDS_128x64", "WGRAD_128x128"), "f32": ("GLDS_128x128", "GLDS_128x64", "WGRAD_128x128")}),
+    ("glds_128x128_long_k", "conv", 3, 1, "SAME", 120, 136, 1, 100, 123, {"bf16": ("GLDS_128x128", "GLDS_128x64", "WGRAD_128x128", 28788480), "f32": ("GLDS_128x128", "GLDS_128x64", "WGRAD_128x128", 28788480)}),
     # forward split: DC 40, K-tiles 22 (bf16) / 43 (f32) over 5 / 10 splits
-    ("splitk_fwd_dc40", "conv", 3, 1, "SAME", 152, 34, 1, 7, 9, {"bf16": ("GLDS_128x64+SPLITK", "GLDS_128x128", "WGRAD_128x64"), "f32": ("GLDS_128x64+SPLITK", "GLDS_128x128", "WGRAD_128x64")}),
+    ("splitk_fwd_dc40", "conv", 3, 1, "SAME", 152, 34, 1, 7, 9, {"bf16": ("GLDS_128x64+SPLITK", "GLDS_128x128", "WGRAD_128x64", 218880), "f32": ("GLDS_128x64+SPLITK", "GLDS_128x128", "WGRAD_128x64", 218880)}),
     # data gradient split: DC 40
-    ("splitk_dgrad_dc40", "conv", 3, 1, "SAME", 34, 152, 1, 7, 9, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_128x128")}),
+    ("splitk_dgrad_dc40", "conv", 3, 1, "SAME", 34, 152, 1, 7, 9, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_128x128", 218880), "f32": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_128x128", 218880)}),
     # forward split: DC 264 (two full 128 tiles + 8), K-tiles 22 / 43 over 5 / 10
-    ("splitk_fwd_dc264", "conv", 3, 1, "SAME", 152, 264, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_V2"), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_V2")}),
+    ("splitk_fwd_dc264", "conv", 3, 1, "SAME", 152, 264, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_V2", 2889216), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_V2", 2889216)}),
     # data gradient split: DC 264
-    ("splitk_dgrad_dc264", "conv", 3, 1, "SAME", 264, 152, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128")}),
+    ("splitk_dgrad_dc264", "conv", 3, 1, "SAME", 264, 152, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128", 1444608), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128", 1444608)}),
     # 1x1 window: one product per input channel (the sensitivity check's Cin >= 256 case); f32: 16 K-tiles over 4 splits
-    ("pointwise_c512", "conv", 1, 1, "SAME", 512, 136, 1, 8, 9, {"bf16": ("GLDS_128x128", "GLDS_128x128", "WGRAD_128x128"), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128", "WGRAD_128x128")}),
+    ("pointwise_c512", "conv", 1, 1, "SAME", 512, 136, 1, 8, 9, {"bf16": ("GLDS_128x128", "GLDS_128x128", "WGRAD_128x128", 278528), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128", "WGRAD_128x128", 278528)}),
     # halo3: forward and data gradient, bf16
-    ("halo3_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64")}),   # H = 4: the fold's virtual rows dy[2]+dy[0] and dy[H-3]+dy[H-1] overlap
-    ("halo3_min_same", "conv", 3, 1, "SAME", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64")}),
+    ("halo3_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64", 294912)}),   # H = 4: the fold's virtual rows dy[2]+dy[0] and dy[H-3]+dy[H-1] overlap
+    ("halo3_min_same", "conv", 3, 1, "SAME", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64", 294912)}),
     # odd batch, two column tiles, destination tail of 8 in the second 256 tile
-    ("halo3_n3_dtail_reflect", "conv", 3, 1, "REFLECT-1", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),
-    ("halo3_n3_dtail_same", "conv", 3, 1, "SAME", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),
+    ("halo3_n3_dtail_reflect", "conv", 3, 1, "REFLECT-1", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST", 21897216)}),
+    ("halo3_n3_dtail_same", "conv", 3, 1, "SAME", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST", 21897216)}),
     # the destination tail on the data-gradient side (forward: 264 source channels, outside)
-    ("halo3_dgrad_dtail_reflect", "conv", 3, 1, "REFLECT-1", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_128x64")}),
-    ("halo3_dgrad_dtail_same", "conv", 3, 1, "SAME", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_128x64")}),
-    ("halo3_out_h5", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 5, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: odd H
-    ("halo3_out_h2_reflect", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 2, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: H = 2 < 4 (w9 admits it)
-    ("halo3_out_h2_same", "conv", 3, 1, "SAME", 64, 64, 1, 2, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),
-    ("halo3_out_w120", "conv", 3, 1, "SAME", 64, 64, 1, 4, 120, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: W one granule short of the tile
-    ("halo3_out_w136", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 4, 136, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: W one granule past the tile
-    ("halo3_out_c72", "conv", 3, 1, "REFLECT-1", 72, 72, 1, 4, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: 72 source channels in both directions
+    ("halo3_dgrad_dtail_reflect", "conv", 3, 1, "REFLECT-1", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_128x64", 1216512)}),
+    ("halo3_dgrad_dtail_same", "conv", 3, 1, "SAME", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_128x64", 1216512)}),
+    ("halo3_out_h5", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 5, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 442368)}),   # outside: odd H
+    ("halo3_out_h2_reflect", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 2, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 147456)}),   # outside: H = 2 < 4 (w9 admits it)
+    ("halo3_out_h2_same", "conv", 3, 1, "SAME", 64, 64, 1, 2, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 147456)}),
+    ("halo3_out_w120", "conv", 3, 1, "SAME", 64, 64, 1, 4, 120, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 294912)}),   # outside: W one granule short of the tile
+    ("halo3_out_w136", "conv", 3, 1, "REFLECT-1", 64, 64, 1, 4, 136, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 442368)}),   # outside: W one granule past the tile
+    ("halo3_out_c72", "conv", 3, 1, "REFLECT-1", 72, 72, 1, 4, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 373248)}),   # outside: 72 source channels in both directions
     # s2halo: stride-2 data gradient / transposed conv forward, bf16
-    ("s2halo_min", "conv", 3, 2, "SAME", 64, 64, 1, 16, 64, {"bf16": ("GLDS_128x64", "S2HALO", "WGRAD_128x64")}),   # one 8 x 32 tile of dy
-    ("s2halo_min_deconv", "deconv", 3, 2, "SAME", 64, 64, 1, 8, 32, {"bf16": ("S2HALO", "GLDS_128x64", "WGRAD_128x64")}),   # the same geometry as a transposed conv forward
-    ("s2halo_out_ho12", "conv", 3, 2, "SAME", 64, 64, 1, 24, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: Ho = 12
-    ("s2halo_out_odd_h", "conv", 3, 2, "SAME", 64, 64, 1, 15, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: odd H (leading pad 1)
-    ("s2halo_out_c72", "conv", 3, 2, "SAME", 72, 72, 1, 16, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),   # outside: 72 channels
+    ("s2halo_min", "conv", 3, 2, "SAME", 64, 64, 1, 16, 64, {"bf16": ("GLDS_128x64", "S2HALO", "WGRAD_128x64", 147456)}),   # one 8 x 32 tile of dy
+    ("s2halo_min_deconv", "deconv", 3, 2, "SAME", 64, 64, 1, 8, 32, {"bf16": ("S2HALO", "GLDS_128x64", "WGRAD_128x64", 147456)}),   # the same geometry as a transposed conv forward
+    ("s2halo_out_ho12", "conv", 3, 2, "SAME", 64, 64, 1, 24, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 294912)}),   # outside: Ho = 12
+    ("s2halo_out_odd_h", "conv", 3, 2, "SAME", 64, 64, 1, 15, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 147456)}),   # outside: odd H (leading pad 1)
+    ("s2halo_out_c72", "conv", 3, 2, "SAME", 72, 72, 1, 16, 64, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 186624)}),   # outside: 72 channels
     # s2n: 3(8) -> 64 stride 2, data and weight gradient
-    ("s2n_wo5", "conv", 3, 2, "SAME", 3, 64, 1, 6, 10, {"bf16": ("GLDS_128x64", "S2N", "S2N"), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64")}),   # Wo = 5: less than one 16-pixel item
-    ("s2n_wo130", "conv", 3, 2, "SAME", 3, 64, 3, 4, 260, {"bf16": ("GLDS_128x64", "S2N", "S2N"), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64")}),   # Wo = 130: one 128-pixel segment plus 2
+    ("s2n_wo5", "conv", 3, 2, "SAME", 3, 64, 1, 6, 10, {"bf16": ("GLDS_128x64", "S2N", "S2N", 55296), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64", 18432)}),   # Wo = 5: less than one 16-pixel item
+    ("s2n_wo130", "conv", 3, 2, "SAME", 3, 64, 3, 4, 260, {"bf16": ("GLDS_128x64", "S2N", "S2N", 221184), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64", 73728)}),   # Wo = 130: one 128-pixel segment plus 2
     # 7x7 head / stem, 5x5 narrow output
-    ("head7_min", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 8, 8, {"bf16": ("N7", "GLDS_128x64", "W7")}),   # the n7 minimum
-    ("head7_ragged", "conv", 7, 1, "REFLECT-3", 64, 3, 2, 9, 65, {"bf16": ("N7", "GLDS_128x64", "W7")}),   # one row and one column past an 8 x 64 tile
-    ("head7_16x32", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 16, 32, {"bf16": ("N7", "HALO_NARROW_IN", "W7"), "f32": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD")}),
-    ("head7_out_7x9", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 7, 9, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16")}),   # outside: H < 8
+    ("head7_min", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 8, 8, {"bf16": ("N7", "GLDS_128x64", "W7", 57344)}),   # the n7 minimum
+    ("head7_ragged", "conv", 7, 1, "REFLECT-3", 64, 3, 2, 9, 65, {"bf16": ("N7", "GLDS_128x64", "W7", 458752)}),   # one row and one column past an 8 x 64 tile
+    ("head7_16x32", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 16, 32, {"bf16": ("N7", "HALO_NARROW_IN", "W7", 114688), "f32": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD", 100352)}),
+    ("head7_out_7x9", "conv", 7, 1, "REFLECT-3", 64, 3, 1, 7, 9, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16", 100352)}),   # outside: H < 8
     # HALO_NARROW_IN forward, n7 data gradient
-    ("stem7_16x32", "conv", 7, 1, "REFLECT-3", 3, 64, 1, 16, 32, {"bf16": ("HALO_NARROW_IN", "N7", "W7"), "f32": ("HALO_NARROW_IN", "HALO_DGRAD_NARROW", "WGRAD_128x64")}),
-    ("stem7_17x33", "conv", 7, 1, "REFLECT-3", 3, 64, 1, 17, 33, {"bf16": ("GLDS_128x64", "N7", "W7")}),   # generic forward, n7 data gradient
-    ("stem7_min", "conv", 7, 1, "REFLECT-3", 3, 64, 2, 8, 8, {"bf16": ("GLDS_128x64", "N7", "W7")}),
+    ("stem7_16x32", "conv", 7, 1, "REFLECT-3", 3, 64, 1, 16, 32, {"bf16": ("HALO_NARROW_IN", "N7", "W7", 185600), "f32": ("HALO_NARROW_IN", "HALO_DGRAD_NARROW", "WGRAD_128x64", 200704)}),
+    ("stem7_17x33", "conv", 7, 1, "REFLECT-3", 3, 64, 1, 17, 33, {"bf16": ("GLDS_128x64", "N7", "W7", 186624)}),   # generic forward, n7 data gradient
+    ("stem7_min", "conv", 7, 1, "REFLECT-3", 3, 64, 2, 8, 8, {"bf16": ("GLDS_128x64", "N7", "W7", 235776)}),
     # narrow output: HALO_FWD, HALO_WGRAD
-    ("narrow5_16x32", "conv", 5, 1, "SAME", 64, 8, 1, 16, 32, {"bf16": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD"), "f32": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD")}),
-    ("narrow5_17x32", "conv", 5, 1, "SAME", 64, 8, 1, 17, 32, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16")}),   # the same one row taller: generic
+    ("narrow5_16x32", "conv", 5, 1, "SAME", 64, 8, 1, 16, 32, {"bf16": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD", 51200), "f32": ("HALO_FWD", "HALO_NARROW_IN", "HALO_WGRAD", 51200)}),
+    ("narrow5_17x32", "conv", 5, 1, "SAME", 64, 8, 1, 17, 32, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16", 153600)}),   # the same one row taller: generic
     # narrow input: HALO_DGRAD_NARROW (the 64 -> 8 shape's data gradient is taken by HALO_NARROW_IN first)
-    ("narrow5_in16_16x32", "conv", 5, 1, "SAME", 16, 64, 1, 16, 32, {"bf16": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64"), "f32": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64")}),
-    ("narrow5_in16_17x32", "conv", 5, 1, "SAME", 16, 64, 1, 17, 32, {"bf16": ("GLDS_128x64", "GLDS_256x16+SPLITK", "WGRAD_128x64")}),   # one row taller: generic
+    ("narrow5_in16_16x32", "conv", 5, 1, "SAME", 16, 64, 1, 16, 32, {"bf16": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64", 204800), "f32": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64", 204800)}),
+    ("narrow5_in16_17x32", "conv", 5, 1, "SAME", 16, 64, 1, 17, 32, {"bf16": ("GLDS_128x64", "GLDS_256x16+SPLITK", "WGRAD_128x64", 307200)}),   # one row taller: generic
     # weight gradients
-    ("w9_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9")}),   # H = 2: row -1 mirrors to 1 and row 2 to 0
-    ("w9_min_same", "conv", 3, 1, "SAME", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9")}),
+    ("w9_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9", 294912)}),   # H = 2: row -1 mirrors to 1 and row 2 to 0
+    ("w9_min_same", "conv", 3, 1, "SAME", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9", 294912)}),
+    # 2 tiles over 2 splits: the smallest shape at which the two-network launch gives each network a slab of its own
+    ("w9_two_splits", "conv", 3, 1, "REFLECT-1", 64, 128, 1, 4, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9", 589824)}),
     # 70 tiles over 35 splits; the odd split count has no two-network launch
-    ("w9_odd_splits", "conv", 3, 1, "REFLECT-1", 64, 128, 5, 4, 448, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9")}),
-    ("w9_out_odd_h", "conv", 3, 1, "SAME", 64, 256, 2, 5, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),   # outside: odd H -> the row-fast DMA kernel with zero padding
-    ("w9s_min", "conv", 3, 2, "SAME", 64, 128, 1, 2, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S")}),   # one output row
-    ("w9s_lead_pad", "conv", 3, 2, "LEAD-1", 64, 128, 1, 2, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S")}),   # pad_t = pad_l = 1 with H = 2 Ho: the halo's leading zero row / column
-    ("rowfast_valid", "conv", 3, 1, "VALID", 64, 256, 2, 6, 66, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),   # Wo = 64 on VALID padding
-    ("rowfast_7x7", "conv", 7, 1, "REFLECT-3", 8, 256, 1, 8, 64, {"bf16": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_V2_ROWFAST")}),   # row-fast on a 7x7 window
+    ("w9_odd_splits", "conv", 3, 1, "REFLECT-1", 64, 128, 5, 4, 448, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9", 10321920)}),
+    ("w9_out_odd_h", "conv", 3, 1, "SAME", 64, 256, 2, 5, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST", 2949120)}),   # outside: odd H -> the row-fast DMA kernel with zero padding
+    ("w9s_min", "conv", 3, 2, "SAME", 64, 128, 1, 2, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S", 294912)}),   # one output row: one split, so two networks take a launch each
+    ("w9s_lead_pad", "conv", 3, 2, "LEAD-1", 64, 128, 1, 2, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S", 294912)}),   # pad_t = pad_l = 1 with H = 2 Ho: the halo's leading zero row / column
+    ("w9s_two_splits", "conv", 3, 2, "SAME", 64, 128, 1, 4, 128, {"bf16": ("GLDS_128x128", "GLDS_128x64", "W9S", 589824)}),   # Ho 2: 2 tiles over 2 splits, two networks share the launch
+    ("rowfast_valid", "conv", 3, 1, "VALID", 64, 256, 2, 6, 66, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST", 2359296)}),   # Wo = 64 on VALID padding
+    ("rowfast_7x7", "conv", 7, 1, "REFLECT-3", 8, 256, 1, 8, 64, {"bf16": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_V2_ROWFAST", 1605632)}),   # row-fast on a 7x7 window
     # f32 stages 32 pixels: row-fast at Wo = 32 (bf16: the gather form), odd H
-    ("rowfast_f32_wo32", "conv", 3, 1, "SAME", 32, 256, 2, 5, 32, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2"), "f32": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST")}),
-    ("wgrad_v2_wo63", "conv", 3, 1, "SAME", 64, 256, 1, 4, 63, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2")}),   # gather form, one pixel short of a stage row
-    ("wgrad_v2_wo65", "conv", 3, 1, "SAME", 64, 256, 1, 4, 65, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2")}),   # gather form, one pixel past
+    ("rowfast_f32_wo32", "conv", 3, 1, "SAME", 32, 256, 2, 5, 32, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2", 884736), "f32": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2_ROWFAST", 884736)}),
+    ("wgrad_v2_wo63", "conv", 3, 1, "SAME", 64, 256, 1, 4, 63, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2", 1179648)}),   # gather form, one pixel short of a stage row
+    ("wgrad_v2_wo65", "conv", 3, 1, "SAME", 64, 256, 1, 4, 65, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "WGRAD_V2", 1769472)}),   # gather form, one pixel past
     # Cr 3 of 8 stored, K tail 8
-    ("wgrad_128x128_cr3", "conv", 3, 1, "SAME", 3, 136, 1, 9, 11, {"bf16": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_128x128"), "f32": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_128x128")}),
-    ("wgrad_128x64_cr3", "conv", 3, 2, "VALID", 3, 24, 1, 9, 11, {"bf16": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64"), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64")}),   # Cr 3 of 8 stored
-    ("wgrad_128x16_kr3", "conv", 3, 1, "SAME", 24, 3, 1, 9, 11, {"bf16": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x16"), "f32": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x16")}),   # Kr 3 of 8 stored
+    ("wgrad_128x128_cr3", "conv", 3, 1, "SAME", 3, 136, 1, 9, 11, {"bf16": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_128x128", 39168), "f32": ("GLDS_128x128", "GLDS_256x16+SPLITK", "WGRAD_128x128", 39168)}),
+    ("wgrad_128x64_cr3", "conv", 3, 2, "VALID", 3, 24, 1, 9, 11, {"bf16": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64", 6912), "f32": ("GLDS_128x64", "GLDS_256x16", "WGRAD_128x64", 6912)}),   # Cr 3 of 8 stored
+    ("wgrad_128x16_kr3", "conv", 3, 1, "SAME", 24, 3, 1, 9, 11, {"bf16": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x16", 6912), "f32": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x16", 6912)}),   # Kr 3 of 8 stored
     # transposed conv
     # outside s2halo: odd sizes, channel tails
-    ("deconv_ragged", "deconv", 3, 2, "SAME", 24, 40, 2, 5, 7, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64"), "f32": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64")}),
+    ("deconv_ragged", "deconv", 3, 2, "SAME", 24, 40, 2, 5, 7, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 34560), "f32": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 34560)}),
 ]
+# The weight-gradient workspace of the bench workload's layers (tests/test_gpu_exact.LAYERS, bf16), recorded like the rows' from the
+# library before its launch layer was given one plan: a planner edit cannot move a production layer's slab count unnoticed.
+BENCH_WS_WGRAD = {
+    "G.res_3x3_256": 75497472, "G.c2_s2_64_128": 75497472, "G.c3_s2_128_256": 60162048, "G.d1_T_256_128": 60162048, "G.d2_T_128_64": 75497472,
+    "G.c1_7x7_3_64": 46273024, "G.out_7x7_64_3": 28901376, "D.h0_s2_3_64": 9437184, "D.h1_s2_64_128": 75497472, "D.h2_s2_128_256": 60162048,
+    "D.h3_s1_256_512": 75497472, "D.h31_s2v_512": 66060288, "D.h32_s2v_512": 66060288, "D.h33_s1v_512": 47185920, "D.h4_s1_512_34": 2211840,
+}
 # Rows whose dx passes bf16's exact-integer range: 49 taps x 256 output channels of +-1 products have a standard deviation of 75,
 # so no draw keeps 4000 of them within 256.  The row is there for its weight gradient; its dx (at most 2^24: exact in f32 in any
 # order) is compared after the ONE round-to-nearest-even to bf16 of store(), as test_gpu_exact.py compares the bench layers'.
@@ -144,6 +156,11 @@ def geom(row, dtype):
 def routes(g):
     from sggan_amd import _abi as A
     return tuple(A.route_name(c) for c in (g.route_fwd, g.route_dgrad, g.route_wgrad))
+
+
+def row_routes(row, dtype):
+    """The three routes the table names for a row."""
+    return row[10][dtype][:3]
 
 
 def ints(rng, shape, lo=-1, hi=1):

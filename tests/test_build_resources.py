@@ -2,8 +2,8 @@
 
 The 8-wave kernels run at 2 waves/SIMD, i.e. a 256-VGPR budget they use almost completely; a source change that tips
 one of them into scratch spills costs 2-5x at run time without failing any numerical test (seen while developing the
-all-taps weight-gradient kernel).  This test recompiles the conv sources of build.SOURCES with -Rpass-analysis=kernel-resource-usage
-and requires zero VGPR spills and the expected occupancy for the production configurations, and one owner file per kernel.
+all-taps weight-gradient kernel).  This test recompiles the conv sources of build.SOURCES (conv.hip, conv_halo3.hip, conv_wgrad.hip)
+with -Rpass-analysis=kernel-resource-usage and requires zero VGPR spills and the expected occupancy for the production configurations, and one owner file per kernel.
 """
 import os
 import re

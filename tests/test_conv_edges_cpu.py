@@ -13,16 +13,45 @@ from tests import conv_edge_cases as E
 
 @pytest.mark.parametrize("row", E.ROWS, ids=E.ROW_IDS)
 def test_row_takes_the_route_the_table_names(row):
-    for dtype, exp in row[10].items():
-        assert E.routes(E.geom(row, dtype)) == exp, (row[0], dtype)
+    for dtype in row[10]:
+        assert E.routes(E.geom(row, dtype)) == E.row_routes(row, dtype), (row[0], dtype)
 
 
 def test_every_route_is_pinned_by_a_row():
-    seen = {r.split("+")[0] for row in E.ROWS for rs in row[10].values() for r in rs}
+    named = [r for row in E.ROWS for dtype in row[10] for r in E.row_routes(row, dtype)]
+    seen = {r.split("+")[0] for r in named}
     # REG: the register-staged GEMM, reachable only in a lab build with the DMA kernels switched off
     assert seen == set(A.ROUTE_NAMES) - {"REG"}, set(A.ROUTE_NAMES) ^ seen
-    split = {r for row in E.ROWS for rs in row[10].values() for r in rs if r.endswith("+SPLITK")}
+    split = {r for r in named if r.endswith("+SPLITK")}
     assert split and not any(r.startswith(("HALO", "S2", "N7", "W")) for r in split)     # only the generic GEMM tiles split K
+
+
+@pytest.mark.parametrize("row", E.ROWS, ids=E.ROW_IDS)
+def test_row_keeps_its_weight_gradient_plan(row):
+    """The planner's answer for the row -- the workspace the table records, i.e. its slab count -- and the precondition of the
+    two-network test of test_gpu_conv_edges.py: operands (x, dy) and (2x, -dy) keep every partial sum of dw within
+    2 N Ho Wo <= 2^24, exact in f32 in any summation order."""
+    for dtype in row[10]:
+        g = E.geom(row, dtype)
+        assert g.ws_wgrad == row[10][dtype][3], (row[0], dtype)
+        if E.row_routes(row, dtype)[2] == "W9":
+            slab = 9 * g.desc.C * g.desc.K * 4                   # one f32 slab of dW per split: the workspace is the split count
+            sp, tiles = g.ws_wgrad // slab, g.desc.N * (g.desc.H // 2) * (g.desc.W // 64)
+            assert g.ws_wgrad == sp * slab and 1 <= sp <= tiles, (row[0], sp, tiles)
+            if row[0] in ("w9_two_splits", "w9_odd_splits"):
+                assert sp == (2 if row[0] == "w9_two_splits" else 35)
+        assert 2 * g.desc.N * g.desc.Ho * g.desc.Wo <= 2 ** 24
+    assert E.BY_NAME["w9s_two_splits"][10]["bf16"][3] == 2 * E.BY_NAME["w9s_min"][10]["bf16"][3]      # two slabs against one
+
+
+def test_bench_layers_keep_their_weight_gradient_plan():
+    """The same for the bench workload's layers (the shapes test_gpu_exact.py runs), against values recorded the same way."""
+    from tests.test_gpu_exact import LAYERS
+    assert set(E.BENCH_WS_WGRAD) == {l[0] for l in LAYERS}
+    for l in LAYERS:
+        g = E.geom(l + ({},), "bf16")
+        assert g.ws_wgrad == E.BENCH_WS_WGRAD[l[0]], l[0]
+        assert 2 * g.desc.N * g.desc.Ho * g.desc.Wo <= 2 ** 24
 
 
 def test_route_query_rejects_bad_arguments():

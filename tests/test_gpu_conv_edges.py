@@ -67,9 +67,9 @@ def test_edge_row_fwd_bwd_bit_exact(sg, row, dtype):
     name, kind, R, stride, padding = row[:5]
     dt = E.DTYPES[dtype]
     g = E.geom(row, dtype)
-    assert E.routes(g) == row[10][dtype]                 # on this device's library too: a lab build or a config difference cannot hide a moved shape
+    assert E.routes(g) == E.row_routes(row, dtype)       # on this device's library too: a lab build or a config difference cannot hide a moved shape
     e = E.expected(name)
-    tag = f"{name}[{dtype}] {row[10][dtype]}"
+    tag = f"{name}[{dtype}] {E.row_routes(row, dtype)}"
     if padding == "LEAD-1":                              # no Keras padding gives this descriptor: the launchers of kernels.py directly
         K = sg.kernels
         g, x, dy, wf, wd, b = operands(sg, row, dtype, e)
@@ -146,6 +146,55 @@ def test_edge_row_fused_forms_in_guard_cells(sg, row, dtype):
         (K.deconv_wgrad if g.is_deconv else K.conv_wgrad)(g, x, dy, dw.t, accumulate=accumulate)
         E.same(dw.t, e.dw + base, f"{tag} dw accumulate={accumulate}")
         dw.check(f"{tag} dw accumulate={accumulate}")
+
+
+# Rows run through the two-network forms of the weight gradient (what the cycle step launches): every route of the family, the
+# grouped call's shared launch (W9 / W9S from two splits on, the LDS-DMA kernel) and its launch per network (the others; W9 with an
+# odd split count, W9S with one split).
+GROUPED = ["narrow5_16x32", "head7_16x32", "head7_ragged", "stem7_17x33", "w9_min_reflect", "w9_odd_splits", "w9_two_splits", "w9s_min",
+           "w9s_lead_pad", "w9s_two_splits", "s2n_wo130", "rowfast_valid", "rowfast_f32_wo32", "wgrad_v2_wo65", "wgrad_128x128_cr3",
+           "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged"]
+GROUPED_CASES = [(E.BY_NAME[n], dt) for n in GROUPED for dt in E.BY_NAME[n][10]]
+
+
+@pytest.mark.parametrize("row,dtype", GROUPED_CASES, ids=[f"{r[0]}-{dt}" for r, dt in GROUPED_CASES])
+def test_edge_row_two_network_weight_gradients_bit_exact(sg, row, dtype):
+    """Network A is the row's (x, dy), network B (2x, -dy), stacked along the batch axis: dwA = dw and dwB = -2 dw, so a swapped
+    operand pointer or swapped slabs change a sign or a factor.  Every operand is exact in bf16 and every partial sum stays
+    within 2 N Ho Wo <= 2^24 (test_conv_edges_cpu.py asserts it), so the results are exact in ANY summation order -- the
+    shared launches sum in another order than a single call -- and the row's one oracle run serves both networks."""
+    K = sg.kernels
+    name = row[0]
+    e = E.expected(name)
+    g, x, dy, _, _, _ = operands(sg, row, dtype, e)
+    assert E.routes(g)[2] == E.row_routes(row, dtype)[2]
+    tag = f"{name}[{dtype}] {E.row_routes(row, dtype)[2]}"
+    xs, dys = torch.cat([x, 2 * x]), torch.cat([dy, -dy])
+    wshape = tuple(e.w.shape)
+    for accumulate in (False, True):
+        dwa, dwb = Guarded(wshape, torch.float32, fill=5.0), Guarded(wshape, torch.float32, fill=-3.0)
+        K.conv_wgrad_group2(g, xs, dys, dwa.t, dwb.t, accumulate=accumulate)
+        E.same(dwa.t, e.dw + (5.0 if accumulate else 0.0), f"{tag} group2 dwA accumulate={accumulate}")
+        E.same(dwb.t, -2 * e.dw + (-3.0 if accumulate else 0.0), f"{tag} group2 dwB accumulate={accumulate}")
+        dwa.check(f"{tag} group2 dwA accumulate={accumulate}")
+        dwb.check(f"{tag} group2 dwB accumulate={accumulate}")
+    if E.row_routes(row, dtype)[2] != "W9":
+        return
+    # two applications of one layer summed into one dw: dw(x, dy) + dw(2x, -dy) = -dw
+    assert g.wgrad_pair
+    for accumulate in (False, True):
+        dwa = Guarded(wshape, torch.float32, fill=5.0)
+        K.conv_wgrad_pair(g, x, dy, 2 * x, -dy, dwa.t, accumulate=accumulate)
+        E.same(dwa.t, -e.dw + (5.0 if accumulate else 0.0), f"{tag} pair accumulate={accumulate}")
+        dwa.check(f"{tag} pair accumulate={accumulate}")
+    if name == "w9_two_splits":                          # ... of two networks: A as above, B dw(2x, dy) + dw(x, dy) = 3 dw
+        for accumulate in (False, True):
+            dwa, dwb = Guarded(wshape, torch.float32, fill=5.0), Guarded(wshape, torch.float32, fill=-3.0)
+            assert K.conv_wgrad_pair2(g, (x, dy, 2 * x, -dy, dwa.t), (2 * x, dy, x, dy, dwb.t), accumulate=accumulate) is True
+            E.same(dwa.t, -e.dw + (5.0 if accumulate else 0.0), f"{tag} pair2 dwA accumulate={accumulate}")
+            E.same(dwb.t, 3 * e.dw + (-3.0 if accumulate else 0.0), f"{tag} pair2 dwB accumulate={accumulate}")
+            dwa.check(f"{tag} pair2 dwA accumulate={accumulate}")
+            dwb.check(f"{tag} pair2 dwB accumulate={accumulate}")
 
 
 def test_odd_split_count_has_no_two_network_weight_gradient(sg):
