@@ -221,11 +221,11 @@ def conv_fwd_stats(g: ConvGeom, x, w_fwd, bias, out=None, out_partial=None):
     return y, partial
 
 
-def conv_fwd_stats_pair(g: ConvGeom, x, w_fwd, bias, w_fwd2, bias2, nsplit):
+def conv_fwd_stats_pair(g: ConvGeom, x, w_fwd, bias, w_fwd2, bias2, nsplit, out=None, out_partial=None):
     """conv_fwd_stats over a stacked batch of two networks: images [:nsplit] with (w_fwd, bias), the rest with (w_fwd2, bias2)."""
     assert tuple(x.shape) == g.x_shape and g.pair_ok and g.stats_chunks > 0 and 0 < nsplit < g.x_shape[0]
-    y = torch.empty(g.y_shape, dtype=x.dtype, device=x.device)
-    partial = torch.empty((g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x.device)
+    y = _out(out, g.y_shape, x.dtype, x.device)
+    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x.device)
     pr = _prof("conv2d_fwd_pair", g)
     if pr: pr.start()
     ws = workspace(g.ws_fwd, x.device) if g.ws_fwd else None
@@ -235,15 +235,15 @@ def conv_fwd_stats_pair(g: ConvGeom, x, w_fwd, bias, w_fwd2, bias2, nsplit):
     return y, partial
 
 
-def conv_fwd_stats_normload(g: ConvGeom, x_raw, x_stats, gamma, beta, w_fwd, bias, pair=None):
+def conv_fwd_stats_normload(g: ConvGeom, x_raw, x_stats, gamma, beta, w_fwd, bias, pair=None, out=None, out_partial=None, out_norm=None):
     """conv(relu(instnorm(x_raw))) with the norm applied to the operand tiles inside the conv kernel ("normalise on load",
     sgg_conv2d_fwd_stats_normload).  x_stats: (mean, rstd) of x_raw (instnorm_finalize).  pair = (gamma2, beta2, w_fwd2,
     bias2, nsplit) for the lockstep pair.  Returns (x_norm, y, partial): the normalised operand (a by-product the backward
     pass needs), the conv output and its statistics rows -- all bit-identical to instnorm_fwd_partial + conv_fwd_stats."""
     assert tuple(x_raw.shape) == g.x_shape and g.normload_ok and g.stats_chunks > 0
-    x_norm = torch.empty_like(x_raw)
-    y = torch.empty(g.y_shape, dtype=x_raw.dtype, device=x_raw.device)
-    partial = torch.empty((g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x_raw.device)
+    x_norm = _out(out_norm, g.x_shape, x_raw.dtype, x_raw.device)
+    y = _out(out, g.y_shape, x_raw.dtype, x_raw.device)
+    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x_raw.device)
     gamma2, beta2, w2, bias2, nsplit = pair if pair is not None else (None, None, None, None, 0)
     pr = _prof("conv2d_fwd_normload" + ("_pair" if pair is not None else ""), g)
     if pr: pr.start()
@@ -263,10 +263,10 @@ def instnorm_finalize(partial, HW, eps=1e-3):
     return stats
 
 
-def conv_dgrad_pair(g: ConvGeom, dy, w_dgrad, w_dgrad2, nsplit, addend=None):
+def conv_dgrad_pair(g: ConvGeom, dy, w_dgrad, w_dgrad2, nsplit, addend=None, out=None):
     assert tuple(dy.shape) == g.y_shape and g.pair_ok and 0 < nsplit < g.y_shape[0]
     assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype == dy.dtype)
-    dx = torch.empty(g.x_shape, dtype=dy.dtype, device=dy.device)
+    dx = _out(out, g.x_shape, dy.dtype, dy.device)
     pr = _prof("conv2d_bwd_data_pair", g)
     if pr: pr.start()
     ws = workspace(g.ws_dgrad, dy.device) if g.ws_dgrad else None
@@ -285,7 +285,7 @@ def conv_dgrad(g: ConvGeom, dy, w_dgrad, addend=None, out_f32=False, out=None):
     if out_f32:
         assert g.dgrad_mixed and dy.dtype == torch.bfloat16
         assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype in (torch.bfloat16, torch.float32))
-        dx = torch.empty(g.x_shape, dtype=torch.float32, device=dy.device)
+        dx = _out(out, g.x_shape, torch.float32, dy.device)
         if pr: pr.start()
         A.check(A.lib().sgg_conv2d_bwd_data_mixed(C.byref(g.desc), _p(dy), _p(w_dgrad), _p(addend),
                                                   int(addend is not None and addend.dtype == torch.float32), _p(dx), _p(ws), g.ws_dgrad, _s()),
@@ -300,13 +300,14 @@ def conv_dgrad(g: ConvGeom, dy, w_dgrad, addend=None, out_f32=False, out=None):
     return dx
 
 
-def conv_dgrad_stats(g: ConvGeom, dy, w_dgrad, addend, norm_x, norm_stats, norm_gamma, norm_beta, norm_act=A.ACT_NONE, norm_leak=0.0):
+def conv_dgrad_stats(g: ConvGeom, dy, w_dgrad, addend, norm_x, norm_stats, norm_gamma, norm_beta, norm_act=A.ACT_NONE, norm_leak=0.0,
+                     out=None, out_partial=None):
     """conv_dgrad + the first pass of the instance-norm backward that consumes dx (the norm whose input is norm_x)."""
     assert tuple(dy.shape) == g.y_shape and not g.is_deconv and g.bwd_stats_chunks > 0
     assert tuple(norm_x.shape) == g.x_shape and norm_x.dtype == dy.dtype
     assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype == dy.dtype)
-    dx = torch.empty(g.x_shape, dtype=dy.dtype, device=dy.device)
-    partial = torch.empty((g.x_shape[0], g.bwd_stats_chunks, g.x_shape[3], 2), dtype=torch.float32, device=dy.device)
+    dx = _out(out, g.x_shape, dy.dtype, dy.device)
+    partial = _out(out_partial, (g.x_shape[0], g.bwd_stats_chunks, g.x_shape[3], 2), torch.float32, dy.device)
     pr = _prof("conv2d_bwd_data", g)
     if pr: pr.start()
     ws = workspace(g.ws_dgrad, dy.device) if g.ws_dgrad else None
@@ -381,10 +382,10 @@ def conv_fwd_group2(g: ConvGeom, x, w_fwd, bias, w_fwd2, bias2, act=A.ACT_NONE, 
     return y
 
 
-def conv_dgrad_group2(g: ConvGeom, dy, w_dgrad, w_dgrad2, addend=None):
+def conv_dgrad_group2(g: ConvGeom, dy, w_dgrad, w_dgrad2, addend=None, out=None):
     assert tuple(dy.shape) == _stacked(g.y_shape) and not g.is_deconv
     assert addend is None or (tuple(addend.shape) == _stacked(g.x_shape) and addend.dtype == dy.dtype)
-    dx = torch.empty(_stacked(g.x_shape), dtype=dy.dtype, device=dy.device)
+    dx = _out(out, _stacked(g.x_shape), dy.dtype, dy.device)
     ws = workspace(2 * g.ws_dgrad, dy.device) if g.ws_dgrad else None
     pr = _prof("conv2d_bwd_data_group2", g)
     if pr: pr.start()
@@ -418,9 +419,9 @@ def deconv_fwd_group2(g: ConvGeom, x, w_dgrad, bias, w_dgrad2, bias2, act=A.ACT_
     return y
 
 
-def deconv_dgrad_group2(g: ConvGeom, dy, w_fwd, w_fwd2):
+def deconv_dgrad_group2(g: ConvGeom, dy, w_fwd, w_fwd2, out=None):
     assert tuple(dy.shape) == _stacked(g.y_shape) and g.is_deconv
-    dx = torch.empty(_stacked(g.x_shape), dtype=dy.dtype, device=dy.device)
+    dx = _out(out, _stacked(g.x_shape), dy.dtype, dy.device)
     ws = workspace(2 * g.ws_dgrad, dy.device) if g.ws_dgrad else None
     pr = _prof("deconv2d_bwd_data_group2", g)
     if pr: pr.start()
@@ -438,12 +439,12 @@ def deconv_fwd(g: ConvGeom, x, w_dgrad, bias, act=A.ACT_NONE, leak=0.0, out=None
     return y
 
 
-def deconv_fwd_stats(g: ConvGeom, x, w_dgrad, bias, pair=None):
+def deconv_fwd_stats(g: ConvGeom, x, w_dgrad, bias, pair=None, out=None, out_partial=None):
     """Conv2DTranspose forward (no activation) + the per-chunk (sum, sumsq) rows of its output for the instance norm behind it.
     pair = (w_dgrad2, bias2, nsplit): `g` describes a stacked batch of two networks, images >= nsplit use the second weight set."""
     assert tuple(x.shape) == g.x_shape and g.is_deconv and g.stats_chunks > 0
-    y = torch.empty(g.y_shape, dtype=x.dtype, device=x.device)
-    partial = torch.empty((g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x.device)
+    y = _out(out, g.y_shape, x.dtype, x.device)
+    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x.device)
     w2, b2, ns = pair if pair is not None else (None, None, 0)
     pr = _prof("deconv2d_fwd_stats", g)
     if pr: pr.start()

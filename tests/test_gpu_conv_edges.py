@@ -22,44 +22,7 @@ def sg():
     return sggan_amd
 
 
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.asarray(a, np.float32)).to("cuda").to(dtype)
-
-
-def padc(a, cp):
-    """Zero channel padding to the stored channel count."""
-    a = np.asarray(a)
-    return a if a.shape[-1] == cp else np.concatenate([a, np.zeros(a.shape[:-1] + (cp - a.shape[-1],))], axis=-1)
-
-
-def operands(sg, row, dtype, e):
-    """The stored form of a row's tensors for the kernels.py launchers: channel-padded activations, packed weights, padded bias."""
-    K = sg.kernels
-    g = E.geom(row, dtype)
-    dt = E.DTYPES[dtype]
-    xc, yc = g.x_shape[3], g.y_shape[3]
-    if g.is_deconv:                                      # w (kh, kw, out, in) is the HWIO kernel of the equivalent conv
-        wf, wd = K.pack_weights(dev(e.w), yc, xc, dt)
-    else:
-        wf, wd = K.pack_weights(dev(e.w), xc, yc, dt)
-    return g, dev(padc(e.x, xc), dt), dev(padc(e.dy, yc), dt), wf, wd, dev(padc(e.b, yc))
-
-
-class Guarded:
-    """A tensor inside a larger buffer filled with a sentinel: the bytes before and after it must survive the launch."""
-    G = 4096
-
-    def __init__(self, shape, dtype, fill=None):
-        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.n = n
-        self.buf = torch.full((2 * self.G + n,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.t = self.buf[self.G:self.G + n].view(dtype).view(shape)
-        if fill is not None:
-            self.t.fill_(fill)
-
-    def check(self, what):
-        assert bool((self.buf[:self.G] == 0xA5).all()), f"{what}: bytes before the tensor were written"
-        assert bool((self.buf[self.G + self.n:] == 0xA5).all()), f"{what}: bytes after the tensor were written"
+dev, padc, operands, Guarded = E.dev, E.padc, E.operands, E.Guarded     # (shared with test_gpu_conv_fused_edges.py)
 
 
 @pytest.mark.parametrize("row,dtype", E.CASES, ids=E.CASE_IDS)
@@ -100,7 +63,8 @@ FUSED = ["glds_256x256_fwd_ragged", "glds_256x256_dgrad", "glds_256x128_3stage",
          "splitk_fwd_dc264", "splitk_dgrad_dc264", "halo3_min_reflect", "halo3_n3_dtail_same", "halo3_dgrad_dtail_reflect",
          "s2halo_min", "s2halo_min_deconv", "s2n_wo130", "head7_ragged", "stem7_16x32", "stem7_17x33", "narrow5_16x32",
          "narrow5_in16_16x32", "w9_min_reflect", "w9_odd_splits", "w9s_min", "rowfast_valid", "rowfast_f32_wo32", "wgrad_v2_wo65",
-         "wgrad_128x128_cr3", "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged"]
+         "wgrad_128x128_cr3", "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged",
+         "halo3_pair_n3_same", "s2halo_deconv_n3", "stem7_32x64_n2"]     # two source chunks forward; S2HALO past one tile; the stem past one tile
 FUSED_CASES = [(E.BY_NAME[n], dt) for n in FUSED for dt in E.BY_NAME[n][10]]
 
 
@@ -153,7 +117,7 @@ def test_edge_row_fused_forms_in_guard_cells(sg, row, dtype):
 # odd split count, W9S with one split).
 GROUPED = ["narrow5_16x32", "head7_16x32", "head7_ragged", "stem7_17x33", "w9_min_reflect", "w9_odd_splits", "w9_two_splits", "w9s_min",
            "w9s_lead_pad", "w9s_two_splits", "s2n_wo130", "rowfast_valid", "rowfast_f32_wo32", "wgrad_v2_wo65", "wgrad_128x128_cr3",
-           "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged"]
+           "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged", "s2halo_deconv_n3"]       # (W9S as a transposed conv)
 GROUPED_CASES = [(E.BY_NAME[n], dt) for n in GROUPED for dt in E.BY_NAME[n][10]]
 
 
