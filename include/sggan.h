@@ -229,7 +229,7 @@ int sgg_deconv2d_bwd_weight(const sgg_conv_desc* d, const void* x, const void* d
  * 8-channel input (S2N's condition -- the image input), as the workspace query does.
  * op: 0 forward, 1 data gradient, 2 weight gradient.  Returns SGG_EINVAL for a bad descriptor or op. */
 typedef enum {
-    SGG_ROUTE_REG = 1,                 /* register-staged v1 GEMM: lab builds with the DMA kernels switched off only */
+    SGG_ROUTE_REG = 1,                 /* reserved, never returned (the retired register-staged GEMM): keeps the numbers below in place */
     SGG_ROUTE_HALO3, SGG_ROUTE_S2HALO, SGG_ROUTE_S2N, SGG_ROUTE_N7, SGG_ROUTE_HALO_NARROW_IN, SGG_ROUTE_HALO_FWD,
     SGG_ROUTE_HALO_DGRAD_NARROW,
     SGG_ROUTE_GLDS_256x256, SGG_ROUTE_GLDS_256x128, SGG_ROUTE_GLDS_128x128, SGG_ROUTE_GLDS_128x64, SGG_ROUTE_GLDS_256x16,

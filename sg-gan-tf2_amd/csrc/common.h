@@ -65,6 +65,22 @@ __device__ __forceinline__ void row_swap16(float& a, float& b) {
     row_swap16(x, y);
     a = __uint_as_float(x); b = __uint_as_float(y);
 }
+// The epilogues' 16-byte bf16 store built on it: p0 / p1 are this lane's 4 channels of two pixel fragments, already rounded;
+// the result is this lane's 8 consecutive channels of one pixel (pack, then swap)
+__device__ __forceinline__ u32x4 row_swap16_pack(const bf16x4& p0, const bf16x4& p1) {
+    const u32x2 q0 = __builtin_bit_cast(u32x2, p0), q1 = __builtin_bit_cast(u32x2, p1);
+    uint32_t a0 = q0[0], a1 = q0[1], b0 = q1[0], b1 = q1[1];
+    row_swap16(a0, b0); row_swap16(a1, b1);
+    return (u32x4){a0, a1, b0, b1};
+}
+// ... with an addend chunk (the 8 bf16 of the destination pixel this lane will own): swap in f32, add, round once
+__device__ __forceinline__ u32x4 row_swap16_add_pack(float* v0, float* v1, const u32x4& addend) {
+    float ad[8], o[8];
+    ET<bf16>::unpack(addend, ad);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { row_swap16(v0[e], v1[e]); o[e] = v0[e] + ad[e]; o[4 + e] = v1[e] + ad[4 + e]; }
+    return ET<bf16>::pack(o);
+}
 
 __device__ inline u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
 __device__ inline void st16(void* p, const u32x4& v) { *reinterpret_cast<u32x4*>(p) = v; }
@@ -249,7 +265,7 @@ static inline void sgg_launch_timed(F kern, dim3 grid, dim3 block, unsigned lds,
 
 // kernel-selection switches (defaults = the shipped configuration); see sgg_config() in conv.hip
 struct SggConfig {
-    int halo3 = 1, s2halo = 1, w9 = 1, w9s2 = 1, stem_dgrad_halo = 1, wgrad_rowfast = 1, glds = 1, n7 = 1;
+    int halo3 = 1, s2halo = 1, w9 = 1, w9s2 = 1, stem_dgrad_halo = 1, wgrad_rowfast = 1, n7 = 1;
     int in_fused_maxhw = -1;      // < 0: IN_FUSED_MAXHW of norm.hip
     int ablate = 0;
 };

@@ -4,15 +4,17 @@
 // tf.pad(...,"REFLECT") in front of them (module.py:210-216,230-264,284-311) and their
 // gradients (gen_tape/disc_tape.gradient, model.py:196-197).
 //
-// Two GEMM kernels, all NHWC with channels padded to 8 so every gather is a 16-byte chunk:
-//   conv_gemm<FWD>   y[pixel][k]   = sum_{tap,c} x~[pixel,tap][c] * Wf[k][tap,c]       (gather over x)
-//   conv_gemm<DGRAD> dx[pixel][c]  = sum_{tap,k} dy[pixel,tap][k] * Wd[c][tap,k]       (transposed gather; the
-//                    stride-2 case is split into stride^2 output-parity classes so each block only visits the
-//                    taps that hit its pixels; REFLECT folds the mirrored border gradients in the gather)
-// Conv2DTranspose forward IS conv_gemm<DGRAD> of the equivalent conv (plus bias), its data gradient IS
-// conv_gemm<FWD>, its weight gradient IS the conv's with the operand roles swapped.
+// The generic GEMM, conv_gemm_glds_kernel, in two modes; all NHWC with channels padded to 8 so every gather is a 16-byte chunk:
+//   FWD    y[pixel][k]   = sum_{tap,c} x~[pixel,tap][c] * Wf[k][tap,c]       (gather over x)
+//   DGRAD  dx[pixel][c]  = sum_{tap,k} dy[pixel,tap][k] * Wd[c][tap,k]       (transposed gather; the
+//          stride-2 case is split into stride^2 output-parity classes so each block only visits the
+//          taps that hit its pixels; REFLECT reads the border pixels' gather rows pre-folded from a side tensor)
+// Conv2DTranspose forward IS the DGRAD GEMM of the equivalent conv (plus bias), its data gradient IS
+// the FWD GEMM, its weight gradient IS the conv's with the operand roles swapped.
+// Beside it: the kernels that keep a layer's halo in LDS (stride-2 3x3, the narrow 7x7 layers, D's first conv) and
+// conv_border_fold_kernel, the small second launch that adds REFLECT's mirrored terms behind two of them.
 //
-// Tile: 256 threads = 4 waves; LDS rows are 128-byte K-slices (64 bf16 / 32 f32) XOR-swizzled on the 16-byte
+// Tiles: LDS rows are 128-byte K-slices (64 bf16 / 32 f32) XOR-swizzled on the 16-byte
 // chunk index so the ds_read_b128 fragment reads are bank-conflict free; MFMA 16x16x32 bf16 (or 16x16x4 f32 on
 // the parity path, consuming the same 16-byte fragments with a k-permutation that A and B share).
 // The weight fragment is the MFMA A operand and the pixel fragment the B operand, so the accumulator holds
@@ -39,7 +41,6 @@ const SggConfig& sgg_config() {
         c.n7 = rd("SGG_N7", c.n7);                                // 7x7 64<->3 layers: (channel, tap column) in the GEMM N dimension
         c.wgrad_rowfast = rd("SGG_WGRAD_ROWFAST", c.wgrad_rowfast);
         c.in_fused_maxhw = rd("SGG_IN_FUSED_MAXHW", c.in_fused_maxhw);
-        { const char* e = getenv("SGG_CONV_IMPL"); if (e && e[0] == 'r') c.glds = 0; }   // v1 register-staged GEMMs
         c.ablate = rd("SGG_ABLATE", 0);                           // timing experiments: skips work, results are WRONG
         return c;
     }();
@@ -69,164 +70,121 @@ __device__ inline int reflect_preimages(int h, int H, int p, int* j) {
     return n;
 }
 
-template <typename T, int MODE, int BM, int BN, int WGM>
-__global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
+// -------------------------------------------------------------------------------------------------
+// Border fold: the second, small launch of a REFLECT data gradient whose main kernel (conv_halo_narrow_in_kernel or
+// conv_halo_fwd_kernel with mirrored taps) treated the padding as zeros.  It visits only the pixels MirrorPadGrad adds mirrored
+// terms to -- rows 1..p, H-1-p..H-2 (all columns), then the same columns of the remaining rows -- gathers the MIRRORED preimages
+// of each (pixel, tap) from dy, multiplies by Wd[c][tap,k] and ADDS the product to the dx the main launch stored.
+// 64 pixels x BN channels per block of 4 waves, register-staged through one LDS stage; few (pixel, tap) pairs have a mirrored
+// source, so K-tiles in which no row of the block has one are skipped.  The bands must be disjoint: H, W > 2p + 1 (launch_border).
+// -------------------------------------------------------------------------------------------------
+template <typename T, int BN, int WGM>
+__global__ __launch_bounds__(256) void conv_border_fold_kernel(ConvArgs a) {
     constexpr int VEC = ET<T>::VEC;
     constexpr int ES = (int)sizeof(T);
+    constexpr int BM = 64;
     constexpr int WGN = 4 / WGM;
     constexpr int WM = BM / WGM, WN = BN / WGN;
     constexpr int MI = WM / 16, NI = WN / 16;
     constexpr int PA = BM / 32;                 // pixel-tile chunks per thread
     constexpr int QA = (BN + 31) / 32;          // weight-tile chunks per thread
-    static_assert(BM % 32 == 0 && WM % 16 == 0 && WN % 16 == 0, "tile shape");
+    static_assert(WM % 16 == 0 && WN % 16 == 0, "tile shape");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* sP = smem;                    // [2][BM][128]
-    char* sQ = smem + 2 * BM * 128;     // [2][BN][128]
+    char* sP = smem;                    // [BM][128]
+    char* sQ = smem + BM * 128;         // [BN][128]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave index as a scalar
     const int wm = wave / WGN, wn = wave % WGN;
-    const int st = (MODE == MODE_DGRAD) ? a.stride : 1;      // tap-enumeration step
-    const int ph = (MODE == MODE_DGRAD) ? (int)blockIdx.z / a.stride : 0;
-    const int pw = (MODE == MODE_DGRAD) ? (int)blockIdx.z % a.stride : 0;
-    const int nr = ph < a.R ? (a.R - ph + st - 1) / st : 0;  // taps of this class along r / s
-    const int ns = pw < a.S ? (a.S - pw + st - 1) / st : 0;
-    const int SC = (MODE == MODE_FWD) ? a.C : a.K;           // reduction channels (source tensor)
-    static_assert(MODE == MODE_FWD || MODE == MODE_DGRAD || MODE == MODE_BORDER, "mode");
-    const int DC = (MODE == MODE_FWD) ? a.K : a.C;           // destination channels
+    const int SC = a.K, DC = a.C;                            // reduction channels (dy), destination channels (dx)
     const int cpv = SC / VEC;                                // 16-byte chunks per tap
     const int wrow = a.R * a.S * SC;                         // weight row length (elements)
-
-    // ---- destination pixel space of this block ----
-    // FWD: all output pixels.  DGRAD: the pixels of parity class (ph,pw).  BORDER: only the pixels whose gradient
-    // receives mirrored contributions (rows 1..p, H-1-p..H-2 and the same columns), or every pixel when the
-    // image is too small for those bands to be disjoint.
-    int hbase = 0, wbase = 0, Hc, Wc;
-    const int p2 = 2 * a.pad_t;
-    const bool ball = (MODE == MODE_BORDER) && (a.H <= p2 + 1 || a.W <= p2 + 1);
-    int Bimg = 0;
-    if (MODE == MODE_FWD) { Hc = a.Ho; Wc = a.Wo; }
-    else if (MODE == MODE_DGRAD) {
-        hbase = ((ph - a.pad_t) % st + st) % st;
-        wbase = ((pw - a.pad_l) % st + st) % st;
-        Hc = hbase < a.H ? (a.H - hbase + st - 1) / st : 0;
-        Wc = wbase < a.W ? (a.W - wbase + st - 1) / st : 0;
-    } else { Hc = a.H; Wc = a.W; Bimg = ball ? a.H * a.W : p2 * a.W + (a.H - p2) * p2; }
-    const int M = (MODE == MODE_BORDER) ? a.N * Bimg : a.N * Hc * Wc;
+    const int p = a.pad_t, p2 = 2 * p;
+    const int Bimg = p2 * a.W + (a.H - p2) * p2;             // border pixels per image
+    const int M = a.N * Bimg;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    if (m0 >= M) return;                                     // whole block outside this class (uniform)
+    if (m0 >= M) return;
 
-    // m -> (image, destination h, destination w); FWD returns the output pixel (ho, wo)
+    // m -> (image, h, w): the 2p border ROW bands first, then the 2p border COLUMNS of the remaining rows
     auto decode = [&](int m, int& n, int& h, int& w) {
-        if (MODE == MODE_BORDER && !ball) {
-            n = m / Bimg;
-            int q = m - n * Bimg;
-            const int p = a.pad_t;
-            if (q < p2 * a.W) {
-                int hi = q / a.W;
-                w = q - hi * a.W;
-                h = hi < p ? 1 + hi : a.H - 1 - p + (hi - p);
-            } else {
-                q -= p2 * a.W;
-                int hh = q / p2, wi = q - hh * p2;
-                h = hh == 0 ? 0 : (hh == a.H - p2 - 1 ? a.H - 1 : p + hh);
-                w = wi < p ? 1 + wi : a.W - 1 - p + (wi - p);
-            }
+        n = m / Bimg;
+        int q = m - n * Bimg;
+        if (q < p2 * a.W) {
+            int hi = q / a.W;
+            w = q - hi * a.W;
+            h = hi < p ? 1 + hi : a.H - 1 - p + (hi - p);
         } else {
-            n = m / (Hc * Wc);
-            int rem = m - n * (Hc * Wc);
-            int hp = rem / Wc;
-            h = hbase + st * hp; w = wbase + st * (rem - hp * Wc);
+            q -= p2 * a.W;
+            int hh = q / p2, wi = q - hh * p2;
+            h = hh == 0 ? 0 : (hh == a.H - p2 - 1 ? a.H - 1 : p + hh);
+            w = wi < p ? 1 + wi : a.W - 1 - p + (wi - p);
         }
     };
 
     // per-thread staging rows: row = (tid>>3) + 32*i, chunk column c = tid&7
     const int cc0 = tid & 7;
-    int rn[PA], rh[PA], rw[PA];                              // image, and the row's h/w anchor
+    int rn[PA], rh[PA], rw[PA];                              // image (-1: past the last pixel) and destination h / w
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
         int m = m0 + (tid >> 3) + 32 * i;
-        if (m < M) {
-            int n, h, w;
-            decode(m, n, h, w);
-            rn[i] = n;
-            if (MODE == MODE_FWD) { rh[i] = h * a.stride - a.pad_t; rw[i] = w * a.stride - a.pad_l; }
-            else if (MODE == MODE_DGRAD) { rh[i] = (h + a.pad_t - ph) / st; rw[i] = (w + a.pad_l - pw) / st; }
-            else { rh[i] = h; rw[i] = w; }                   // BORDER keeps destination coords; folds in the gather
-        } else rn[i] = -1;
+        rn[i] = -1;
+        if (m < M) decode(m, rn[i], rh[i], rw[i]);
     }
 
     // tap iterator of this thread's chunk column (shared by all its rows)
-    int t_cc, t_ri, t_si;
-    { int ti = cc0 / cpv; t_cc = cc0 - ti * cpv; t_ri = ns ? ti / ns : nr; t_si = ns ? ti - t_ri * ns : 0; }
-    const int ktiles = (nr * ns * cpv + 7) / 8;
+    int t_cc, t_r, t_s;
+    { int ti = cc0 / cpv; t_cc = cc0 - ti * cpv; t_r = ti / a.S; t_s = ti - t_r * a.S; }
+    const int ktiles = (a.R * a.S * cpv + 7) / 8;
 
     u32x4 regP[PA], regQ[QA];
-    bool anyP = false;                                       // BORDER: did this thread load anything for the tile
+    bool anyP = false;                                       // did this thread load anything for the tile
 
     auto load_tile = [&]() {
         anyP = false;
-        const bool tapok = t_ri < nr;
-        const int r = ph + st * t_ri, s = pw + st * t_si;
+        const bool tapok = t_r < a.R;
         // weights
 #pragma unroll
         for (int i = 0; i < QA; ++i) {
             int row = (tid >> 3) + 32 * i, dc = n0 + row;
             regQ[i] = zero16();
             if (tapok && row < BN && dc < DC)
-                regQ[i] = ld16(a.wmat + ((size_t)dc * wrow + (size_t)(r * a.S + s) * SC + t_cc * VEC) * ES);
+                regQ[i] = ld16(a.wmat + ((size_t)dc * wrow + (size_t)(t_r * a.S + t_s) * SC + t_cc * VEC) * ES);
         }
-        // pixels
+        // pixels: the sum over the MIRRORED preimages only (the direct term was written by the main launch)
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             regP[i] = zero16();
             if (!tapok || rn[i] < 0) continue;
-            if (MODE == MODE_FWD) {
-                int hi = rh[i] + r, wi = rw[i] + s;
-                bool ok = true;
-                if (a.reflect) {
-                    hi = hi < 0 ? -hi : (hi >= a.H ? 2 * (a.H - 1) - hi : hi);
-                    wi = wi < 0 ? -wi : (wi >= a.W ? 2 * (a.W - 1) - wi : wi);
-                } else ok = (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-                if (ok) regP[i] = ld16(a.src + (((size_t)rn[i] * a.H + hi) * a.W + wi) * SC * ES + t_cc * 16);
-            } else if (MODE == MODE_DGRAD) {
-                // REFLECT convs take this path too (ho = h + p - r): the mirrored contributions of the border
-                // pixels are added by the BORDER launch that follows and overwrites those pixels.
-                int ho = rh[i] - t_ri, wo = rw[i] - t_si;
-                if ((unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo)
-                    regP[i] = ld16(a.src + (((size_t)rn[i] * a.Ho + ho) * a.Wo + wo) * SC * ES + t_cc * 16);
-            } else {                                         // MirrorPadGrad fold: the MIRRORED preimages only
-                int jh[3], jw[3];
-                int nh = reflect_preimages(rh[i], a.H, a.pad_t, jh);
-                int nw = reflect_preimages(rw[i], a.W, a.pad_l, jw);
-                bool first = true;
-                for (int ia = 0; ia < nh; ++ia)
-                    for (int ib = 0; ib < nw; ++ib) {
-                        if (ia == 0 && ib == 0) continue;    // the direct term was written by the main launch
-                        int ho = jh[ia] - r, wo = jw[ib] - s;
-                        if ((unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo) {
-                            u32x4 v = ld16(a.src + (((size_t)rn[i] * a.Ho + ho) * a.Wo + wo) * SC * ES + t_cc * 16);
-                            regP[i] = first ? v : chunk_add<T>(regP[i], v);
-                            first = false;
-                        }
+            int jh[3], jw[3];
+            int nh = reflect_preimages(rh[i], a.H, a.pad_t, jh);
+            int nw = reflect_preimages(rw[i], a.W, a.pad_l, jw);
+            bool first = true;
+            for (int ia = 0; ia < nh; ++ia)
+                for (int ib = 0; ib < nw; ++ib) {
+                    if (ia == 0 && ib == 0) continue;
+                    int ho = jh[ia] - t_r, wo = jw[ib] - t_s;
+                    if ((unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo) {
+                        u32x4 v = ld16(a.src + (((size_t)rn[i] * a.Ho + ho) * a.Wo + wo) * SC * ES + t_cc * 16);
+                        regP[i] = first ? v : chunk_add<T>(regP[i], v);
+                        first = false;
                     }
-                anyP |= !first;
-            }
+                }
+            anyP |= !first;
         }
         // advance the tap iterator by one K-tile (8 chunks)
         t_cc += 8;
-        while (t_cc >= cpv) { t_cc -= cpv; if (++t_si == ns) { t_si = 0; ++t_ri; } }
+        while (t_cc >= cpv) { t_cc -= cpv; if (++t_s == a.S) { t_s = 0; ++t_r; } }
     };
-    auto store_tile = [&](int buf) {
+    auto store_tile = [&]() {
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             int row = (tid >> 3) + 32 * i;
-            st16(sP + (buf * BM + row) * 128 + ((cc0 ^ ((row >> 1) & 7)) << 4), regP[i]);
+            st16(sP + row * 128 + ((cc0 ^ ((row >> 1) & 7)) << 4), regP[i]);
         }
 #pragma unroll
         for (int i = 0; i < QA; ++i) {
             int row = (tid >> 3) + 32 * i;
-            if (row < BN) st16(sQ + (buf * BN + row) * 128 + ((cc0 ^ ((row >> 1) & 7)) << 4), regQ[i]);
+            if (row < BN) st16(sQ + row * 128 + ((cc0 ^ ((row >> 1) & 7)) << 4), regQ[i]);
         }
     };
 
@@ -238,9 +196,9 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
 
     const int frow = lane & 15, fq = lane >> 4, fsw = frow >> 1;   // fragment row / k-chunk / swizzle key
 
-    auto compute_tile = [&](int buf) {
-        const char* bP = sP + (buf * BM + wm * WM + frow) * 128;
-        const char* bQ = sQ + (buf * BN + wn * WN + frow) * 128;
+    auto compute_tile = [&]() {
+        const char* bP = sP + (wm * WM + frow) * 128;
+        const char* bQ = sQ + (wn * WN + frow) * 128;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const int off = (((fq + 4 * kk) ^ fsw) << 4);
@@ -266,56 +224,30 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
         }
     };
 
-    if (MODE == MODE_BORDER) {
-        // mirrored terms touch few (tap, pixel) pairs: skip K-tiles in which no row of the block has a source
-        for (int kt = 0; kt < ktiles; ++kt) {
-            load_tile();
-            if (!__syncthreads_or(anyP ? 1 : 0)) continue;   // also fences the previous tile's LDS reads
-            store_tile(0);
-            __syncthreads();
-            compute_tile(0);
-        }
-    } else {
-        if (ktiles > 0) { load_tile(); store_tile(0); }
+    for (int kt = 0; kt < ktiles; ++kt) {
+        load_tile();
+        if (!__syncthreads_or(anyP ? 1 : 0)) continue;       // also fences the previous tile's LDS reads
+        store_tile();
         __syncthreads();
-        for (int kt = 0; kt < ktiles; ++kt) {
-            const int buf = kt & 1;
-            if (kt + 1 < ktiles) load_tile();
-            compute_tile(buf);
-            if (kt + 1 < ktiles) store_tile(buf ^ 1);
-            __syncthreads();
-        }
+        compute_tile();
     }
 
-    // ---- epilogue: lane holds D[cout = 4*fq + e][pixel = frow] of each 16x16 tile ----
+    // ---- epilogue: lane holds D[channel = 4*fq + e][pixel = frow] of each 16x16 tile; add it to what the main launch wrote ----
 #pragma unroll
     for (int j = 0; j < MI; ++j) {
         int m = m0 + wm * WM + j * 16 + frow;
         if (m >= M) continue;
-        size_t dpix;
-        if (MODE == MODE_FWD) dpix = (size_t)m;
-        else {
-            int n, h, w;
-            decode(m, n, h, w);
-            dpix = ((size_t)n * a.H + h) * a.W + w;
-        }
+        int n, h, w;
+        decode(m, n, h, w);
+        const size_t dpix = ((size_t)n * a.H + h) * a.W + w;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             int dc = n0 + wn * WN + i * 16 + fq * 4;
             if (dc >= DC) continue;
             float v[4];
             T* o = reinterpret_cast<T*>(a.dst) + dpix * DC + dc;
-            if (MODE == MODE_BORDER) {                       // add the mirrored terms to what the main launch wrote
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + (float)o[e];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float t = acc[i][j][e] + (a.bias ? a.bias[dc + e] : 0.f);
-                    v[e] = act_apply(t, a.act, a.leak);
-                    if (a.addend) v[e] += (float)(reinterpret_cast<const T*>(a.addend) + dpix * DC + dc)[e];
-                }
-            }
+            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + (float)o[e];
             if constexpr (sizeof(T) == 2) {
                 bf16x4 pk = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
                 *reinterpret_cast<bf16x4*>(o) = pk;
@@ -327,7 +259,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// v2 GEMM kernel: direct-to-LDS staging (global_load_lds_dwordx4), single 32 KB LDS stage, ~4 blocks per CU.
+// The generic GEMM kernel: direct-to-LDS staging (global_load_lds_dwordx4), single 32 KB LDS stage, ~4 blocks per CU.
 //
 // Each wave-instruction writes 1 KiB = 8 tile rows x 128 B linearly (LDS dest = wave-uniform base + lane*16), so the
 // XOR swizzle is applied on the SOURCE side: lane (row, pos) fetches logical chunk pos ^ swz(row) and the fragment
@@ -337,9 +269,6 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
 // what the memory side delivers (PMC: the 128x128 variant was bound there at ~9 TB/s of L2 reads, 93 % hits).
 // -------------------------------------------------------------------------------------------------
 
-#ifndef GL_WIDE
-#define GL_WIDE 1                                      // epilogue with 16-byte stores (two fragments exchanged between lane rows), bf16 results
-#endif
 template <typename T, int MODE, int BM, int BN, int WGM, int NW, int BKB, int NS>
 __global__ __launch_bounds__(NW * 64) void conv_gemm_glds_kernel(ConvArgs a_in) {
     // grouped launch (a.grp == 2): blockIdx.z = group * classes + parity class; group 1 is the second network's call
@@ -611,7 +540,7 @@ __global__ __launch_bounds__(NW * 64) void conv_gemm_glds_kernel(ConvArgs a_in) 
     // uniform conditions (split-K, activation, addend) are tested once, outside the unrolled store loops
     auto epilogue = [&](auto mode_c) {
         constexpr int EP = decltype(mode_c)::value;               // -1: split-K partial; else 2 * ACT + (addend ? 1 : 0)
-        if constexpr (GL_WIDE && EP >= 0 && sizeof(T) == 2 && MI % 2 == 0) {
+        if constexpr (EP >= 0 && sizeof(T) == 2 && MI % 2 == 0) {
             // 16-byte stores (see conv3x3_halo_gemm_kernel's epilogue): pixel fragments 2 jp and 2 jp + 1 trade halves between lane
             // rows, a lane then owns 8 consecutive channels of one GEMM row -- half the store instructions, same values
             const int jo = fq & 1, cb = (fq >> 1) * 8;
@@ -637,17 +566,10 @@ __global__ __launch_bounds__(NW * 64) void conv_gemm_glds_kernel(ConvArgs a_in) 
                     }
                     u32x4 pk;
                     if constexpr (EP & 1) {
-                        float ad[8], o[8];
-                        ET<bf16>::unpack(ok ? ld16(reinterpret_cast<const bf16*>(a.addend) + dpix * DC + dc) : zero16(), ad);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { row_swap16(v0[e], v1[e]); o[e] = v0[e] + ad[e]; o[4 + e] = v1[e] + ad[4 + e]; }
-                        pk = ET<bf16>::pack(o);
+                        pk = row_swap16_add_pack(v0, v1, ok ? ld16(reinterpret_cast<const bf16*>(a.addend) + dpix * DC + dc) : zero16());
                     } else {
                         const bf16x4 p0 = {(bf16)v0[0], (bf16)v0[1], (bf16)v0[2], (bf16)v0[3]}, p1 = {(bf16)v1[0], (bf16)v1[1], (bf16)v1[2], (bf16)v1[3]};
-                        const u32x2 q0 = __builtin_bit_cast(u32x2, p0), q1 = __builtin_bit_cast(u32x2, p1);
-                        uint32_t a0 = q0[0], a1 = q0[1], b0 = q1[0], b1 = q1[1];
-                        row_swap16(a0, b0); row_swap16(a1, b1);
-                        pk = (u32x4){a0, a1, b0, b1};
+                        pk = row_swap16_pack(p0, p1);
                     }
                     if (ok) st16(reinterpret_cast<bf16*>(a.dst) + dpix * DC + dc, pk);
                 }
@@ -713,9 +635,6 @@ __global__ __launch_bounds__(NW * 64) void conv_gemm_glds_kernel(ConvArgs a_in) 
 // Output pixel (2i+a, 2j+b) of class (a,b) takes tap (r,s) with a = (r+pad_t)&1, b = (s+pad_l)&1 from dy pixel
 // (i + (a+pad_t-r)/2, j + (b+pad_l-s)/2), zero outside dy.
 // -------------------------------------------------------------------------------------------------
-#ifndef S2_WIDE
-#define S2_WIDE 1                                      // epilogue with 16-byte stores (two fragments exchanged between lane rows)
-#endif
 #define S2_TI 8
 #define S2_TJ 32
 #define S2_PITCH 40                                    // halo row pitch in pixels (34 used)
@@ -867,65 +786,32 @@ __global__ __launch_bounds__(512) void deconv_s2_halo_kernel(ConvArgs a, int tot
                 constexpr int ACT = decltype(act_c)::value;
                 auto store_tile = [&](auto add_c) {
                     constexpr bool ADD = decltype(add_c)::value;
-                    if constexpr (S2_WIDE) {
-                        // 16-byte stores: the two pixel fragments of a class trade halves between lane rows (row_swap16, see the
-                        // 3x3 halo GEMM's epilogue) -- 16 store instructions per wave and tile instead of 32; the layers this
-                        // kernel serves move more output bytes per FLOP than any other GEMM of the step
-                        const int jo = fq & 1, cb = (fq >> 1) * 8;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            const int h = 2 * (cur.i0 + wave) + (c >> 1);
-                            const int w = 2 * (cur.j0 + jo * 16 + frow) + (c & 1);
-                            const size_t dpix = ((size_t)cur.img * a.H + h) * a.W + w;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int dc = cur.n0 + i * 16 + cb;
-                                float v0[4], v1[4];
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    v0[e] = act_apply_c<ACT>(acc[c][0][i][e] + bv[i][e], a.leak);
-                                    v1[e] = act_apply_c<ACT>(acc[c][1][i][e] + bv[i][e], a.leak);
-                                }
-                                u32x4 pk;
-                                if constexpr (ADD) {
-                                    float ad[8], o[8];
-                                    ET<bf16>::unpack(ld16(reinterpret_cast<const bf16*>(a.addend) + dpix * DC + dc), ad);
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) { row_swap16(v0[e], v1[e]); o[e] = v0[e] + ad[e]; o[4 + e] = v1[e] + ad[4 + e]; }
-                                    pk = ET<bf16>::pack(o);
-                                } else {
-                                    const bf16x4 p0 = {(bf16)v0[0], (bf16)v0[1], (bf16)v0[2], (bf16)v0[3]}, p1 = {(bf16)v1[0], (bf16)v1[1], (bf16)v1[2], (bf16)v1[3]};
-                                    const u32x2 q0 = __builtin_bit_cast(u32x2, p0), q1 = __builtin_bit_cast(u32x2, p1);
-                                    uint32_t a0 = q0[0], a1 = q0[1], b0 = q1[0], b1 = q1[1];
-                                    row_swap16(a0, b0); row_swap16(a1, b1);
-                                    pk = (u32x4){a0, a1, b0, b1};
-                                }
-                                st16(reinterpret_cast<bf16*>(a.dst) + dpix * DC + dc, pk);
-                            }
-                        }
-                        return;
-                    }
+                    // 16-byte stores: the two pixel fragments of a class trade halves between lane rows (row_swap16, see the
+                    // 3x3 halo GEMM's epilogue) -- 16 store instructions per wave and tile instead of 32; the layers this
+                    // kernel serves move more output bytes per FLOP than any other GEMM of the step
+                    const int jo = fq & 1, cb = (fq >> 1) * 8;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int h = 2 * (cur.i0 + wave) + (c >> 1);
+                        const int w = 2 * (cur.j0 + jo * 16 + frow) + (c & 1);
+                        const size_t dpix = ((size_t)cur.img * a.H + h) * a.W + w;
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const int w = 2 * (cur.j0 + j * 16 + frow) + (c & 1);
-                            const size_t dpix = ((size_t)cur.img * a.H + h) * a.W + w;
+                        for (int i = 0; i < 4; ++i) {
+                            const int dc = cur.n0 + i * 16 + cb;
+                            float v0[4], v1[4];
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int dc = cur.n0 + i * 16 + fq * 4;
-                                float v[4];
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = act_apply_c<ACT>(acc[c][j][i][e] + bv[i][e], a.leak);
-                                if constexpr (ADD) {
-                                    const bf16* ad = reinterpret_cast<const bf16*>(a.addend) + dpix * DC + dc;
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] += (float)ad[e];
-                                }
-                                bf16x4 pk = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-                                *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(a.dst) + dpix * DC + dc) = pk;
+                            for (int e = 0; e < 4; ++e) {
+                                v0[e] = act_apply_c<ACT>(acc[c][0][i][e] + bv[i][e], a.leak);
+                                v1[e] = act_apply_c<ACT>(acc[c][1][i][e] + bv[i][e], a.leak);
                             }
+                            u32x4 pk;
+                            if constexpr (ADD) {
+                                pk = row_swap16_add_pack(v0, v1, ld16(reinterpret_cast<const bf16*>(a.addend) + dpix * DC + dc));
+                            } else {
+                                const bf16x4 p0 = {(bf16)v0[0], (bf16)v0[1], (bf16)v0[2], (bf16)v0[3]}, p1 = {(bf16)v1[0], (bf16)v1[1], (bf16)v1[2], (bf16)v1[3]};
+                                pk = row_swap16_pack(p0, p1);
+                            }
+                            st16(reinterpret_cast<bf16*>(a.dst) + dpix * DC + dc, pk);
                         }
                     }
                 };
@@ -1002,7 +888,7 @@ __global__ __launch_bounds__(512) void deconv_s2_stats_kernel(ConvArgs a) {
 
 static bool s2halo_ok(const ConvArgs& a, bool is_bf16) {
     const int en = sgg_config().s2halo;
-    if (!en || !is_bf16 || !use_glds() || a.ksplit > 1 || SGG_ABLATE_OF(a) || a.reflect) return false;
+    if (!en || !is_bf16 || a.ksplit > 1 || SGG_ABLATE_OF(a) || a.reflect) return false;
     if (a.R != 3 || a.S != 3 || a.stride != 2 || a.H != 2 * a.Ho || a.W != 2 * a.Wo) return false;
     if (a.pad_t != 0 || a.pad_l != 0) return false;     // TF 'SAME' with an even input pads bottom/right only
     return a.K % 64 == 0 && a.C % 64 == 0 && a.Wo % S2_TJ == 0 && a.Ho % S2_TI == 0;
@@ -1486,7 +1372,7 @@ __global__ __launch_bounds__(256) void conv3x3s2_narrow_dgrad_kernel(S2NArgs a) 
 }
 
 static bool s2n_dgrad_ok(const sgg_conv_desc* d) {
-    return use_glds() && d->dtype == SGG_BF16 && d->pad_mode == SGG_PAD_ZERO && d->R == 3 && d->S == 3 && d->stride == 2 && d->C == 8 && d->K == 64 &&
+    return d->dtype == SGG_BF16 && d->pad_mode == SGG_PAD_ZERO && d->R == 3 && d->S == 3 && d->stride == 2 && d->C == 8 && d->K == 64 &&
            d->pad_t == 0 && d->pad_l == 0 && d->H == 2 * d->Ho && d->W == 2 * d->Wo;
 }
 static int launch_s2n_dgrad(const sgg_conv_desc* d, const void* dy, const void* w, const void* w2, int nsplit, const void* addend, void* dx, hipStream_t s) {
@@ -1533,11 +1419,11 @@ static int launch_halo_fwd(const sgg_conv_desc* d, const ConvArgs& a, hipStream_
 
 // data gradient of a narrow-INPUT conv (the stem, 3->64 7x7; cycle mode back-propagates into the fake image): as a
 // convolution over dy it is the head's shape (64 -> <= 16 channels), so it runs conv_halo_fwd_kernel with mirrored taps
-// and zero padding; REFLECT's MirrorPadGrad terms are then added to the border pixels by the MODE_BORDER launch
+// and zero padding; REFLECT's MirrorPadGrad terms are then added to the border pixels by launch_border
 static bool halo_dgrad_narrow_ok(const sgg_conv_desc* d) {
     const int en = sgg_config().stem_dgrad_halo;
     const int cch = d->dtype == SGG_BF16 ? 64 : 32;
-    return en && use_glds() && d->C <= 16 && d->stride == 1 && d->R <= HALO_MAXR && d->S <= HALO_MAXR && d->R == d->S &&
+    return en && d->C <= 16 && d->stride == 1 && d->R <= HALO_MAXR && d->S <= HALO_MAXR && d->R == d->S &&
            d->Ho == d->H && d->Wo == d->W && d->pad_t == (d->R - 1) / 2 && d->pad_l == (d->S - 1) / 2 &&
            d->H % HALO_TH == 0 && d->W % HALO_TW == 0 && d->K % cch == 0;
 }
@@ -1547,9 +1433,6 @@ static bool halo_dgrad_narrow_ok(const sgg_conv_desc* d) {
 // implicit GEMM every (pixel, tap) is a separate 16-byte DMA element; here the source halo of a 16x32 tile (13 KB) and
 // the whole weight matrix (64 x 49*8, 53 KB) sit in LDS, each lane picks the chunk of ITS tap out of the halo, and
 // persistent blocks amortise the weight load.  flip = data-gradient (taps mirrored, zero fill).
-#ifndef NI_WIDE
-#define NI_WIDE 1                                      // bf16 epilogue with 16-byte stores (+ the optional norm-statistics rows)
-#endif
 template <typename T>
 __global__ __launch_bounds__(512) void conv_halo_narrow_in_kernel(ConvArgs a, int ntiles, int flip) {
     constexpr int VEC = ET<T>::VEC;
@@ -1650,7 +1533,7 @@ __global__ __launch_bounds__(512) void conv_halo_narrow_in_kernel(ConvArgs a, in
             for (int e = 0; e < 4; ++e) bv[i][e] = a.bias ? a.bias[i * 16 + fq * 4 + e] : 0.f;
         act_dispatch(a.act, [&](auto act_c) {
             constexpr int ACT = decltype(act_c)::value;
-            if constexpr (sizeof(T) == 2 && NI_WIDE) {
+            if constexpr (sizeof(T) == 2) {
                 // 16-byte stores (the two 16-column fragments of a tile row trade halves between lane rows, see conv3x3_halo_gemm_kernel) and,
                 // with a.stats, the (sum, sumsq) rows of the stored output for the instance norm behind the stem (module.py:230-233):
                 // wave butterfly -> the eight waves' rows through LDS -> ONE partial row per (image, 16 x 32 tile)
@@ -1683,10 +1566,7 @@ __global__ __launch_bounds__(512) void conv_halo_narrow_in_kernel(ConvArgs a, in
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) { const float r1 = (float)p1[e]; s1[i][e] += r1; s2[i][e] += r1 * r1; }
                             }
-                            const u32x2 q0 = __builtin_bit_cast(u32x2, p0), q1 = __builtin_bit_cast(u32x2, p1);
-                            uint32_t a0 = q0[0], a1 = q0[1], b0 = q1[0], b1 = q1[1];
-                            row_swap16(a0, b0); row_swap16(a1, b1);
-                            st16(reinterpret_cast<bf16*>(a.dst) + dpix * DCH + i * 16 + cb, (u32x4){a0, a1, b0, b1});
+                            st16(reinterpret_cast<bf16*>(a.dst) + dpix * DCH + i * 16 + cb, row_swap16_pack(p0, p1));
                         }
                     }
                     if constexpr (ST) {
@@ -1746,7 +1626,7 @@ __global__ __launch_bounds__(512) void conv_halo_narrow_in_kernel(ConvArgs a, in
 
 // src_ch / dst_ch: channel counts of the gathered tensor and of the result for the direction in question
 static bool halo_narrow_in_ok(const sgg_conv_desc* d, int src_ch, int dst_ch) {
-    return use_glds() && src_ch == 8 && dst_ch == 64 && d->stride == 1 && d->R <= HALO_MAXR && d->S <= HALO_MAXR &&
+    return src_ch == 8 && dst_ch == 64 && d->stride == 1 && d->R <= HALO_MAXR && d->S <= HALO_MAXR &&
            d->Ho == d->H && d->Wo == d->W && d->H % HALO_TH == 0 && d->W % HALO_TW == 0;
 }
 
@@ -1894,14 +1774,24 @@ static ConvArgs make_args(const sgg_conv_desc* d, const void* src, const void* w
     return a;
 }
 
-template <typename T, int MODE, int BM, int BN, int WGM>
-static int launch_gemm_cfg(const ConvArgs& a, int64_t Mmax, int DC, int classes, hipStream_t s) {
-    constexpr size_t lds = 2 * (BM + BN) * 128;
-    auto kern = conv_gemm_kernel<T, MODE, BM, BN, WGM>;
-    SGG_LDS_ATTR(kern, (int)lds);
-    dim3 grid((unsigned)((Mmax + BM - 1) / BM), (unsigned)((DC + BN - 1) / BN), (unsigned)classes);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+// REFLECT data gradient behind a main launch that padded with zeros: add the mirrored terms to the border pixels of dx
+// (conv_border_fold_kernel); few pixels and short K loops, hence the small tiles
+template <typename T>
+static int launch_border_t(const ConvArgs& a, hipStream_t s) {
+    const int64_t M = (int64_t)a.N * fold_border_per_image(a.H, a.W, a.pad_t);
+    const unsigned mtiles = (unsigned)((M + 63) / 64);
+    if (a.C > 16) {
+        hipLaunchKernelGGL((conv_border_fold_kernel<T, 64, 2>), dim3(mtiles, (unsigned)((a.C + 63) / 64)), dim3(256), (64 + 64) * 128, s, a);
+    } else {
+        hipLaunchKernelGGL((conv_border_fold_kernel<T, 16, 4>), dim3(mtiles, 1), dim3(256), (64 + 16) * 128, s, a);
+    }
     return sgg_check_launch();
+}
+static int launch_border(const sgg_conv_desc* d, const ConvArgs& a, hipStream_t s) {
+    // The kernel enumerates the border as disjoint row and column bands, which needs H, W > 2p + 1.  Both callers tile the image
+    // 16 x 32 at the same output size, where desc_ok's REFLECT rule leaves p = (R - 1) / 2 <= 3: a smaller image never gets here.
+    if (a.H <= 2 * a.pad_t + 1 || a.W <= 2 * a.pad_t + 1) return SGG_EUNSUPPORTED;
+    return d->dtype == SGG_BF16 ? launch_border_t<bf16>(a, s) : launch_border_t<float>(a, s);
 }
 
 // out[p][c] = act(sum_s partial[s][p][c] + bias[c])  (fixed order -> deterministic)
@@ -1961,20 +1851,10 @@ static int launch_glds_cfg(const ConvArgs& a, int64_t Mmax, int DC, int classes,
     return sgg_check_launch();
 }
 
-#ifndef GLDS_NS_256x128
-#define GLDS_NS_256x128 3                              // LDS stages of the 256x128 tile (48 KB each): its layers (c2 forward, d2 data gradient,
-                                                       // D.h1 forward) gather their pixel operand from HBM with 9 short K-tiles per block;
-                                                       // two tiles in flight instead of one: 96.8 -> 93.4 us (c2), 26.4 -> 25.3 us (D.h1)
-#endif
 // rows, result channels and parity classes of the GEMM a launch of `mode` runs
 static void gemm_dims(const ConvArgs& a, int mode, int& DC, int& classes, int64_t& Mmax) {
     if (mode == MODE_FWD) { DC = a.K; classes = 1; Mmax = (int64_t)a.N * a.Ho * a.Wo; }
-    else if (mode == MODE_BORDER) {
-        DC = a.C; classes = 1;
-        int p2 = 2 * a.pad_t;
-        bool all = a.H <= p2 + 1 || a.W <= p2 + 1;
-        Mmax = (int64_t)a.N * (all ? a.H * a.W : p2 * a.W + (a.H - p2) * p2);
-    } else {
+    else {
         DC = a.C; classes = a.stride * a.stride;
         Mmax = (int64_t)a.N * ((a.H + a.stride - 1) / a.stride) * ((a.W + a.stride - 1) / a.stride);
     }
@@ -1983,10 +1863,8 @@ static void gemm_dims(const ConvArgs& a, int mode, int& DC, int& classes, int64_
 // The kernel launch_gemm() runs for these arguments (an sgg_route without the split-K bit): launch_gemm switches on it and
 // sgg_conv2d_route() reports it, so there is one copy of the conditions.
 static int gemm_route(const ConvArgs& a, int mode, bool is_bf16) {
-    if (mode == MODE_BORDER) return SGG_ROUTE_REG;     // few pixels, short K loops: the small register-path tiles
     if (mode == MODE_DGRAD && s2halo_ok(a, is_bf16)) return SGG_ROUTE_S2HALO;
     if (halo3_ok(a, mode, is_bf16)) return SGG_ROUTE_HALO3;
-    if (!use_glds()) return SGG_ROUTE_REG;
     int DC, classes;
     int64_t Mmax;
     gemm_dims(a, mode, DC, classes, Mmax);
@@ -2010,7 +1888,7 @@ static int launch_gemm(const ConvArgs& a, hipStream_t s) {
     int DC, classes;
     int64_t Mmax;
     gemm_dims(a, MODE, DC, classes, Mmax);
-    if constexpr (MODE != MODE_BORDER && sizeof(T) == 2) {
+    if constexpr (sizeof(T) == 2) {
         // grouped launch of a shape whose kernel takes a STACKED batch with per-image weights (the LDS-resident 3x3 / stride-2
         // halo kernels): the two groups are contiguous, so it is that kernel on 2N images with the split at N
         if (a.grp == 2 && a.ksplit == 1 && (halo3_ok(a, MODE, true) || (MODE == MODE_DGRAD && s2halo_ok(a, true)))) {
@@ -2025,34 +1903,23 @@ static int launch_gemm(const ConvArgs& a, hipStream_t s) {
         if constexpr (MODE == MODE_DGRAD && sizeof(T) == 2) return launch_s2halo(a, s);
         break;
     case SGG_ROUTE_HALO3:
-        if constexpr (MODE != MODE_BORDER && sizeof(T) == 2) return launch_halo3(a, MODE, s);
+        if constexpr (sizeof(T) == 2) return launch_halo3(a, MODE, s);
         break;
     case SGG_ROUTE_GLDS_256x256:
-        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 256, 256, 2, 8, 128, 2>(a, Mmax, DC, classes, s);
-        break;
+        return launch_glds_cfg<T, MODE, 256, 256, 2, 8, 128, 2>(a, Mmax, DC, classes, s);
     case SGG_ROUTE_GLDS_256x128:
-        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 256, 128, 4, 8, 128, GLDS_NS_256x128>(a, Mmax, DC, classes, s);
-        break;
+        // three LDS stages (48 KB each): its layers (c2 forward, d2 data gradient, D.h1 forward) gather their pixel operand from HBM
+        // with 9 short K-tiles per block; two tiles in flight instead of one: 96.8 -> 93.4 us (c2), 26.4 -> 25.3 us (D.h1)
+        return launch_glds_cfg<T, MODE, 256, 128, 4, 8, 128, 3>(a, Mmax, DC, classes, s);
     case SGG_ROUTE_GLDS_128x128:
-        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, Mmax, DC, classes, s);
-        break;
+        return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, Mmax, DC, classes, s);
     case SGG_ROUTE_GLDS_128x64:
-        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 128, 64, 4, 4>(a, Mmax, DC, classes, s);
-        break;
+        return launch_glds_cfg<T, MODE, 128, 64, 4, 4>(a, Mmax, DC, classes, s);
     case SGG_ROUTE_GLDS_256x16:
-        if constexpr (MODE != MODE_BORDER) return launch_glds_cfg<T, MODE, 256, 16, 4, 4>(a, Mmax, DC, classes, s);
-        break;
+        return launch_glds_cfg<T, MODE, 256, 16, 4, 4>(a, Mmax, DC, classes, s);
     default: break;
     }
-    if (route != SGG_ROUTE_REG) return SGG_EUNSUPPORTED;   // (a route this instantiation has no kernel for: gemm_route never returns one)
-    if constexpr (MODE == MODE_BORDER) {               // few pixels, short K loops: small tiles for parallelism
-        if (DC >= 128) return launch_gemm_cfg<T, MODE, 64, 128, 2>(a, Mmax, DC, classes, s);
-        if (DC > 16) return launch_gemm_cfg<T, MODE, 64, 64, 2>(a, Mmax, DC, classes, s);
-        return launch_gemm_cfg<T, MODE, 64, 16, 4>(a, Mmax, DC, classes, s);
-    }
-    if (DC >= 128) return launch_gemm_cfg<T, MODE, 128, 128, 2>(a, Mmax, DC, classes, s);
-    if (DC > 16) return launch_gemm_cfg<T, MODE, 128, 64, 4>(a, Mmax, DC, classes, s);
-    return launch_gemm_cfg<T, MODE, 256, 16, 4>(a, Mmax, DC, classes, s);
+    return SGG_EUNSUPPORTED;                           // (a route this instantiation has no kernel for: gemm_route never returns one)
 }
 
 // split-K planning shared by the workspace queries and the launches
@@ -2070,8 +1937,8 @@ static GemmPlan plan_gemm(const sgg_conv_desc* d, int mode) {
         g.pdst = (size_t)d->N * d->H * d->W;
         g.ktot_max = (((d->R + st - 1) / st) * ((d->S + st - 1) / st) * (d->K / vec) + 7) / 8;
     }
-    g.ksplit = use_glds() ? conv_ksplit(g.Mmax, g.DC, g.classes, g.ktot_max) : 1;
-    if (g.ksplit > 1 && (mode == MODE_FWD || mode == MODE_DGRAD)) {
+    g.ksplit = conv_ksplit(g.Mmax, g.DC, g.classes, g.ktot_max);
+    if (g.ksplit > 1) {
         // shapes the halo-resident kernels take are never split (they only occur at sizes that fill the chip; it also
         // keeps the small parity-test shapes on the same kernels as the full-size layers)
         ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
@@ -2110,15 +1977,15 @@ static int run_gemm_route(const sgg_conv_desc* d, int mode) {
 // (run_gemm_route).  The launchers switch on these; sgg_conv2d_route() reports them.
 static int conv_fwd_head_route(const sgg_conv_desc* d) {
     if (halo_narrow_in_ok(d, d->C, d->K)) return SGG_ROUTE_HALO_NARROW_IN;   // narrow input (stem): halo + whole weight matrix resident in LDS
-    if (use_glds() && conv7_head_ok(d)) return SGG_ROUTE_N7;                     // the 7x7 head: (channel, tap column) in the GEMM N dimension
-    if (use_glds() && halo_fwd_ok(d)) return SGG_ROUTE_HALO_FWD;             // narrow output at full resolution: input halo resident in LDS
+    if (conv7_head_ok(d)) return SGG_ROUTE_N7;                     // the 7x7 head: (channel, tap column) in the GEMM N dimension
+    if (halo_fwd_ok(d)) return SGG_ROUTE_HALO_FWD;             // narrow output at full resolution: input halo resident in LDS
     return 0;
 }
 // addend: a skip gradient is joined in the epilogue; stats: the norm-backward sums are wanted
 static int conv_dgrad_head_route(const sgg_conv_desc* d, bool addend, bool stats) {
     if (!addend && halo_narrow_in_ok(d, d->K, d->C)) return SGG_ROUTE_HALO_NARROW_IN;   // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
     if (!stats && s2n_dgrad_ok(d)) return SGG_ROUTE_S2N;
-    if (!stats && use_glds() && conv7_stem_ok(d)) return SGG_ROUTE_N7;         // (addend: joined in the fold pass, before its one rounding)
+    if (!stats && conv7_stem_ok(d)) return SGG_ROUTE_N7;         // (addend: joined in the fold pass, before its one rounding)
     if (!addend && halo_dgrad_narrow_ok(d)) return SGG_ROUTE_HALO_DGRAD_NARROW;
     return 0;
 }
@@ -2130,10 +1997,9 @@ extern "C" {
 // debug aid (not part of include/sggan.h): occupancy the runtime reports for the hot kernels
 int sgg_debug_occupancy(int* out, int cap) {
     int n = 0, v = 0;
-    if (cap < 4) return SGG_EINVAL;
+    if (cap < 3) return SGG_EINVAL;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conv_gemm_glds_kernel<bf16, MODE_FWD, 256, 256, 2, 8, 128, 2>, 512, 131072); out[n++] = v;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conv_gemm_glds_kernel<bf16, MODE_DGRAD, 256, 256, 2, 8, 128, 2>, 512, 131072); out[n++] = v;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conv_gemm_kernel<bf16, MODE_FWD, 128, 128, 2>, 256, 65536); out[n++] = v;
     out[n++] = wgrad_debug_occupancy();                  // conv_wgrad_kernel<bf16, 128, 128, 2>, asked where the kernel is built
     return n;
 }
@@ -2207,7 +2073,7 @@ static size_t halo3_fwd_stats_chunks(const sgg_conv_desc* d) {           // the 
 }
 size_t sgg_conv2d_fwd_stats_chunks(const sgg_conv_desc* d) {
     if (!desc_ok(d) || d->dtype != SGG_BF16) return 0;
-    if (NI_WIDE && halo_narrow_in_ok(d, d->C, d->K)) return (size_t)(d->H / HALO_TH) * (d->W / HALO_TW);   // the stem: a row per 16 x 32 tile
+    if (halo_narrow_in_ok(d, d->C, d->K)) return (size_t)(d->H / HALO_TH) * (d->W / HALO_TW);   // the stem: a row per 16 x 32 tile
     return halo3_fwd_stats_chunks(d);
 }
 
@@ -2222,14 +2088,14 @@ int sgg_conv2d_fwd_stats(const sgg_conv_desc* d, const void* x, const void* w, c
 }
 
 static size_t fold_bytes(const sgg_conv_desc* d) {
-    if (d->pad_mode != SGG_PAD_REFLECT || !use_glds()) return 0;
+    if (d->pad_mode != SGG_PAD_REFLECT) return 0;
     size_t es = d->dtype == SGG_BF16 ? 2 : 4;
     return align_up((size_t)d->N * fold_border_per_image(d->H, d->W, d->pad_t) * d->R * d->S * d->K * es, 256);
 }
 
 size_t sgg_conv2d_bwd_data_workspace(const sgg_conv_desc* d) {
     if (!desc_ok(d)) return 0;
-    if (use_glds() && conv7_stem_ok(d)) return n7_dgrad_ws(d);
+    if (conv7_stem_ok(d)) return n7_dgrad_ws(d);
     return fold_bytes(d) + plan_gemm(d, MODE_DGRAD).ws_bytes;
 }
 
@@ -2251,8 +2117,7 @@ static int conv2d_bwd_data_impl(const sgg_conv_desc* d, const void* dy, const vo
     case SGG_ROUTE_HALO_NARROW_IN: {                     // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
         int rc0 = d->dtype == SGG_BF16 ? launch_halo_narrow_in<bf16>(d, a, 1, (hipStream_t)stream) : launch_halo_narrow_in<float>(d, a, 1, (hipStream_t)stream);
         if (rc0 || !a.reflect) return rc0;
-        // REFLECT: add the mirrored (MirrorPadGrad) terms of the border pixels with the small register-path launch
-        return d->dtype == SGG_BF16 ? launch_gemm<bf16, MODE_BORDER>(a, (hipStream_t)stream) : launch_gemm<float, MODE_BORDER>(a, (hipStream_t)stream);
+        return launch_border(d, a, (hipStream_t)stream);   // REFLECT: + the mirrored (MirrorPadGrad) terms of the border pixels
     }
     case SGG_ROUTE_S2N: return launch_s2n_dgrad(d, dy, w, nullptr, 0, addend, dx, (hipStream_t)stream);
     case SGG_ROUTE_N7: {                                 // (addend: joined in the fold pass, before its one rounding)
@@ -2275,13 +2140,13 @@ static int conv2d_bwd_data_impl(const sgg_conv_desc* d, const void* dy, const vo
         h.C = d->K; h.K = d->C; h.reflect = 0;
         int rc0 = d->dtype == SGG_BF16 ? launch_halo_fwd<bf16>(d, h, (hipStream_t)stream, 1) : launch_halo_fwd<float>(d, h, (hipStream_t)stream, 1);
         if (rc0 || !a.reflect) return rc0;
-        return d->dtype == SGG_BF16 ? launch_gemm<bf16, MODE_BORDER>(a, (hipStream_t)stream) : launch_gemm<float, MODE_BORDER>(a, (hipStream_t)stream);
+        return launch_border(d, a, (hipStream_t)stream);
     }
     default: break;                                      // the GEMM planner decides (run_gemm)
     }
     const size_t fb = fold_bytes(d);
     if (fb) {
-        // v2: pre-fold the gather rows of the border pixels, then ONE GEMM launch reads them like any other source
+        // pre-fold the gather rows of the border pixels, then ONE GEMM launch reads them like any other source
         if (!ws || ws_bytes < fb) return SGG_EWORKSPACE;
         size_t es = d->dtype == SGG_BF16 ? 2 : 4;
         int64_t total = (int64_t)d->N * fold_border_per_image(d->H, d->W, d->pad_t) * d->R * d->S * d->K * es / 16;
@@ -2299,9 +2164,7 @@ static int conv2d_bwd_data_impl(const sgg_conv_desc* d, const void* dy, const vo
     size_t ws2_bytes = ws_bytes > fb ? ws_bytes - fb : 0;
     int rc = d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_DGRAD>(d, a, ws2, ws2_bytes, (hipStream_t)stream)
                                   : run_gemm<float, MODE_DGRAD>(d, a, ws2, ws2_bytes, (hipStream_t)stream);
-    if (rc || !a.reflect || use_glds()) return rc;
-    // v1 REFLECT: a second, small launch adds the mirrored (MirrorPadGrad) terms to the border pixels
-    return d->dtype == SGG_BF16 ? launch_gemm<bf16, MODE_BORDER>(a, (hipStream_t)stream) : launch_gemm<float, MODE_BORDER>(a, (hipStream_t)stream);
+    return rc;
 }
 
 int sgg_conv2d_bwd_data(const sgg_conv_desc* d, const void* dy, const void* w, const void* addend, void* dx, void* ws, size_t ws_bytes, void* stream) {
@@ -2397,7 +2260,7 @@ int sgg_conv2d_fwd_group2(const sgg_conv_desc* d, const void* x, const void* w, 
                           void* y, int act, float leak, void* ws, size_t ws_bytes, void* stream) {
     if (!desc_ok(d) || !x || !w || !w2 || !y) return SGG_EINVAL;
     const size_t xin = tensor_bytes(d, false), yout = tensor_bytes(d, true);
-    if (!use_glds() || halo_narrow_in_ok(d, d->C, d->K) || conv7_head_ok(d) || halo_fwd_ok(d)) {
+    if (halo_narrow_in_ok(d, d->C, d->K) || conv7_head_ok(d) || halo_fwd_ok(d)) {
         int rc = sgg_conv2d_fwd(d, x, w, bias, y, act, leak, ws, ws_bytes, stream);
         return rc ? rc : sgg_conv2d_fwd(d, (const char*)x + xin, w2, bias2, (char*)y + yout, act, leak, ws, ws_bytes, stream);
     }
@@ -2415,7 +2278,7 @@ int sgg_conv2d_bwd_data_group2(const sgg_conv_desc* d, const void* dy, const voi
         d2.N = 2 * d->N;
         return launch_s2n_dgrad(&d2, dy, w, w2, d->N, addend, dx, (hipStream_t)stream);
     }
-    const bool special = !use_glds() || conv7_stem_ok(d) || (!addend && (halo_narrow_in_ok(d, d->K, d->C) || halo_dgrad_narrow_ok(d))) || fold_bytes(d) > 0;
+    const bool special = conv7_stem_ok(d) || (!addend && (halo_narrow_in_ok(d, d->K, d->C) || halo_dgrad_narrow_ok(d))) || fold_bytes(d) > 0;
     if (special) {                                       // (REFLECT shapes of the 3x3 halo kernel: sgg_conv2d_bwd_data_pair)
         int rc = sgg_conv2d_bwd_data(d, dy, w, addend, dx, ws, ws_bytes, stream);
         return rc ? rc : sgg_conv2d_bwd_data(d, (const char*)dy + yout, w2, addend ? (const char*)addend + xin : nullptr, (char*)dx + xin, ws, ws_bytes, stream);
@@ -2431,10 +2294,6 @@ int sgg_deconv2d_fwd_group2(const sgg_conv_desc* d, const void* x, const void* w
                             void* y, int act, float leak, void* ws, size_t ws_bytes, void* stream) {
     if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || !x || !w || !w2 || !y) return SGG_EINVAL;
     ConvArgs a = make_args(d, x, w, bias, y, act, leak);
-    if (!use_glds()) {
-        int rc = sgg_deconv2d_fwd(d, x, w, bias, y, act, leak, ws, ws_bytes, stream);
-        return rc ? rc : sgg_deconv2d_fwd(d, (const char*)x + tensor_bytes(d, true), w2, bias2, (char*)y + tensor_bytes(d, false), act, leak, ws, ws_bytes, stream);
-    }
     a.grp = 2; a.wmat2 = (const char*)w2; a.bias2 = bias2; a.net_src = tensor_bytes(d, true); a.net_dst = tensor_bytes(d, false);
     return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream)
                                 : run_gemm<float, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream);
@@ -2442,10 +2301,6 @@ int sgg_deconv2d_fwd_group2(const sgg_conv_desc* d, const void* x, const void* w
 int sgg_deconv2d_bwd_data_group2(const sgg_conv_desc* d, const void* dy, const void* w, const void* w2, void* dx,
                                  void* ws, size_t ws_bytes, void* stream) {
     if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || !dy || !w || !w2 || !dx) return SGG_EINVAL;
-    if (!use_glds()) {
-        int rc = sgg_deconv2d_bwd_data(d, dy, w, dx, ws, ws_bytes, stream);
-        return rc ? rc : sgg_deconv2d_bwd_data(d, (const char*)dy + tensor_bytes(d, false), w2, (char*)dx + tensor_bytes(d, true), ws, ws_bytes, stream);
-    }
     ConvArgs a = make_args(d, dy, w, nullptr, dx, SGG_ACT_NONE, 0.f);
     a.grp = 2; a.wmat2 = (const char*)w2; a.net_src = tensor_bytes(d, false); a.net_dst = tensor_bytes(d, true);
     return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
@@ -2513,7 +2368,7 @@ int sgg_deconv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const
 // Conv2DTranspose forward that also emits the per-chunk (sum, sumsq) rows of its stored output for the instance norm behind it
 // (module.py:254-260): one row per (image, 16 x 64 output-pixel tile) of the stride-2 halo kernel, from deconv_s2_stats_kernel.
 size_t sgg_deconv2d_fwd_stats_chunks(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_ZERO || !S2_WIDE) return 0;
+    if (!desc_ok(d) || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_ZERO) return 0;
     ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
     if (!s2halo_ok(a, true)) return 0;
     return (size_t)(d->Ho / S2_TI) * (d->Wo / S2_TJ);

@@ -729,7 +729,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
 // 128 | W, even H; REFLECT only forward (the REFLECT data gradient needs the mirrored border terms)
 bool halo3_ok(const ConvArgs& a, int mode, bool is_bf16) {
     const int en = sgg_config().halo3;
-    if (!en || !is_bf16 || !use_glds() || a.ksplit > 1) return false;
+    if (!en || !is_bf16 || a.ksplit > 1) return false;
     if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1 || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.W % H3_TW || (a.H & 1) || a.H < 4) return false;
     const int SC = mode == MODE_FWD ? a.C : a.K;

@@ -11,7 +11,7 @@
 #define SGG_ABLATE_OF(a) 0      // the shipped kernels carry no ablation branches
 #endif
 
-enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_BORDER = 2 };   // BORDER: dgrad of the REFLECT border pixels only
+enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 
 struct ConvArgs {
     const char* src;     // FWD: x (N,H,W,C)    DGRAD: dy (N,Ho,Wo,K)
@@ -19,7 +19,7 @@ struct ConvArgs {
     const float* bias;   // per destination channel or nullptr
     char* dst;           // FWD: y (N,Ho,Wo,K)  DGRAD: dx (N,H,W,C)
     const char* addend;  // optional tensor added to the result (same layout as dst): the skip-connection gradient
-    const char* fold;    // REFLECT DGRAD (v2): pre-folded gather rows of the border pixels [pixel][tap][K], else nullptr
+    const char* fold;    // REFLECT DGRAD: pre-folded gather rows of the border pixels [pixel][tap][K], else nullptr
     float* stats;        // halo 3x3 kernels only: per-(image, pixel chunk, channel) partial sums for the instance norm next to
                          // the conv, [N][chunks][DC][2] f32; nullptr = not wanted.  Forward: (sum, sumsq) of the output.
                          // Data gradient: (sum g, sum g*xhat) of the norm backward that consumes dx, which needs:
@@ -35,7 +35,7 @@ struct ConvArgs {
     char* nout;
     const float* ngamma2;
     const float* nbeta2;
-    float* partial;      // split-K (v2): f32 slabs [ksplit][pdst][DC]
+    float* partial;      // split-K: f32 slabs [ksplit][pdst][DC]
     int ksplit;          // 1 = no split
     const char* wmat2;   // halo 3x3 kernels, two networks on one stacked batch: images >= nsplit use wmat2 / bias2
     const float* bias2;
@@ -58,9 +58,6 @@ struct ConvArgs {
 // 16 zero bytes that out-of-range DMA lanes read instead of branching.  Internal linkage, one copy per file that uses it: the
 // library is built without relocatable device code, so a device global cannot be shared across translation units.
 static __device__ __attribute__((aligned(16))) uint32_t g_zero_page[4] = {0u, 0u, 0u, 0u};
-
-// SGG_CONV_IMPL=reg selects the v1 register-staged kernels (kept for A/B runs); default = v2 direct-to-LDS
-static inline bool use_glds() { return sgg_config().glds != 0; }
 
 // output tile and largest window of the kernels that keep a narrow layer's input halo in LDS (forward, narrow input, weight gradient)
 #define HALO_TH 16

@@ -576,7 +576,7 @@ __global__ __launch_bounds__(512) void conv_halo_wgrad_kernel(WgradArgs a, int n
 
 static bool halo_wgrad_ok(const sgg_conv_desc* d) {
     const int cch = d->dtype == SGG_BF16 ? 64 : 32;
-    return use_glds() && d->K <= 16 && d->stride == 1 && d->R <= HALO_MAXR && d->S <= HALO_MAXR && d->R * d->S <= 56 &&
+    return d->K <= 16 && d->stride == 1 && d->R <= HALO_MAXR && d->S <= HALO_MAXR && d->R * d->S <= 56 &&
            d->Ho == d->H && d->Wo == d->W && d->H % HALO_TH == 0 && d->W % HALO_TW == 0 && d->C <= 64 && d->C % cch == 0;
 }
 static int halo_wgrad_blocks(const sgg_conv_desc* d) {
@@ -1063,7 +1063,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* ws,
 
 #define S2W_BLOCKS 512                                  // persistent blocks = slabs (1024 / 2048 measured 7 / 22 % slower)
 static bool s2n_wgrad_ok(const sgg_conv_desc* d) {
-    return use_glds() && d->dtype == SGG_BF16 && d->pad_mode == SGG_PAD_ZERO && d->R == 3 && d->S == 3 && d->stride == 2 && d->C == 8 && d->K == 64 &&
+    return d->dtype == SGG_BF16 && d->pad_mode == SGG_PAD_ZERO && d->R == 3 && d->S == 3 && d->stride == 2 && d->C == 8 && d->K == 64 &&
            d->pad_t == 0 && d->pad_l == 0 && d->H == 2 * d->Ho && d->W == 2 * d->Wo;
 }
 struct S2WGrid { int units, per_block, blocks; };       // blocks = slabs
@@ -1436,7 +1436,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_halo_s2_kernel(W9SArgs a) {
 // -------------------------------------------------------------------------------------------------
 static bool w9s_ok(const sgg_conv_desc* d) {
     const int en = sgg_config().w9s2;
-    if (!en || !use_glds() || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_ZERO) return false;
+    if (!en || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_ZERO) return false;
     if (d->R != 3 || d->S != 3 || d->stride != 2 || d->H != 2 * d->Ho || d->W != 2 * d->Wo) return false;
     if ((unsigned)d->pad_t > 1u || (unsigned)d->pad_l > 1u) return false;
     // K >= 256 layers (c3 / d1) already run the 256x256 DMA kernel at the same speed (72 us); this kernel is for the
@@ -1458,7 +1458,7 @@ static int w9s_splits(const sgg_conv_desc* d) { return w9_split_rule(d, w9s_tile
 
 bool w9_ok(const sgg_conv_desc* d) {
     const int en = sgg_config().w9;
-    if (!en || !use_glds() || d->dtype != SGG_BF16) return false;
+    if (!en || d->dtype != SGG_BF16) return false;
     if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->Ho != d->H || d->Wo != d->W) return false;
     return d->W % W9_TW == 0 && d->H % 2 == 0 && d->C % 64 == 0 && d->K % 128 == 0;
 }
@@ -1483,7 +1483,7 @@ static WgradPlan plan_wgrad(const sgg_conv_desc* d, int Cr) {
     const int64_t P = (int64_t)d->N * d->Ho * d->Wo;
     WgradPlan p;
     p.slab_bytes = (size_t)d->R * d->S * d->C * d->K * sizeof(float);
-    if (use_glds() && (conv7_head_ok(d) || conv7_stem_ok(d))) {         // the two 7x7 layers with a 3-channel side
+    if (conv7_head_ok(d) || conv7_stem_ok(d)) {         // the two 7x7 layers with a 3-channel side
         const W7Plan w = w7_plan(d, conv7_stem_ok(d));
         p.route = SGG_ROUTE_W7; p.slabs = w.blocks; p.slab_bytes = 7 * 64 * 32 * sizeof(float);
         p.ws_bytes = w.slab_bytes + w.xpad_bytes;
@@ -1493,7 +1493,7 @@ static WgradPlan plan_wgrad(const sgg_conv_desc* d, int Cr) {
     else if (w9_ok(d)) { p.route = SGG_ROUTE_W9; p.slabs = w9_splits(d); }                      // 3x3 s1: x halo resident, all taps per block
     else if (w9s_ok(d)) { p.route = SGG_ROUTE_W9S; p.slabs = w9s_splits(d); }                   // 3x3 s2: the same with a parity-de-interleaved halo
     else if (s2n_wgrad_ok(d) && Cr <= 4) { p.route = SGG_ROUTE_S2N; p.slabs = s2n_wgrad_grid(d).blocks; }   // D.h0: the vector-ALU kernel, one slab per block
-    else if (use_glds() && d->K >= 256 && d->R * d->S * d->C >= 256) {   // the LDS-DMA kernel, one 8-wave block per CU: ~256 blocks in all
+    else if (d->K >= 256 && d->R * d->S * d->C >= 256) {   // the LDS-DMA kernel, one 8-wave block per CU: ~256 blocks in all
         const int bkp = bf ? 64 : 32;                                   // pixels per stage (BKP in the kernel)
         p.route = sgg_config().wgrad_rowfast && d->Wo % bkp == 0 ? SGG_ROUTE_WGRAD_V2_ROWFAST : SGG_ROUTE_WGRAD_V2;
         int64_t tiles = (int64_t)((d->R * d->S * d->C + 255) / 256) * ((d->K + 255) / 256);

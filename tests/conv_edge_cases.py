@@ -106,6 +106,11 @@ ROWS = [
     ("narrow5_17x32", "conv", 5, 1, "SAME", 64, 8, 1, 17, 32, {"bf16": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x16", 153600)}),   # the same one row taller: generic
     # narrow input: HALO_DGRAD_NARROW (the 64 -> 8 shape's data gradient is taken by HALO_NARROW_IN first)
     ("narrow5_in16_16x32", "conv", 5, 1, "SAME", 16, 64, 1, 16, 32, {"bf16": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64", 204800), "f32": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64", 204800)}),
+    # REFLECT 2: the border fold's second launch behind HALO_DGRAD_NARROW, in its 64 x 16 tile (the only test of it in bf16); one 16 x 32
+    # tile with p = 2 has two mirrored bands per side, the smallest shape whose band arithmetic differs from p = 1
+    ("narrow5_in16_reflect", "conv", 5, 1, "REFLECT-2", 16, 64, 1, 16, 32,
+     {"bf16": ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64", 204800),
+      "f32":  ("GLDS_128x64", "HALO_DGRAD_NARROW", "WGRAD_128x64", 204800)}),
     ("narrow5_in16_17x32", "conv", 5, 1, "SAME", 16, 64, 1, 17, 32, {"bf16": ("GLDS_128x64", "GLDS_256x16+SPLITK", "WGRAD_128x64", 307200)}),   # one row taller: generic
     # weight gradients
     ("w9_min_reflect", "conv", 3, 1, "REFLECT-1", 64, 128, 1, 2, 64, {"bf16": ("GLDS_128x128", "GLDS_128x64+SPLITK", "W9", 294912)}),   # H = 2: row -1 mirrors to 1 and row 2 to 0
@@ -311,12 +316,14 @@ DECONV_STATS = [("s2halo_min_deconv", 0), ("s2halo_min_deconv", 1), ("s2halo_dec
 # Two-network grouped forward / data gradient / bias gradient, by the grp == 2 path the row reaches (asserted from its route):
 # ragged last M tile; unequal stride-2 parity classes; split-K on each side (twice the single workspace); the stacked HALO3 rewrite
 # (2N images, split at N); the REFLECT fold's two launches; stacked S2HALO (as data gradient and as transposed conv forward); stacked
-# S2N; the special kernels' two launches; narrow5_in16_16x32, whose grouped data gradient an addend moves onto the generic GEMM.
+# S2N; the special kernels' two launches; narrow5_in16_16x32, whose grouped data gradient an addend moves onto the generic GEMM;
+# narrow5_in16_reflect, the same with the border fold's second launch behind each network's.
 GROUP2 = ["glds_256x256_fwd_ragged", "glds_256x128_3stage", "glds_128x128_long_k", "glds_256x256_dgrad_s2",
           "splitk_fwd_dc40", "splitk_dgrad_dc40", "splitk_fwd_dc264", "splitk_dgrad_dc264", "pointwise_c512",
           "halo3_min_same", "halo3_n3_dtail_same", "halo3_n3_dtail_reflect", "halo3_dgrad_dtail_reflect",
           "s2halo_min", "s2halo_min_deconv", "s2halo_deconv_n3", "s2n_wo5", "s2n_wo130",
-          "head7_ragged", "head7_16x32", "stem7_16x32", "stem7_17x33", "narrow5_16x32", "narrow5_in16_16x32", "deconv_ragged", "wgrad_128x64_cr3"]
+          "head7_ragged", "head7_16x32", "stem7_16x32", "stem7_17x33", "narrow5_16x32", "narrow5_in16_16x32", "narrow5_in16_reflect",
+          "deconv_ragged", "wgrad_128x64_cr3"]
 GROUP2_CASES = [(BY_NAME[n], dt) for n in GROUP2 for dt in BY_NAME[n][10]]
 TWO_NETWORK = sorted({n for n, _ in PAIRED + DECONV_STATS} | set(GROUP2) | {"halo3_pair_n3_reflect"})
 

@@ -21,7 +21,7 @@ def test_row_takes_the_route_the_table_names(row):
 def test_every_route_is_pinned_by_a_row():
     named = [r for row in E.ROWS for dtype in row[10] for r in E.row_routes(row, dtype)]
     seen = {r.split("+")[0] for r in named}
-    # REG: the register-staged GEMM, reachable only in a lab build with the DMA kernels switched off
+    # REG: a reserved number that no query returns (the retired register-staged GEMM); it keeps the other routes' numbers in place
     assert seen == set(A.ROUTE_NAMES) - {"REG"}, set(A.ROUTE_NAMES) ^ seen
     split = {r for r in named if r.endswith("+SPLITK")}
     assert split and not any(r.startswith(("HALO", "S2", "N7", "W")) for r in split)     # only the generic GEMM tiles split K

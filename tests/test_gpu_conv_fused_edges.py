@@ -263,7 +263,7 @@ REACHES = {
     "s2n_wo5": (1, "S2N", ("bf16",)), "s2n_wo130": (1, "S2N", ("bf16",)),
     "head7_ragged": (0, "N7", ("bf16",)), "head7_16x32": (1, "HALO_NARROW_IN", ("bf16", "f32")), "stem7_16x32": (0, "HALO_NARROW_IN", ("bf16", "f32")),
     "stem7_17x33": (1, "N7", ("bf16",)), "narrow5_16x32": (0, "HALO_FWD", ("bf16", "f32")),
-    "narrow5_in16_16x32": (1, "HALO_DGRAD_NARROW", ("bf16", "f32")),
+    "narrow5_in16_16x32": (1, "HALO_DGRAD_NARROW", ("bf16", "f32")), "narrow5_in16_reflect": (1, "HALO_DGRAD_NARROW", ("bf16", "f32")),
     "deconv_ragged": (0, "GLDS_128x64", ("bf16", "f32")), "wgrad_128x64_cr3": (0, "GLDS_128x64", ("bf16", "f32")),
 }
 

@@ -7,4 +7,4 @@ import sggan_amd
 L = ctypes.CDLL(sggan_amd.LIB_PATH)
 out = (ctypes.c_int * 8)()
 n = L.sgg_debug_occupancy(out, 8)
-print("occupancy (blocks/CU): glds_fwd, glds_dgrad, reg_fwd, wgrad =", list(out)[:n])
+print("occupancy (blocks/CU): glds_fwd, glds_dgrad, wgrad =", list(out)[:n])
