@@ -112,7 +112,13 @@ int sgg_conv2d_fwd_stats(const sgg_conv_desc* d, const void* x, const void* w_fw
  * ws: sgg_conv2d_bwd_data_workspace() bytes (REFLECT: pre-folded gather rows of the border pixels; small outputs: split-K slabs). */
 size_t sgg_conv2d_bwd_data_workspace(const sgg_conv_desc* d);
 /* addend (nullable, same shape/dtype as dx): dx = conv^T(dy) + addend -- the skip-connection gradient of a
- * residual block (module.py:217) folded into the epilogue. */
+ * residual block (module.py:217) folded into the epilogue.
+ * Rounding: dx (+ addend) is accumulated in f32 and rounded to the storage type ONCE, with one exception.  A bf16 REFLECT
+ * data gradient without addend on the HALO_NARROW_IN / HALO_DGRAD_NARROW routes (sgg_conv2d_route) is two launches: the
+ * main one pads with zeros and stores dx rounded to bf16, the border fold reads that value back, adds MirrorPadGrad's
+ * mirrored terms and rounds a SECOND time.  On the pixels those terms reach (rows and columns 1..p and H-1-p..H-2,
+ * W-1-p..W-2) dx is bf16(bf16(dx_zero_padded) + mirrored terms); everywhere else, on every other route (N7 folds in f32, the
+ * generic GEMM folds dy before it multiplies) and in f32 it is the once-rounded value. */
 int sgg_conv2d_bwd_data(const sgg_conv_desc* d, const void* dy, const void* w_dgrad, const void* addend, void* dx,
                         void* ws, size_t ws_bytes, void* stream);
 

@@ -77,6 +77,9 @@ __device__ inline int reflect_preimages(int h, int H, int p, int* j) {
 // of each (pixel, tap) from dy, multiplies by Wd[c][tap,k] and ADDS the product to the dx the main launch stored.
 // 64 pixels x BN channels per block of 4 waves, register-staged through one LDS stage; few (pixel, tap) pairs have a mirrored
 // source, so K-tiles in which no row of the block has one are skipped.  The bands must be disjoint: H, W > 2p + 1 (launch_border).
+// Rounding: the dx it reads back is already rounded to the storage type, and the sum is rounded again -- in bf16 the band's
+// values are bf16(bf16(dx_zero_padded) + mirrored terms), not the once-rounded dx the N7 and generic routes give for the same
+// layer (include/sggan.h states it at sgg_conv2d_bwd_data; tests/test_gpu_conv_rounding.py pins both values).  f32: exact sums stay exact.
 // -------------------------------------------------------------------------------------------------
 template <typename T, int BN, int WGM>
 __global__ __launch_bounds__(256) void conv_border_fold_kernel(ConvArgs a) {

@@ -1,6 +1,7 @@
 """The convolution edge-case table shared by test_conv_edges_cpu.py (routes, eligibility, exactness bounds, sensitivity -- no GPU),
-test_gpu_conv_edges.py (bit-exact parity of the plain calls on the device) and test_gpu_conv_fused_edges.py (the same for the fused
-and two-network forms), with the integer oracle, the exact comparison and the guard cells they share.
+test_gpu_conv_edges.py (bit-exact parity of the plain calls on the device), test_gpu_conv_fused_edges.py (the same for the fused
+and two-network forms) and test_gpu_conv_rounding.py (the one rounding of every epilogue: fractional draws, "rounding draws" below),
+with the integer oracle, the exact comparison and the guard cells they share.
 
 Every row is the smallest shape at which one route's index arithmetic can go wrong: a ragged last M tile, a channel tail
 of one 8-channel granule, an odd parity class, the minimum a predicate admits and the first shape on either side of it.
@@ -261,6 +262,130 @@ def expected(name):
     for a in vars(e).values():
         a.setflags(write=False)
     return e
+
+
+# ---------------------------------------------------------------------------------------------------------------- rounding draws
+# The draws of test_gpu_conv_rounding.py: the ONE rounding of every epilogue.  x and dy stay in {-1, 0, 1} (so REFLECT's pre-fold, which
+# stores sums of up to four dy values in the operand type, stays exact); weights, bias and addend carry FRAC[dtype] fraction bits:
+#   bf16: w = k/128 with |k| <= 128 (exact in bf16), bias = k/128 in [-2, 2], addend = k/8 in [-3, 3]
+#   f32:  w = k/4096 with |k| <= 4096 (12-13 significant bits: more than bf16 or a 10-bit-mantissa operand path holds), bias and addend
+#         likewise k/4096
+# Every product is a multiple of 2^-f, so where sum |terms| 2^f < 2^24 per output element (bias and addend included) the f32
+# accumulation is exact in ANY order and split, the float64 oracle is exact too, and the stored value is ONE round-to-nearest-even of
+# it: store().  sum |terms| is the oracle run on |x|, |w|, |b|, |dy| (test_conv_edges_cpu.py asserts the bound for every case used).
+FRAC = {"bf16": 7, "f32": 12}
+# Two rows with 3 real channels on one side: 27 terms leave most sums below 2, where bf16 holds every multiple of 1/128, and the draw
+# above misses a discrimination floor of test_conv_edges_cpu.py -- s2n_wo130: 23.7 % of y change under store (floor 25 %);
+# wgrad_128x16_kr3: 21.8 % of dx (floor 25 %).  Their draw has no zeros in x and dy and no weight below 1/2: |w| < 1/2 is moved to
+# |w| + 1/2.  (The other 3-channel rows keep the common draw: wgrad_128x128_cr3 25.1 % of y, wgrad_128x64_cr3 10.4 % from truncation.)
+ROUND_THIN = {"s2n_wo130", "wgrad_128x16_kr3"}
+# REFLECT rows whose bf16 data gradient is a narrow halo kernel on zero padding plus conv_border_fold_kernel, which rounds a second time
+FOLD_TWICE = ["narrow5_in16_reflect", "head7_16x32"]
+
+
+@functools.lru_cache(maxsize=3)
+def rounding(name, dtype, net=""):
+    """Inputs, exact results and sum |terms| (y_abs, dx_abs) of a row's rounding draw, seeded by name + "/round" (network B of the
+    two-network forms: + "/B"): never written to, and evaluated once for the tests of a case that run next to each other
+    (test_gpu_conv_rounding.py groups the tests of a case through a module-scoped parametrised fixture)."""
+    row = BY_NAME[name]
+    _, kind, R, _, _, Ci, Co, N, H, W, _ = row
+    q = 2 ** FRAC[dtype]
+    rng = seeded(name, "round" + net)
+    x = ints(rng, (N, H, W, Ci))
+    b = ints(rng, (Co,), -2 * q, 2 * q) / q
+    w = ints(rng, (R, R, Ci, Co) if kind == "conv" else (R, R, Co, Ci), -q, q) / q
+    e = run_oracle(row, x, b, w, rng)
+    if name in ROUND_THIN:
+        x = np.where(x == 0, 2 * ints(rng, x.shape, 0, 1) - 1, x)
+        w = np.where(np.abs(w) < 0.5, np.where(w < 0, w - 0.5, w + 0.5), w)
+        e = run_oracle(row, x, b, w, dy=np.where(e.dy == 0, 2 * ints(rng, e.dy.shape, 0, 1) - 1, e.dy))
+    m = run_oracle(row, np.abs(x), np.abs(b), np.abs(w), dy=np.abs(e.dy))
+    e.x, e.b, e.w, e.y_abs, e.dx_abs = x, b, w, m.y, m.dx
+    del e.dw, e.db                                       # (not part of these cases: wgrad_rounding())
+    for a in vars(e).values():
+        a.setflags(write=False)
+    e.f = FRAC[dtype]
+    return e
+
+
+def frac_addend(name, shape, dtype):
+    """The fractional addend of a row's data gradient: k/8 in [-3, 3] in bf16 (exact there), k/4096 in [-3, 3] in f32."""
+    q = 8 if dtype == "bf16" else 4096
+    return ints(seeded(name, "round/addend"), shape, -3 * q, 3 * q) / q
+
+
+def frac_addend_f32(name, shape):
+    """The f32 addend of the mixed form: addend_f32's odd integers (bf16 holds none) plus k/4096 with |k| < 4096."""
+    return addend_f32(name, shape) + ints(seeded(name, "round/addend_f32"), shape, -4095, 4095) / 4096
+
+
+def truncate(a, dtype):
+    """What an epilogue that TRUNCATES (drops the low mantissa bits of the f32 value) instead of rounding to nearest even stores."""
+    t = torch.tensor(np.asarray(a, np.float64)).to(torch.float32)
+    if dtype == torch.bfloat16:
+        t = (t.view(torch.int32) & -65536).view(torch.float32)
+    return t.to(torch.float64).numpy()
+
+
+def lrelu_f32(v, leak):
+    """The kernels' LeakyReLU on an exact f32 pre-activation: v > 0 ? v : float32(leak) * float32(v), one f32 rounding of the product."""
+    v32 = np.asarray(v, np.float64).astype(np.float32)
+    assert np.array_equal(v32.astype(np.float64), v)
+    return np.where(v32 > 0, v32, np.float32(leak) * v32).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=2)
+def fold_two_step(name):
+    """The bf16 data gradient of a FOLD_TWICE row as the narrow halo routes compute it: the main launch pads with zeros and stores
+    store(dx_zero); conv_border_fold_kernel reads that, adds the mirrored terms dx_reflect - dx_zero and rounds AGAIN.  Returns
+    (band, value): band marks the elements where the REFLECT and the zero-padding oracle differ; off it the value is store(dx)."""
+    row = BY_NAME[name]
+    e = rounding(name, "bf16")
+    assert row[1] == "conv" and row[3] == 1 and row[4].startswith("REFLECT")
+    zero = run_oracle(row[:4] + ("SAME",) + row[5:], e.x, e.b, e.w, dy=e.dy)
+    assert zero.y.shape == e.y.shape
+    mirrored = e.dx - zero.dx
+    band = mirrored != 0
+    bf = torch.bfloat16
+    two = np.where(band, store(store(zero.dx, bf) + mirrored, bf), store(e.dx, bf))
+    band.setflags(write=False)
+    two.setflags(write=False)
+    return band, two
+
+
+def round_paired(name, nsplit, field):
+    """paired() of the rounding draws: images below nsplit from network A's tensor, the others from B's (an N = 1 row: A then B)."""
+    a, b = getattr(rounding(name, "bf16"), field), getattr(rounding(name, "bf16", "/B"), field)
+    return np.concatenate([a, b]) if a.shape[0] == 1 else np.concatenate([a[:nsplit], b[nsplit:]])
+
+
+@functools.lru_cache(maxsize=2)
+def wgrad_rounding(name):
+    """The weight-gradient draw of an f32 row: x = k/2^f in [-1, 1], dy in {-1, 0, 1}, with the largest f <= 12 at which
+    sum |x| |dy| 2^f < 2^24 holds for every element of dw (dw_abs: the oracle on |x|, |dy|), so dw is exact in f32 in any order and
+    split.  k is drawn at 12 bits and truncated towards zero to f bits; `above` is sum |terms| of the draw at f + 1 bits, which
+    missed the bound (None at f = 12)."""
+    row = BY_NAME[name]
+    _, kind, R, _, _, Ci, Co, N, H, W, _ = row
+    rng = seeded(name, "round/wgrad")
+    k = ints(rng, (N, H, W, Ci), -4096, 4096)
+    w = np.zeros((R, R, Ci, Co) if kind == "conv" else (R, R, Co, Ci))
+    b = np.zeros(Co)
+    e = run_oracle(row, k / 4096, b, w, rng)
+    dy, top, above = e.dy, None, None
+    for f in range(12, 0, -1):
+        x = np.trunc(k / 2 ** (12 - f)) / 2 ** f
+        above, top = top, np.abs(run_oracle(row, np.abs(x), b, w, dy=np.abs(dy)).dw).max()
+        if top * 2 ** f < 2 ** 24:
+            break
+    if f < 12:
+        e = run_oracle(row, x, b, w, dy=dy)
+    c = NS(x=x, dy=dy, dw=e.dw)
+    for a in vars(c).values():
+        a.setflags(write=False)
+    c.f, c.dw_abs, c.above = f, top, above
+    return c
 
 
 def inputs_b(row):

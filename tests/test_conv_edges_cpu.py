@@ -1,7 +1,8 @@
 """Host-side half of the convolution edge-case tests (no GPU): the route every row of tests/conv_edge_cases.py takes, the
 exactness precondition of its integer oracle, and a proof that the exact comparison can fail where the tolerance of
 test_gpu_ops.py cannot; the fused forms each row has (statistics epilogues, paired form, normalise on load, mixed precision) and the
-exactness bounds of the draws test_gpu_conv_fused_edges.py runs them on."""
+exactness bounds of the draws test_gpu_conv_fused_edges.py runs them on; the exactness bound and the discrimination of the fractional
+draws test_gpu_conv_rounding.py pins every epilogue's one rounding with."""
 import ctypes
 
 import numpy as np
@@ -294,3 +295,170 @@ def test_exact_sums_see_a_dropped_statistics_row():
         if name == "s2halo_deconv_n3":
             assert 0.05 < ((ys != 0) & (np.abs(ys) < tol1) & (ys * ys < tol2)).mean() < 0.10
     assert inside_sum["s2halo_deconv_n3"] >= 1 and sum(inside_sum.values()) == inside_sum["s2halo_deconv_n3"]
+
+
+# ------------------------------------------------------------------------------------------------------------ rounding draws
+# The draws of test_gpu_conv_rounding.py (conv_edge_cases.rounding), on the oracle alone: the exactness bound that makes store() of
+# the float64 result THE expected value, and proof that each draw tells the faulty epilogues from the right one.
+from tests import test_gpu_conv_rounding as RD          # noqa: E402  (module level: lists only, nothing touches a device)
+
+BF = torch.bfloat16
+
+
+def _share(a, b):
+    return float((a != b).mean())
+
+
+def _sig_bits(a, bits):
+    """a rounded to `bits` significant bits (round to nearest): what an operand path with that mantissa makes of it."""
+    m, ex = np.frexp(a)
+    return np.ldexp(np.round(m * 2.0 ** bits) / 2.0 ** bits, ex)
+
+
+def test_rounding_helpers():
+    one = np.array([1.0, 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), 1 + 2.0 ** -7 + 2.0 ** -9, 0.0])
+    assert np.array_equal(E.store(one, BF), [1, 1, 1 + 2.0 ** -6, -1, 1 + 2.0 ** -7, 0])           # ties to even
+    assert np.array_equal(E.truncate(one, BF), [1, 1, 1 + 2.0 ** -7, -1, 1 + 2.0 ** -7, 0])        # towards zero
+    assert np.array_equal(E.truncate(one, torch.float32), one)
+    v = np.array([3.0, -3.0, -0.0078125, 0.0])
+    assert np.array_equal(E.lrelu_f32(v, 0.5), [3, -1.5, -0.00390625, 0])
+    l2 = E.lrelu_f32(v, 0.2)                                                                       # 0.2 is not exact in binary: one f32 product
+    assert l2[1] == float(np.float32(0.2) * np.float32(-3.0)) and l2[1] != -3.0 * 0.2
+    assert np.array_equal(_sig_bits(np.array([4095 / 4096, 0.5, 3 / 4096]), 11), [1.0, 0.5, 3 / 4096])
+
+
+def _draws():
+    """Every (row, dtype, network) draw test_gpu_conv_rounding.py evaluates: its forward / data-gradient cases, the bf16 draws of the
+    statistics, norm-backward and mixed-precision rows, and network B of the two-network transposed-conv statistics."""
+    d = [(r[0], dt, "") for r, dt in RD.CASES_AB]
+    d += [(n, "bf16", "") for n in E.STATS_FWD + E.STATS_BWD + [n for n, _ in E.DECONV_STATS]]
+    d += [(n, "bf16", "/B") for n, k in E.DECONV_STATS if k]
+    return list(dict.fromkeys(d))
+
+
+_DRAWS = _draws()
+
+
+@pytest.mark.parametrize("name,dtype,net", _DRAWS, ids=[f"{n}-{dt}{net.replace('/', '-')}" for n, dt, net in _DRAWS])
+def test_rounding_draw_is_exact_and_discriminating(name, dtype, net):
+    """Exactness: sum |terms| 2^f < 2^24 for y (bias included), dx and dx + addend, every value a multiple of 2^-f.
+    Discrimination: at least 25 % of y and of dx change under store, at least 10 % differ from truncation and at least 10 % from
+    adding the bias after the rounding.  In bf16 the store is the row's own; an f32 row stores its exact result unchanged
+    (asserted), so there the floors are taken against bf16 -- the format a faulty path would pass through -- and a quarter of the
+    weights does not survive an 11-significant-bit operand (a 10-bit mantissa)."""
+    row = E.BY_NAME[name]
+    e = E.rounding(name, dtype, net)
+    q = 2.0 ** e.f
+    assert e.f == E.FRAC[dtype] and set(np.unique(e.x)) <= {-1, 0, 1} and set(np.unique(e.dy)) <= {-1, 0, 1}
+    for a in (e.w, e.b, e.y, e.dx):
+        assert np.array_equal(a * q, np.round(a * q))
+    assert np.abs(e.w).max() <= 1 and np.abs(e.b).max() <= 2
+    assert np.array_equal(E.store(e.w, E.DTYPES[dtype]), e.w)
+    assert (np.abs(e.y) <= e.y_abs).all() and (np.abs(e.dx) <= e.dx_abs).all()
+    assert e.y_abs.max() * q < 2 ** 24 and e.dx_abs.max() * q < 2 ** 24
+    if row[1] == "conv":
+        add = E.frac_addend(name, e.x.shape, dtype)
+        assert np.abs(add).max() <= 3 and np.array_equal(E.store(add, E.DTYPES[dtype]), add) and np.array_equal(add * q, np.round(add * q))
+        assert (e.dx_abs + np.abs(add)).max() * q < 2 ** 24
+        assert _share(E.store(e.dx + add, BF), e.dx + add) >= 0.25
+    if dtype == "f32":
+        assert np.array_equal(E.store(e.y, torch.float32), e.y) and np.array_equal(E.store(e.dx, torch.float32), e.dx)
+        assert _share(_sig_bits(e.w, 11), e.w) >= 0.2
+    ys = E.store(e.y, BF)
+    shares = (_share(ys, e.y), _share(E.store(e.dx, BF), e.dx), _share(E.truncate(e.y, BF), ys),
+              _share(E.store(E.store(e.y - e.b, BF) + e.b, BF), ys))
+    print(f"{name}[{dtype}]{net}: bound y {e.y_abs.max() * q / 2 ** 24:.4f} dx {e.dx_abs.max() * q / 2 ** 24:.4f} of 2^24; "
+          f"store changes y {shares[0]:.2f} dx {shares[1]:.2f}, truncation differs {shares[2]:.2f}, bias after rounding {shares[3]:.2f}")
+    assert shares[0] >= 0.25 and shares[1] >= 0.25 and shares[2] >= 0.10 and shares[3] >= 0.10, shares
+    # LeakyReLU 0.2 and its misplacement behind the rounding (bf16 rows; the f32 product is rounded once more on the way out)
+    if dtype == "bf16":
+        l = E.lrelu_f32(e.y, RD.LEAK)
+        assert _share(E.store(E.lrelu_f32(ys, RD.LEAK), BF), E.store(l, BF)) >= 0.03
+
+
+def test_reduced_operand_precision_changes_an_f32_row():
+    """What the operand-precision check of the f32 rows sees: the same row with its weights at 11 significant bits (or at bf16's 8)
+    differs from the exact result in nearly every element."""
+    name = "splitk_fwd_dc40"
+    e = E.rounding(name, "f32")
+    for w in (_sig_bits(e.w, 11), E.store(e.w, BF)):
+        p = E.run_oracle(E.BY_NAME[name], e.x, e.b, w, dy=e.dy)
+        assert _share(p.y, e.y) > 0.9 and _share(p.dx, e.dx) > 0.9
+
+
+_STAT_NETS = sorted({(n, "") for n in E.STATS_FWD} | {(n, "") for n, _ in E.DECONV_STATS} | {(n, "/B") for n, k in E.DECONV_STATS if k})
+
+
+@pytest.mark.parametrize("name,net", _STAT_NETS, ids=[n + net.replace("/", "-") for n, net in _STAT_NETS])
+def test_rounding_statistics_sums_are_exact_and_see_the_store(name, net):
+    """sum y_s: stored values are multiples of 1/128, sum |y_s| 128 < 2^24 per (image, channel), so f32 holds every partial sum in any
+    order.  The sum of the stored y differs from the sum of the exact y in at least 90 % of the pairs: rows summed from the accumulator
+    cannot pass.  (sum y_s^2 is compared at a derived tolerance: test_gpu_conv_rounding.sums_of_stored.)"""
+    e = E.rounding(name, "bf16", net)
+    ys = E.store(e.y, BF)
+    assert np.array_equal(ys * 128, np.round(ys * 128)) and np.abs(ys).sum((1, 2)).max() * 128 < 2 ** 24
+    assert _share(ys.sum((1, 2)), e.y.sum((1, 2))) >= 0.9
+    assert _share(E.stat_sums(ys)[..., 1], E.stat_sums(e.y)[..., 1]) >= 0.9
+    if net:
+        a = E.rounding(name, "bf16")
+        for f in ("x", "w", "b", "y"):
+            assert _share(getattr(a, f), getattr(e, f)) > 0.5, (name, f)
+
+
+@pytest.mark.parametrize("name", E.STATS_BWD)
+def test_rounding_norm_backward_and_mixed_draws_are_exact(name):
+    e, c = E.rounding(name, "bf16"), E.norm_bwd_case(name)
+    add = E.frac_addend(name, e.x.shape, "bf16")
+    for dx in (e.dx, e.dx + add):
+        dxs = E.store(dx, BF)
+        assert _share(dxs, dx) >= 0.25
+        # g = dx_s act'(z) is a multiple of 1/256 (act' = 0.5), x an integer; the kernel sums g and g x and forms rstd (sum g x - mean
+        # sum g) with |mean| <= 1 and rstd a power of two: every partial sum is a multiple of 1/256 below 2^24 of them
+        assert (np.abs(dxs) * (np.abs(c.nx) + 1)).sum((1, 2)).max() * 256 < 2 ** 24
+        for act, leak in (("none", 0.0), ("relu", 0.0), ("lrelu", 0.5)):
+            s, sx = E.norm_bwd_sums(dxs, c, act, leak), E.norm_bwd_sums(dx, c, act, leak)
+            assert np.array_equal(s * 512, np.round(s * 512)) and np.array_equal(E.store(s, torch.float32), s)
+            assert _share(s[..., 0], sx[..., 0]) >= 0.75           # sums formed from the unrounded dx differ (relu: some channels sum nothing)
+    # mixed precision: dx in units of 1/128 plus an addend in units of 1/4096 around +-1001, exact in f32 and not in bf16
+    big = E.frac_addend_f32(name, e.x.shape)
+    assert np.abs(big).min() > 1000 and np.array_equal(big * 4096, np.round(big * 4096))
+    assert (e.dx_abs + np.abs(big)).max() * 4096 < 2 ** 24
+    for a in (e.dx, e.dx + add, e.dx + big):
+        assert np.array_equal(E.store(a, torch.float32), a) and _share(E.store(a, BF), a) >= 0.25
+    assert (E.store(big, BF) != big).all()
+
+
+@pytest.mark.parametrize("name", E.FOLD_TWICE)
+def test_border_fold_rounds_a_second_time_on_its_band(name):
+    """The documented exception: in bf16 these REFLECT rows' data gradient is store(store(dx_zero) + mirrored terms) on the band the
+    mirrored terms reach.  The two candidates differ there, so the device test tells them apart; off the band they are the same."""
+    row = E.BY_NAME[name]
+    assert E.row_routes(row, "bf16")[1] in ("HALO_NARROW_IN", "HALO_DGRAD_NARROW") and row[4].startswith("REFLECT")
+    assert name in RD.ROWS_AB
+    band, two = E.fold_two_step(name)
+    one = E.store(E.rounding(name, "bf16").dx, BF)
+    p = int(row[4].split("-")[1])
+    inner = np.zeros(band.shape, bool)
+    inner[:, 2 * p + 1:-(2 * p + 1), 2 * p + 1:-(2 * p + 1)] = True
+    assert band.any() and not (band & inner).any()       # rows and columns 1..p and their mirror images only (0..2p bounds them)
+    assert np.array_equal(two[~band], one[~band])
+    print(f"{name}: {int((two != one).sum())} of {int(band.sum())} band elements differ between one and two roundings")
+    assert (two != one)[band].any()
+
+
+def test_weight_gradient_rounding_rows():
+    """The f32 weight-gradient draw: the rows test_gpu_conv_rounding.py leaves out are exactly those whose bound holds fewer than 9
+    fraction bits, at most half of the f32 rows."""
+    assert RD.WGRAD_ROWS and all("f32" in E.BY_NAME[n][10] for n in RD.WGRAD_ROWS)
+    assert 2 * len(RD.WGRAD_LEFT_OUT) <= len(RD.WGRAD_ROWS) and set(RD.WGRAD_LEFT_OUT) <= set(RD.WGRAD_ROWS)
+    for name in RD.WGRAD_ROWS:
+        c = E.wgrad_rounding(name)
+        q = 2.0 ** c.f
+        print(f"{name}: f = {c.f}, sum |terms| 2^f = {c.dw_abs * q / 2 ** 24:.3f} of 2^24")
+        assert c.f <= 12 and c.dw_abs * q < 2 ** 24 and ((c.above is None) if c.f == 12 else c.above * 2 * q >= 2 ** 24)
+        assert np.array_equal(c.x * q, np.round(c.x * q)) and np.abs(c.x).max() <= 1 and set(np.unique(c.dy)) <= {-1, 0, 1}
+        assert np.array_equal(E.store(c.dw, torch.float32), c.dw) and np.abs(c.dw).max() <= c.dw_abs
+        assert (c.f < RD.WGRAD_MIN_F) == (name in RD.WGRAD_LEFT_OUT), (name, c.f)
+        if c.f >= RD.WGRAD_MIN_F:                         # x needs more bits than a bf16 operand holds (f = 12: than a 10-bit mantissa)
+            assert _share(E.store(c.x, BF), c.x) >= 0.4 and _share(E.store(c.dw, BF), c.dw) >= 0.9
+            assert c.f < 12 or _share(_sig_bits(c.x, 11), c.x) >= 0.2
