@@ -22,7 +22,6 @@ template <typename T> using InAcc = typename std::conditional<std::is_same<T, fl
 // the first, the rest to the second -- the cycle step's G_A->B / G_B->A and D_A / D_B pairs): the norm is per image, so one
 // launch serves both and only the affine parameters (and their gradients) are picked by image index.  nsplit >= N: one network.
 struct InSplit { const float* gamma2; const float* beta2; float* dgamma2; float* dbeta2; int nsplit; };
-static inline InSplit in_nosplit() { InSplit s; s.gamma2 = nullptr; s.beta2 = nullptr; s.dgamma2 = nullptr; s.dbeta2 = nullptr; s.nsplit = 0x7fffffff; return s; }
 
 // The incoming gradient dy normally has the tensor's storage type T.  Mixed mode (bf16 tensors, f32 gradient chain): dy is
 // f32 -- the VEC channels of a 16-byte chunk of x are then two 16-byte chunks of dy.  `elem` = element index of the chunk.
@@ -558,17 +557,173 @@ __global__ __launch_bounds__(256) void in_skip_bwd_partial_kernel(const char* x,
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Host side.  Every entry point fills one InCall and runs in_forward or in_backward, which validate, carve the workspace
+// (partial[N][chunks][C][2], absent when the caller brings the rows; then sums[N][C][2] and tot[N][C][2], backward only) and
+// derive the grids once, then launch the passes the call's fields select.  DESIGN.md section 3 has the table of forms.
+// -------------------------------------------------------------------------------------------------
+struct InCall {
+    const void* x = nullptr; const float* gamma = nullptr; const float* beta = nullptr;
+    float* stats = nullptr;                        // (mean, rstd)[N][C]: written forward, read backward
+    void* out = nullptr;                           // y forward, dx backward
+    int N = 0; int64_t HW = 0; int C = 0; float eps = 0.f; int act = SGG_ACT_NONE; float leak = 0.f; int dtype = SGG_F32;
+    void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
+    bool pair = false; InSplit sp = {nullptr, nullptr, nullptr, nullptr, 0x7fffffff};      // one network unless in_pair() fills it
+    bool with_skip = false;                        // y = act(gamma*xhat + beta + skip): addend is the skip; backward takes y_in, writes dskip
+    const void* addend = nullptr;                  // forward: the residual (added after the activation; optional) or the skip
+    const void* y_in = nullptr; void* dskip = nullptr;
+    bool with_partial = false; const float* partial = nullptr; int chunks = 0;             // statistics rows of the producing conv
+    const void* dy = nullptr; bool dy_f32 = false; // backward; dy_f32: mixed mode (bf16 tensors, f32 gradient)
+    float* dgamma = nullptr; float* dbeta = nullptr; int C_real = 0, accumulate = 0;
+};
+static InCall in_fwd_call(const void* x, const float* gamma, const float* beta, const void* addend, bool with_skip, void* y, float* stats,
+                          int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    InCall c;
+    c.x = x; c.gamma = gamma; c.beta = beta; c.addend = addend; c.with_skip = with_skip; c.out = y; c.stats = stats; c.N = N; c.HW = HW; c.C = C;
+    c.eps = eps; c.act = act; c.leak = leak; c.dtype = dtype; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+    return c;
+}
+static InCall in_bwd_call(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx, float* dgamma,
+                          float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak, int dtype,
+                          void* ws, size_t ws_bytes, void* stream) {
+    InCall c;
+    c.dy = dy; c.x = x; c.gamma = gamma; c.beta = beta; c.stats = (float*)stats; c.out = dx; c.dgamma = dgamma; c.dbeta = dbeta; c.N = N; c.HW = HW;
+    c.C = C; c.C_real = C_real; c.accumulate = accumulate; c.act = act; c.leak = leak; c.dtype = dtype; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+    return c;
+}
+static void in_rows(InCall& c, const float* partial, int chunks) { c.with_partial = true; c.partial = partial; c.chunks = chunks; }
+// two networks on one stacked batch, for forward and backward alike (forward: no dgamma2 / dbeta2)
+static void in_pair(InCall& c, const float* gamma2, const float* beta2, float* dgamma2, float* dbeta2, int nsplit) {
+    c.pair = true; c.sp.gamma2 = gamma2; c.sp.beta2 = beta2; c.sp.dgamma2 = dgamma2; c.sp.dbeta2 = dbeta2; c.sp.nsplit = nsplit;
+}
+static inline bool in_pair_ok(const InCall& c) { return !c.pair || (c.sp.gamma2 && c.sp.beta2 && c.sp.nsplit > 0 && c.sp.nsplit < c.N); }
+
 static bool in_use_fused(int64_t HW) {
     const int mx = sgg_config().in_fused_maxhw;
     return HW <= (mx >= 0 ? mx : IN_FUSED_MAXHW);
 }
 
-static int in_rows_per_block(int N, int64_t HW, int C, int vec) {
+static int in_rows_per_block(int N, int64_t HW) {
     // aim for >= 2048 blocks of >= 64 pixels
     int64_t r = HW * N / 2048;
     if (r < 64) r = 64;
     if (r > 4096) r = 4096;
     return (int)r;
+}
+static inline dim3 in_apply_grid(const InCall& c, int rpb) { return dim3((unsigned)((c.HW + rpb - 1) / rpb), c.N); }
+
+// ---- the instantiation a call's dtype selects, one helper per kernel family (the specialisations of a family share one type)
+static auto in_partial_fn(const InCall& c, bool bwd) {
+    if (c.dtype == SGG_F32) return bwd ? in_partial_kernel<float, true> : in_partial_kernel<float, false>;
+    if (c.dy_f32) return in_partial_kernel<bf16, true, float>;
+    return bwd ? in_partial_kernel<bf16, true> : in_partial_kernel<bf16, false>;
+}
+static auto in_apply_fn(const InCall& c, bool bwd) {
+    if (c.dtype == SGG_F32) return bwd ? in_apply_kernel<float, true> : in_apply_kernel<float, false>;
+    if (c.dy_f32) return in_apply_kernel<bf16, true, float>;
+    return bwd ? in_apply_kernel<bf16, true> : in_apply_kernel<bf16, false>;
+}
+static auto in_fused_fn(const InCall& c, bool bwd) {
+    if (c.dtype == SGG_F32) return bwd ? in_fused_small_kernel<float, true> : in_fused_small_kernel<float, false>;
+    return bwd ? in_fused_small_kernel<bf16, true> : in_fused_small_kernel<bf16, false>;
+}
+static auto in_apply_skip_fn(const InCall& c) { return c.dtype == SGG_F32 ? in_apply_skip_kernel<float> : in_apply_skip_kernel<bf16>; }
+static auto in_skip_bwd_partial_fn(const InCall& c) { return c.dtype == SGG_F32 ? in_skip_bwd_partial_kernel<float> : in_skip_bwd_partial_kernel<bf16>; }
+
+// ---- the passes, each launched from here only
+// statistics: per-chunk (sum, sumsq) forward, (sum g, sum g*xhat) backward; the skip backward also stores dz to dskip
+static void in_launch_stats(const InCall& c, bool bwd, float* partial, int chunks) {
+    const dim3 gp(chunks, c.N);
+    const int rpc = in_rows_per_chunk(c.HW);
+    hipStream_t s = (hipStream_t)c.stream;
+    if (bwd && c.with_skip)
+        hipLaunchKernelGGL(in_skip_bwd_partial_fn(c), gp, dim3(256), 0, s, (const char*)c.x, (const char*)c.dy, (const char*)c.y_in,
+                           (const float*)c.stats, (char*)c.dskip, partial, c.HW, c.C, chunks, rpc, c.act, c.leak);
+    else
+        hipLaunchKernelGGL(in_partial_fn(c, bwd), gp, dim3(256), 0, s, (const char*)c.x, (const char*)(bwd ? c.dy : nullptr), c.gamma, c.beta,
+                           (const float*)(bwd ? c.stats : nullptr), partial, c.HW, c.C, chunks, rpc, c.act, c.leak, c.sp);
+}
+// forward: stats = (mean, rstd); backward: sums = the two sums / HW, tot = the raw sums
+static void in_launch_finalize(const InCall& c, bool bwd, const float* partial, int chunks, float* sums, float* tot) {
+    const dim3 gf((c.C + FIN_CH - 1) / FIN_CH, c.N);
+    hipStream_t s = (hipStream_t)c.stream;
+    if (bwd) hipLaunchKernelGGL(in_finalize_bwd_kernel, gf, dim3(1024), 0, s, partial, sums, tot, c.HW, c.C, chunks);
+    else hipLaunchKernelGGL(in_finalize_fwd_kernel, gf, dim3(1024), 0, s, partial, c.stats, c.HW, c.C, chunks, c.eps);
+}
+// backward: g is the gradient the pass reads (dy, or the skip form's dskip) with the activation still to be undone by (act, leak).
+// The bf16 forward launch is the timed one of this family (sgg_time_next_launch): a span then times the apply pass only.
+static void in_launch_apply(const InCall& c, bool bwd, const void* g, int act, float leak, const float* sums, const InParamGrad& pg) {
+    const int rpb = in_rows_per_block(c.N, c.HW);
+    const dim3 ga = in_apply_grid(c, rpb);
+    hipStream_t s = (hipStream_t)c.stream;
+    const auto kern = in_apply_fn(c, bwd);
+    auto launch = [&](auto... a) {
+        if (!bwd && c.dtype == SGG_BF16) sgg_launch_timed(kern, ga, dim3(256), 0u, s, a...);
+        else hipLaunchKernelGGL(kern, ga, dim3(256), 0, s, a...);
+    };
+    launch((const char*)c.x, (const char*)(bwd ? g : nullptr), (const char*)(bwd ? nullptr : c.addend), c.gamma, c.beta, (const float*)c.stats,
+           sums, (char*)c.out, c.HW, c.C, rpb, act, leak, pg, c.sp);
+}
+static void in_launch_apply_skip(const InCall& c) {
+    const int rpb = in_rows_per_block(c.N, c.HW);
+    hipLaunchKernelGGL(in_apply_skip_fn(c), in_apply_grid(c, rpb), dim3(256), 0, (hipStream_t)c.stream, (const char*)c.x, (const char*)c.addend,
+                       c.gamma, c.beta, (const float*)c.stats, (char*)c.out, c.HW, c.C, rpb, c.act, c.leak, c.sp);
+}
+static void in_launch_fused(const InCall& c, bool bwd, float* tot) {
+    const int vec = c.dtype == SGG_BF16 ? 8 : 4;
+    const dim3 gf((unsigned)((c.C / vec + IN_CVB - 1) / IN_CVB), c.N);
+    hipLaunchKernelGGL(in_fused_fn(c, bwd), gf, dim3(256), 0, (hipStream_t)c.stream, (const char*)c.x, (const char*)(bwd ? c.dy : nullptr),
+                       (const char*)(bwd ? nullptr : c.addend), c.gamma, c.beta, c.stats, tot, (char*)c.out, c.HW, c.C, bwd ? 0.f : c.eps,
+                       c.act, c.leak, c.sp);
+}
+
+// One precedence for every form: arguments (SGG_EINVAL), then what no kernel does (SGG_EUNSUPPORTED), then the dtype
+// (SGG_EINVAL), then the workspace (SGG_EWORKSPACE).  A refused call launches nothing.
+static int in_forward(const InCall& c) {
+    if (!c.x || !c.gamma || !c.beta || !c.out || !c.stats || c.N <= 0 || c.HW <= 0 || c.C <= 0 || c.C % SGG_CPAD || !in_pair_ok(c)) return SGG_EINVAL;
+    if ((c.with_skip && !c.addend) || (c.with_partial && (!c.partial || c.chunks <= 0))) return SGG_EINVAL;
+    if (c.act == SGG_ACT_TANH || c.dy_f32) return SGG_EUNSUPPORTED;
+    if (c.dtype != SGG_BF16 && c.dtype != SGG_F32) return SGG_EINVAL;
+    if (!c.with_partial && (!c.ws || c.ws_bytes < sgg_instnorm_workspace(c.N, c.HW, c.C))) return SGG_EWORKSPACE;
+    if (!c.with_skip && !c.with_partial && in_use_fused(c.HW)) {
+        in_launch_fused(c, false, nullptr);
+        return sgg_check_launch();
+    }
+    const int chunks = c.with_partial ? c.chunks : in_chunks(c.HW);
+    if (!c.with_partial) in_launch_stats(c, false, (float*)c.ws, chunks);
+    in_launch_finalize(c, false, c.with_partial ? c.partial : (const float*)c.ws, chunks, nullptr, nullptr);
+    if (c.with_skip) in_launch_apply_skip(c);
+    else in_launch_apply(c, false, nullptr, c.act, c.leak, nullptr, InParamGrad{});
+    return sgg_check_launch();
+}
+
+// Mixed mode (dy_f32): dy is f32, x / dx are bf16 (the gradient chain between the instance norms of the residual blocks stays f32:
+// the norm backward subtracts the mean and the xhat-correlated part of dy, so a bf16 rounding of dy -- relative to dy, not
+// to what is left of it -- is amplified there layer after layer).  Same passes as the plain backward.
+static int in_backward(const InCall& c) {
+    if (!c.dy || !c.x || !c.gamma || !c.beta || !c.stats || !c.out || !c.dgamma || !c.dbeta || c.N <= 0 || c.HW <= 0 || c.C <= 0 ||
+        c.C % SGG_CPAD || c.C_real <= 0 || c.C_real > c.C || !in_pair_ok(c) || (c.pair && (!c.sp.dgamma2 || !c.sp.dbeta2))) return SGG_EINVAL;
+    if (c.with_partial && (!c.partial || c.chunks <= 0)) return SGG_EINVAL;
+    if (c.with_skip && (!c.y_in || !c.dskip || c.out == c.dskip || c.out == c.dy || c.out == c.x)) return SGG_EINVAL;
+    if (c.act == SGG_ACT_TANH || (int)c.dy_f32 + (int)c.with_partial + (int)c.with_skip > 1) return SGG_EUNSUPPORTED;
+    if (c.dtype != SGG_BF16 && (c.dtype != SGG_F32 || c.dy_f32)) return SGG_EINVAL;
+    const int chunks = c.with_partial ? c.chunks : in_chunks(c.HW);
+    const size_t own = c.with_partial ? 0 : (size_t)c.N * chunks * c.C * 2;          // floats of the partial rows this call writes
+    if (!c.ws || c.ws_bytes < (own + (size_t)c.N * c.C * 4) * sizeof(float)) return SGG_EWORKSPACE;
+    float* sums = (float*)c.ws + own;
+    float* tot = sums + (size_t)c.N * c.C * 2;
+    const InParamGrad pg{tot, c.dgamma, c.dbeta, c.N, c.C_real, c.accumulate};
+    if (!c.dy_f32 && !c.with_partial && !c.with_skip && in_use_fused(c.HW)) {
+        in_launch_fused(c, true, tot);
+        hipLaunchKernelGGL(in_param_grad_kernel, dim3(1), dim3(256), 0, (hipStream_t)c.stream, pg, c.C, c.sp);
+        return sgg_check_launch();
+    }
+    if (!c.with_partial) in_launch_stats(c, true, (float*)c.ws, chunks);
+    in_launch_finalize(c, true, c.with_partial ? c.partial : (const float*)c.ws, chunks, sums, tot);
+    // the skip form's statistics pass has undone the activation: dskip = dy * act'(y) is what the apply pass reads
+    if (c.with_skip) in_launch_apply(c, true, c.dskip, SGG_ACT_NONE, 0.f, sums, pg);
+    else in_launch_apply(c, true, c.dy, c.act, c.leak, sums, pg);
+    return sgg_check_launch();
 }
 
 extern "C" {
@@ -578,289 +733,115 @@ size_t sgg_instnorm_workspace(int N, int64_t HW, int C) {
     return ((size_t)N * in_chunks(HW) * C * 2 + (size_t)N * C * 4) * sizeof(float);
 }
 
-static int instnorm_fwd_impl(const void* x, const float* gamma, const float* beta, const void* residual, void* y, float* stats,
-                     int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream, InSplit sp) {
-    if (!x || !gamma || !beta || !y || !stats || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    if (in_use_fused(HW)) {
-        const int vec = dtype == SGG_BF16 ? 8 : 4;
-        dim3 gf((unsigned)((C / vec + IN_CVB - 1) / IN_CVB), N);
-        if (dtype == SGG_BF16) hipLaunchKernelGGL((in_fused_small_kernel<bf16, false>), gf, dim3(256), 0, s, (const char*)x, nullptr, (const char*)residual, gamma, beta, stats, nullptr, (char*)y, HW, C, eps, act, leak, sp);
-        else hipLaunchKernelGGL((in_fused_small_kernel<float, false>), gf, dim3(256), 0, s, (const char*)x, nullptr, (const char*)residual, gamma, beta, stats, nullptr, (char*)y, HW, C, eps, act, leak, sp);
-        return sgg_check_launch();
-    }
-    int chunks = in_chunks(HW);
-    float* partial = (float*)ws;
-    int rpb = in_rows_per_block(N, HW, C, 0);
-    dim3 gp(chunks, N), ga((unsigned)((HW + rpb - 1) / rpb), N);
-    if (dtype == SGG_BF16) {
-        hipLaunchKernelGGL((in_partial_kernel<bf16, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-        hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-        sgg_launch_timed(in_apply_kernel<bf16, false>, ga, dim3(256), 0u, s, (const char*)x, (const char*)nullptr, (const char*)residual, gamma, beta, (const float*)stats, (const float*)nullptr, (char*)y, HW, C, rpb, act, leak, InParamGrad{}, sp);
-    } else if (dtype == SGG_F32) {
-        hipLaunchKernelGGL((in_partial_kernel<float, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-        hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-        hipLaunchKernelGGL((in_apply_kernel<float, false>), ga, dim3(256), 0, s, (const char*)x, nullptr, (const char*)residual, gamma, beta, stats, nullptr, (char*)y, HW, C, rpb, act, leak, InParamGrad{}, sp);
-    } else return SGG_EINVAL;
-    return sgg_check_launch();
-}
-
-static int instnorm_fwd_partial_impl(const void* x, const float* gamma, const float* beta, const void* residual, void* y, float* stats,
-                             const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
-                             void* stream, InSplit sp) {
-    if (!x || !gamma || !beta || !y || !stats || !partial || chunks <= 0 || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    int rpb = in_rows_per_block(N, HW, C, 0);
-    dim3 ga((unsigned)((HW + rpb - 1) / rpb), N);
-    hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-    if (dtype == SGG_BF16) sgg_launch_timed(in_apply_kernel<bf16, false>, ga, dim3(256), 0u, s, (const char*)x, (const char*)nullptr, (const char*)residual, gamma, beta, (const float*)stats, (const float*)nullptr, (char*)y, HW, C, rpb, act, leak, InParamGrad{}, sp);
-    else hipLaunchKernelGGL((in_apply_kernel<float, false>), ga, dim3(256), 0, s, (const char*)x, nullptr, (const char*)residual, gamma, beta, stats, nullptr, (char*)y, HW, C, rpb, act, leak, InParamGrad{}, sp);
-    return sgg_check_launch();
-}
-
-static int instnorm_bwd_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx,
-                     float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
-                     int dtype, void* ws, size_t ws_bytes, void* stream, InSplit sp) {
-    if (!dy || !x || !gamma || !beta || !stats || !dx || !dgamma || !dbeta || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD || C_real <= 0 || C_real > C) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    int chunks = in_chunks(HW);
-    float* partial = (float*)ws;
-    float* sums = partial + (size_t)N * chunks * C * 2;
-    float* tot = sums + (size_t)N * C * 2;
-    int rpb = in_rows_per_block(N, HW, C, 0);
-    dim3 gp(chunks, N), ga((unsigned)((HW + rpb - 1) / rpb), N);
-    const InParamGrad pg{tot, dgamma, dbeta, N, C_real, accumulate};
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    if (in_use_fused(HW)) {
-        const int vec = dtype == SGG_BF16 ? 8 : 4;
-        dim3 gf((unsigned)((C / vec + IN_CVB - 1) / IN_CVB), N);
-        if (dtype == SGG_BF16) hipLaunchKernelGGL((in_fused_small_kernel<bf16, true>), gf, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, (float*)stats, tot, (char*)dx, HW, C, 0.f, act, leak, sp);
-        else hipLaunchKernelGGL((in_fused_small_kernel<float, true>), gf, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, (float*)stats, tot, (char*)dx, HW, C, 0.f, act, leak, sp);
-        hipLaunchKernelGGL(in_param_grad_kernel, dim3(1), dim3(256), 0, s, pg, C, sp);
-        return sgg_check_launch();
-    }
-    if (dtype == SGG_BF16) {
-        hipLaunchKernelGGL((in_partial_kernel<bf16, true>), gp, dim3(256), 0, s, (const char*)x, (const char*)dy, gamma, beta, stats, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-        hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
-        hipLaunchKernelGGL((in_apply_kernel<bf16, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, act, leak, pg, sp);
-    } else if (dtype == SGG_F32) {
-        hipLaunchKernelGGL((in_partial_kernel<float, true>), gp, dim3(256), 0, s, (const char*)x, (const char*)dy, gamma, beta, stats, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-        hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
-        hipLaunchKernelGGL((in_apply_kernel<float, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, act, leak, pg, sp);
-    } else return SGG_EINVAL;
-    return sgg_check_launch();
-}
-
-// Mixed mode: dy is f32, x / dx are bf16 (the gradient chain between the instance norms of the residual blocks stays f32:
-// the norm backward subtracts the mean and the xhat-correlated part of dy, so a bf16 rounding of dy -- relative to dy, not
-// to what is left of it -- is amplified there layer after layer).  Same passes as sgg_instnorm_bwd.
-static int instnorm_bwd_mixed_impl(const float* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx,
-                           float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
-                           void* ws, size_t ws_bytes, void* stream, InSplit sp) {
-    if (!dy || !x || !gamma || !beta || !stats || !dx || !dgamma || !dbeta || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD || C_real <= 0 || C_real > C) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    int chunks = in_chunks(HW);
-    float* partial = (float*)ws;
-    float* sums = partial + (size_t)N * chunks * C * 2;
-    float* tot = sums + (size_t)N * C * 2;
-    int rpb = in_rows_per_block(N, HW, C, 0);
-    dim3 gp(chunks, N), ga((unsigned)((HW + rpb - 1) / rpb), N);
-    const InParamGrad pg{tot, dgamma, dbeta, N, C_real, accumulate};
-    hipLaunchKernelGGL((in_partial_kernel<bf16, true, float>), gp, dim3(256), 0, s, (const char*)x, (const char*)dy, gamma, beta, stats, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-    hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
-    hipLaunchKernelGGL((in_apply_kernel<bf16, true, float>), ga, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, act, leak, pg, sp);
-    return sgg_check_launch();
-}
-
-static int instnorm_bwd_partial_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx,
-                             float* dgamma, float* dbeta, const float* partial, int chunks, int N, int64_t HW, int C, int C_real,
-                             int accumulate, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream, InSplit sp) {
-    if (!dy || !x || !gamma || !beta || !stats || !dx || !dgamma || !dbeta || !partial || chunks <= 0 || N <= 0 || HW <= 0 || C <= 0 ||
-        C % SGG_CPAD || C_real <= 0 || C_real > C) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    if (!ws || ws_bytes < (size_t)N * C * 4 * sizeof(float)) return SGG_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* sums = (float*)ws;
-    float* tot = sums + (size_t)N * C * 2;
-    int rpb = in_rows_per_block(N, HW, C, 0);
-    dim3 ga((unsigned)((HW + rpb - 1) / rpb), N);
-    const InParamGrad pg{tot, dgamma, dbeta, N, C_real, accumulate};
-    hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
-    if (dtype == SGG_BF16) hipLaunchKernelGGL((in_apply_kernel<bf16, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, act, leak, pg, sp);
-    else hipLaunchKernelGGL((in_apply_kernel<float, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dy, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, act, leak, pg, sp);
-    return sgg_check_launch();
-}
-
 // ---- public entry points: one network, or two networks of the same shape stacked on the batch dimension ("pair": images
 // 0..nsplit-1 use gamma/beta and add to dgamma/dbeta, the rest use gamma2/beta2 and dgamma2/dbeta2)
 int sgg_instnorm_fwd(const void* x, const float* gamma, const float* beta, const void* residual, void* y, float* stats,
                      int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_fwd_impl(x, gamma, beta, residual, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream, in_nosplit());
+    return in_forward(in_fwd_call(x, gamma, beta, residual, false, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream));
 }
 int sgg_instnorm_fwd_partial(const void* x, const float* gamma, const float* beta, const void* residual, void* y, float* stats,
                              const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
                              void* stream) {
-    return instnorm_fwd_partial_impl(x, gamma, beta, residual, y, stats, partial, chunks, N, HW, C, eps, act, leak, dtype, stream, in_nosplit());
+    InCall c = in_fwd_call(x, gamma, beta, residual, false, y, stats, N, HW, C, eps, act, leak, dtype, nullptr, 0, stream);
+    in_rows(c, partial, chunks);
+    return in_forward(c);
 }
 int sgg_instnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx,
                      float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
                      int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_bwd_impl(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream, in_nosplit());
+    return in_backward(in_bwd_call(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream));
 }
 int sgg_instnorm_bwd_mixed(const float* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx,
                            float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
                            void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_bwd_mixed_impl(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, ws, ws_bytes, stream, in_nosplit());
+    InCall c = in_bwd_call(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, SGG_BF16, ws, ws_bytes, stream);
+    c.dy_f32 = true;
+    return in_backward(c);
 }
 int sgg_instnorm_bwd_partial(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats, void* dx,
                              float* dgamma, float* dbeta, const float* partial, int chunks, int N, int64_t HW, int C, int C_real,
                              int accumulate, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_bwd_partial_impl(dy, x, gamma, beta, stats, dx, dgamma, dbeta, partial, chunks, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream, in_nosplit());
+    InCall c = in_bwd_call(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream);
+    in_rows(c, partial, chunks);
+    return in_backward(c);
 }
 // (mean, rstd)[N][C] from per-chunk (sum, sumsq) rows -- the finalize step of sgg_instnorm_fwd_partial on its own, for a
 // consumer that applies the norm itself (sgg_conv2d_fwd_stats_normload)
 int sgg_instnorm_finalize(const float* partial, int chunks, float* stats, int N, int64_t HW, int C, float eps, void* stream) {
     if (!partial || !stats || chunks <= 0 || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
-    hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, (hipStream_t)stream, partial, stats, HW, C, chunks, eps);
+    InCall c;
+    c.stats = stats; c.N = N; c.HW = HW; c.C = C; c.eps = eps; c.stream = stream;
+    in_launch_finalize(c, false, partial, chunks, nullptr, nullptr);
     return sgg_check_launch();
 }
-static inline int in_pair_ok(const float* g2, const float* b2, int nsplit, int N) { return g2 && b2 && nsplit > 0 && nsplit < N; }
 int sgg_instnorm_fwd_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
                           const void* residual, void* y, float* stats, int N, int64_t HW, int C, float eps, int act, float leak,
                           int dtype, void* ws, size_t ws_bytes, void* stream) {
-    if (!in_pair_ok(gamma2, beta2, nsplit, N)) return SGG_EINVAL;
-    InSplit sp = in_nosplit(); sp.gamma2 = gamma2; sp.beta2 = beta2; sp.nsplit = nsplit;
-    return instnorm_fwd_impl(x, gamma, beta, residual, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream, sp);
+    InCall c = in_fwd_call(x, gamma, beta, residual, false, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream);
+    in_pair(c, gamma2, beta2, nullptr, nullptr, nsplit);
+    return in_forward(c);
 }
 int sgg_instnorm_fwd_partial_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
                                   const void* residual, void* y, float* stats, const float* partial, int chunks, int N, int64_t HW, int C,
                                   float eps, int act, float leak, int dtype, void* stream) {
-    if (!in_pair_ok(gamma2, beta2, nsplit, N)) return SGG_EINVAL;
-    InSplit sp = in_nosplit(); sp.gamma2 = gamma2; sp.beta2 = beta2; sp.nsplit = nsplit;
-    return instnorm_fwd_partial_impl(x, gamma, beta, residual, y, stats, partial, chunks, N, HW, C, eps, act, leak, dtype, stream, sp);
+    InCall c = in_fwd_call(x, gamma, beta, residual, false, y, stats, N, HW, C, eps, act, leak, dtype, nullptr, 0, stream);
+    in_rows(c, partial, chunks);
+    in_pair(c, gamma2, beta2, nullptr, nullptr, nsplit);
+    return in_forward(c);
 }
 int sgg_instnorm_bwd_pair(const void* dy, const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2,
                           int nsplit, const float* stats, void* dx, float* dgamma, float* dbeta, float* dgamma2, float* dbeta2,
                           int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak, int dtype,
                           void* ws, size_t ws_bytes, void* stream) {
-    if (!in_pair_ok(gamma2, beta2, nsplit, N) || !dgamma2 || !dbeta2) return SGG_EINVAL;
-    InSplit sp; sp.gamma2 = gamma2; sp.beta2 = beta2; sp.dgamma2 = dgamma2; sp.dbeta2 = dbeta2; sp.nsplit = nsplit;
-    return instnorm_bwd_impl(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream, sp);
+    InCall c = in_bwd_call(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream);
+    in_pair(c, gamma2, beta2, dgamma2, dbeta2, nsplit);
+    return in_backward(c);
 }
 
-// ---- skip added before the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip).  One network (in_nosplit())
-// or two in lockstep on a stacked batch (the _pair entry points): the statistics passes and the backward's dz pass never read
-// the affine parameters, so only the two apply kernels and the parameter-gradient sums pick a set by image index.
-static int instnorm_fwd_skip_apply(const void* x, const float* gamma, const float* beta, const void* skip, void* y, const float* stats,
-                                   int N, int64_t HW, int C, int act, float leak, int dtype, hipStream_t s, InSplit sp) {
-    const int rpb = in_rows_per_block(N, HW, C, 0);
-    const dim3 ga((unsigned)((HW + rpb - 1) / rpb), N);
-    if (dtype == SGG_BF16) hipLaunchKernelGGL(in_apply_skip_kernel<bf16>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak, sp);
-    else hipLaunchKernelGGL(in_apply_skip_kernel<float>, ga, dim3(256), 0, s, (const char*)x, (const char*)skip, gamma, beta, stats, (char*)y, HW, C, rpb, act, leak, sp);
-    return sgg_check_launch();
-}
-static int instnorm_fwd_skip_impl(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
-                                  int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream,
-                                  InSplit sp) {
-    if (!x || !gamma || !beta || !skip || !y || !stats || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = in_chunks(HW);
-    float* partial = (float*)ws;
-    const dim3 gp(chunks, N);
-    if (dtype == SGG_BF16) hipLaunchKernelGGL((in_partial_kernel<bf16, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-    else hipLaunchKernelGGL((in_partial_kernel<float, false>), gp, dim3(256), 0, s, (const char*)x, nullptr, gamma, beta, nullptr, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak, sp);
-    hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s, sp);
-}
-static int instnorm_fwd_skip_partial_impl(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
-                                          const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
-                                          void* stream, InSplit sp) {
-    if (!x || !gamma || !beta || !skip || !y || !stats || !partial || chunks <= 0 || N <= 0 || HW <= 0 || C <= 0 || C % SGG_CPAD) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(in_finalize_fwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, stats, HW, C, chunks, eps);
-    return instnorm_fwd_skip_apply(x, gamma, beta, skip, y, stats, N, HW, C, act, leak, dtype, s, sp);
-}
-static int instnorm_bwd_skip_impl(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
-                                  void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
-                                  int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream, InSplit sp) {
-    if (!dy || !y || !x || !gamma || !beta || !stats || !dx || !dskip || !dgamma || !dbeta || N <= 0 || HW <= 0 || C <= 0 ||
-        C % SGG_CPAD || C_real <= 0 || C_real > C) return SGG_EINVAL;
-    if (act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (dtype != SGG_BF16 && dtype != SGG_F32) return SGG_EINVAL;
-    if (dx == dskip || dx == dy || dx == x) return SGG_EINVAL;
-    if (!ws || ws_bytes < sgg_instnorm_workspace(N, HW, C)) return SGG_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = in_chunks(HW);
-    float* partial = (float*)ws;
-    float* sums = partial + (size_t)N * chunks * C * 2;
-    float* tot = sums + (size_t)N * C * 2;
-    const int rpb = in_rows_per_block(N, HW, C, 0);
-    const dim3 gp(chunks, N), ga((unsigned)((HW + rpb - 1) / rpb), N);
-    const InParamGrad pg{tot, dgamma, dbeta, N, C_real, accumulate};
-    if (dtype == SGG_BF16) {
-        hipLaunchKernelGGL(in_skip_bwd_partial_kernel<bf16>, gp, dim3(256), 0, s, (const char*)x, (const char*)dy, (const char*)y, stats, (char*)dskip, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak);
-        hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
-        hipLaunchKernelGGL((in_apply_kernel<bf16, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dskip, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, (int)SGG_ACT_NONE, 0.f, pg, sp);
-    } else {
-        hipLaunchKernelGGL(in_skip_bwd_partial_kernel<float>, gp, dim3(256), 0, s, (const char*)x, (const char*)dy, (const char*)y, stats, (char*)dskip, partial, HW, C, chunks, in_rows_per_chunk(HW), act, leak);
-        hipLaunchKernelGGL(in_finalize_bwd_kernel, dim3((C + FIN_CH - 1) / FIN_CH, N), dim3(1024), 0, s, partial, sums, tot, HW, C, chunks);
-        hipLaunchKernelGGL((in_apply_kernel<float, true>), ga, dim3(256), 0, s, (const char*)x, (const char*)dskip, nullptr, gamma, beta, stats, sums, (char*)dx, HW, C, rpb, (int)SGG_ACT_NONE, 0.f, pg, sp);
-    }
-    return sgg_check_launch();
-}
+// ---- skip added before the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip).  One network or two in
+// lockstep on a stacked batch (the _pair entry points): the statistics passes and the backward's dz pass never read the
+// affine parameters, so only the two apply kernels and the parameter-gradient sums pick a set by image index.
 int sgg_instnorm_fwd_skip(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
                           int N, int64_t HW, int C, float eps, int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_fwd_skip_impl(x, gamma, beta, skip, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream, in_nosplit());
+    return in_forward(in_fwd_call(x, gamma, beta, skip, true, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream));
 }
 int sgg_instnorm_fwd_skip_partial(const void* x, const float* gamma, const float* beta, const void* skip, void* y, float* stats,
                                   const float* partial, int chunks, int N, int64_t HW, int C, float eps, int act, float leak, int dtype,
                                   void* stream) {
-    return instnorm_fwd_skip_partial_impl(x, gamma, beta, skip, y, stats, partial, chunks, N, HW, C, eps, act, leak, dtype, stream, in_nosplit());
+    InCall c = in_fwd_call(x, gamma, beta, skip, true, y, stats, N, HW, C, eps, act, leak, dtype, nullptr, 0, stream);
+    in_rows(c, partial, chunks);
+    return in_forward(c);
 }
 int sgg_instnorm_bwd_skip(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* stats,
                           void* dx, void* dskip, float* dgamma, float* dbeta, int N, int64_t HW, int C, int C_real, int accumulate,
                           int act, float leak, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_bwd_skip_impl(dy, y, x, gamma, beta, stats, dx, dskip, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype,
-                                  ws, ws_bytes, stream, in_nosplit());
+    InCall c = in_bwd_call(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream);
+    c.with_skip = true; c.y_in = y; c.dskip = dskip;
+    return in_backward(c);
 }
-// the lockstep forms: images 0..nsplit-1 use (gamma, beta) and add into (dgamma, dbeta), the rest the second set
 int sgg_instnorm_fwd_skip_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
                                const void* skip, void* y, float* stats, int N, int64_t HW, int C, float eps, int act, float leak,
                                int dtype, void* ws, size_t ws_bytes, void* stream) {
-    if (!in_pair_ok(gamma2, beta2, nsplit, N)) return SGG_EINVAL;
-    InSplit sp = in_nosplit(); sp.gamma2 = gamma2; sp.beta2 = beta2; sp.nsplit = nsplit;
-    return instnorm_fwd_skip_impl(x, gamma, beta, skip, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream, sp);
+    InCall c = in_fwd_call(x, gamma, beta, skip, true, y, stats, N, HW, C, eps, act, leak, dtype, ws, ws_bytes, stream);
+    in_pair(c, gamma2, beta2, nullptr, nullptr, nsplit);
+    return in_forward(c);
 }
 int sgg_instnorm_fwd_skip_partial_pair(const void* x, const float* gamma, const float* beta, const float* gamma2, const float* beta2, int nsplit,
                                        const void* skip, void* y, float* stats, const float* partial, int chunks, int N, int64_t HW, int C,
                                        float eps, int act, float leak, int dtype, void* stream) {
-    if (!in_pair_ok(gamma2, beta2, nsplit, N)) return SGG_EINVAL;
-    InSplit sp = in_nosplit(); sp.gamma2 = gamma2; sp.beta2 = beta2; sp.nsplit = nsplit;
-    return instnorm_fwd_skip_partial_impl(x, gamma, beta, skip, y, stats, partial, chunks, N, HW, C, eps, act, leak, dtype, stream, sp);
+    InCall c = in_fwd_call(x, gamma, beta, skip, true, y, stats, N, HW, C, eps, act, leak, dtype, nullptr, 0, stream);
+    in_rows(c, partial, chunks);
+    in_pair(c, gamma2, beta2, nullptr, nullptr, nsplit);
+    return in_forward(c);
 }
 int sgg_instnorm_bwd_skip_pair(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* gamma2,
                                const float* beta2, int nsplit, const float* stats, void* dx, void* dskip, float* dgamma, float* dbeta,
                                float* dgamma2, float* dbeta2, int N, int64_t HW, int C, int C_real, int accumulate, int act, float leak,
                                int dtype, void* ws, size_t ws_bytes, void* stream) {
-    if (!in_pair_ok(gamma2, beta2, nsplit, N) || !dgamma2 || !dbeta2) return SGG_EINVAL;
-    InSplit sp; sp.gamma2 = gamma2; sp.beta2 = beta2; sp.dgamma2 = dgamma2; sp.dbeta2 = dbeta2; sp.nsplit = nsplit;
-    return instnorm_bwd_skip_impl(dy, y, x, gamma, beta, stats, dx, dskip, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype,
-                                  ws, ws_bytes, stream, sp);
+    InCall c = in_bwd_call(dy, x, gamma, beta, stats, dx, dgamma, dbeta, N, HW, C, C_real, accumulate, act, leak, dtype, ws, ws_bytes, stream);
+    c.with_skip = true; c.y_in = y; c.dskip = dskip;
+    in_pair(c, gamma2, beta2, dgamma2, dbeta2, nsplit);
+    return in_backward(c);
 }
 
 }  // extern "C"

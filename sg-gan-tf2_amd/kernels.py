@@ -492,172 +492,134 @@ def bias_grad_group2(dy, db, db2, accumulate=False):
 
 
 # ----------------------------------------------------------------------------- instance norm / activations
-def instnorm_fwd(x, gamma, beta, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
+# The public instnorm_* functions below are thin calls into _instnorm_fwd / _instnorm_bwd, which check, allocate, size the
+# workspace, open the profiler span and assemble the argument list of the sgg_instnorm_* symbol the arguments select.
+#   addend   the tensor added to the output: the residual (after the activation; may be None), or with skip=True the skip
+#            (before the activation: y = act(gamma*xhat + beta + skip), generator_unet d3 / d7)
+#   partial  the (sum, sumsq) / (sum g, sum g*xhat) rows of the producing conv: the norm skips its statistics pass
+#   pair     two networks of the same shape on one stacked batch (images 0..nsplit-1: first network; the rest: second):
+#            (gamma2, beta2, nsplit) forward, (gamma2, beta2, nsplit, dgamma2, dbeta2) backward
+#   span     (name, key) of the profiler span, or None for none
+def _instnorm_fwd(span, x, gamma, beta, addend, eps, act, leak, skip=False, partial=None, pair=None):
     N, H, W, Cp = x.shape
     assert gamma.numel() == Cp and beta.numel() == Cp, "gamma/beta must be channel-padded"
+    if skip:
+        assert tuple(addend.shape) == tuple(x.shape) and addend.dtype == x.dtype
+    if partial is not None:
+        assert partial.shape[0] == N and partial.shape[2] == Cp
+    if pair is not None:
+        assert pair[0].numel() == Cp and 0 < pair[2] < N
+    name = "instnorm_fwd" + ("_skip" if skip else "") + ("_partial" if partial is not None else "") + ("_pair" if pair is not None else "")
     y = torch.empty_like(x)
     stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
-    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-    pr = _prof("instnorm_fwd", (tuple(x.shape), residual is not None))
+    args = [_p(x), _p(gamma), _p(beta)]
+    if pair is not None:
+        args += [_p(pair[0]), _p(pair[1]), pair[2]]
+    args += [_p(addend), _p(y), _p(stats)]
+    if partial is not None:
+        args += [_p(partial), partial.shape[1]]
+    args += [N, H * W, Cp, eps, act, leak, dt(x)]
+    if partial is None:
+        ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
+        args += [_p(ws), ws.numel()]
+    pr = _prof(*span) if span else None
     if pr: pr.start()
-    A.check(A.lib().sgg_instnorm_fwd(_p(x), _p(gamma), _p(beta), _p(residual), _p(y), _p(stats), N, H * W, Cp, eps, act, leak,
-                                     dt(x), _p(ws), ws.numel(), _s()), "instnorm_fwd")
+    A.check(getattr(A.lib(), "sgg_" + name)(*args, _s()), name)
     if pr: pr.stop()
     return y, stats
+
+
+def _instnorm_bwd(span, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=None, partial=None, pair=None):
+    """y: the stored output of the skip form, whose backward returns (dx, dskip), dskip = dy * act'(y); otherwise dx alone."""
+    N, H, W, Cp = x.shape
+    skip = y is not None
+    mixed = dy.dtype == torch.float32 and x.dtype == torch.bfloat16        # mixed mode: f32 gradient chain, bf16 tensors
+    if skip:
+        assert dy.dtype == x.dtype and y.dtype == x.dtype and tuple(dy.shape) == tuple(x.shape) == tuple(y.shape)
+    if partial is not None:
+        assert partial.shape[0] == N and partial.shape[2] == Cp
+    if pair is not None:
+        assert dy.dtype == x.dtype and dgamma.numel() == pair[3].numel() and 0 < pair[2] < N
+    assert not (mixed and partial is not None), "mixed mode has no partial form"
+    name = "instnorm_bwd" + ("_skip" if skip else "") + ("_partial" if partial is not None else "") + ("_pair" if pair is not None else "") + \
+        ("_mixed" if mixed else "")
+    dx = torch.empty_like(x)
+    dskip = torch.empty_like(x) if skip else None
+    need = N * Cp * 16 if partial is not None else int(A.lib().sgg_instnorm_workspace(N, H * W, Cp))
+    ws = workspace(need, x.device)
+    args = [_p(dy)] + ([_p(y)] if skip else []) + [_p(x), _p(gamma), _p(beta)]
+    if pair is not None:
+        args += [_p(pair[0]), _p(pair[1]), pair[2]]
+    args += [_p(stats), _p(dx)] + ([_p(dskip)] if skip else []) + [_p(dgamma), _p(dbeta)]
+    if pair is not None:
+        args += [_p(pair[3]), _p(pair[4])]
+    if partial is not None:
+        args += [_p(partial), partial.shape[1]]
+    args += [N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak] + ([] if mixed else [dt(x)])
+    pr = _prof(*span) if span else None
+    if pr: pr.start()
+    A.check(getattr(A.lib(), "sgg_" + name)(*args, _p(ws), ws.numel(), _s()), name)
+    if pr: pr.stop()
+    return (dx, dskip) if skip else dx
+
+
+def instnorm_fwd(x, gamma, beta, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
+    return _instnorm_fwd(("instnorm_fwd", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak)
 
 
 def instnorm_fwd_partial(x, partial, gamma, beta, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
     """instance norm whose statistics pass was done by the producing conv (conv_fwd_stats): finalize + apply only."""
-    N, H, W, Cp = x.shape
-    assert gamma.numel() == Cp and beta.numel() == Cp and partial.shape[0] == N and partial.shape[2] == Cp
-    y = torch.empty_like(x)
-    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
-    pr = _prof("instnorm_fwd_partial", (tuple(x.shape), residual is not None))
-    if pr: pr.start()
-    A.check(A.lib().sgg_instnorm_fwd_partial(_p(x), _p(gamma), _p(beta), _p(residual), _p(y), _p(stats), _p(partial), partial.shape[1],
-                                             N, H * W, Cp, eps, act, leak, dt(x), _s()), "instnorm_fwd_partial")
-    if pr: pr.stop()
-    return y, stats
+    return _instnorm_fwd(("instnorm_fwd_partial", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak,
+                         partial=partial)
 
 
 def instnorm_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
-    N, H, W, Cp = x.shape
-    dx = torch.empty_like(x)
-    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-    if dy.dtype == torch.float32 and x.dtype == torch.bfloat16:        # mixed mode: f32 gradient chain, bf16 tensors
-        A.check(A.lib().sgg_instnorm_bwd_mixed(_p(dy), _p(x), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dgamma), _p(dbeta), N, H * W, Cp,
-                                               dgamma.numel(), int(accumulate), act, leak, _p(ws), ws.numel(), _s()), "instnorm_bwd_mixed")
-        return dx
-    A.check(A.lib().sgg_instnorm_bwd(_p(dy), _p(x), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dgamma), _p(dbeta), N, H * W, Cp,
-                                     dgamma.numel(), int(accumulate), act, leak, dt(x), _p(ws), ws.numel(), _s()), "instnorm_bwd")
-    return dx
+    """sgg_instnorm_bwd, or sgg_instnorm_bwd_mixed when dy is f32 and x is bf16."""
+    return _instnorm_bwd(None, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak)
 
 
 def instnorm_bwd_partial(dy, x, partial, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
     """instance-norm backward whose statistics pass was done by the conv data gradient that produced dy."""
-    N, H, W, Cp = x.shape
-    assert partial.shape[0] == N and partial.shape[2] == Cp
-    dx = torch.empty_like(x)
-    ws = workspace(N * Cp * 16, x.device)
-    A.check(A.lib().sgg_instnorm_bwd_partial(_p(dy), _p(x), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dgamma), _p(dbeta), _p(partial),
-                                             partial.shape[1], N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak, dt(x),
-                                             _p(ws), ws.numel(), _s()), "instnorm_bwd_partial")
-    return dx
+    return _instnorm_bwd(None, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, partial=partial)
 
 
-# ---- the skip added BEFORE the activation (generator_unet d3 / d7): y = act(gamma*xhat + beta + skip)
 def instnorm_fwd_skip(x, gamma, beta, skip, eps=1e-3, act=A.ACT_NONE, leak=0.0, partial=None):
     """partial: the producing conv's (sum, sumsq) rows (conv_fwd_stats / deconv_fwd_stats) -- the norm skips its statistics pass."""
-    N, H, W, Cp = x.shape
-    assert gamma.numel() == Cp and beta.numel() == Cp and tuple(skip.shape) == tuple(x.shape) and skip.dtype == x.dtype
-    y = torch.empty_like(x)
-    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
-    pr = _prof("instnorm_fwd_skip", (tuple(x.shape), partial is not None))
-    if pr: pr.start()
-    if partial is not None:
-        assert partial.shape[0] == N and partial.shape[2] == Cp
-        A.check(A.lib().sgg_instnorm_fwd_skip_partial(_p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats), _p(partial), partial.shape[1],
-                                                      N, H * W, Cp, eps, act, leak, dt(x), _s()), "instnorm_fwd_skip_partial")
-    else:
-        ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-        A.check(A.lib().sgg_instnorm_fwd_skip(_p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats), N, H * W, Cp, eps, act, leak,
-                                              dt(x), _p(ws), ws.numel(), _s()), "instnorm_fwd_skip")
-    if pr: pr.stop()
-    return y, stats
+    return _instnorm_fwd(("instnorm_fwd_skip", (tuple(x.shape), partial is not None)), x, gamma, beta, skip, eps, act, leak,
+                         skip=True, partial=partial)
 
 
 def instnorm_bwd_skip(dy, y, x, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
     """Backward of instnorm_fwd_skip from its stored output y: returns (dx, dskip), dskip = dy * act'(y)."""
-    N, H, W, Cp = x.shape
-    assert dy.dtype == x.dtype and y.dtype == x.dtype and tuple(dy.shape) == tuple(x.shape) == tuple(y.shape)
-    dx, dskip = torch.empty_like(x), torch.empty_like(x)
-    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-    pr = _prof("instnorm_bwd_skip", tuple(x.shape))
-    if pr: pr.start()
-    A.check(A.lib().sgg_instnorm_bwd_skip(_p(dy), _p(y), _p(x), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dskip), _p(dgamma), _p(dbeta),
-                                          N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak, dt(x), _p(ws), ws.numel(), _s()),
-            "instnorm_bwd_skip")
-    if pr: pr.stop()
-    return dx, dskip
+    return _instnorm_bwd(("instnorm_bwd_skip", tuple(x.shape)), dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=y)
 
 
-# ---- two networks of the same shape on one stacked batch (images 0..nsplit-1: first network; the rest: second)
 def instnorm_fwd_pair(x, gamma, beta, gamma2, beta2, nsplit, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
-    N, H, W, Cp = x.shape
-    assert gamma.numel() == Cp and gamma2.numel() == Cp and 0 < nsplit < N
-    y = torch.empty_like(x)
-    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
-    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-    pr = _prof("instnorm_fwd_pair", (tuple(x.shape), residual is not None))
-    if pr: pr.start()
-    A.check(A.lib().sgg_instnorm_fwd_pair(_p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(residual), _p(y), _p(stats), N, H * W, Cp,
-                                          eps, act, leak, dt(x), _p(ws), ws.numel(), _s()), "instnorm_fwd_pair")
-    if pr: pr.stop()
-    return y, stats
+    return _instnorm_fwd(("instnorm_fwd_pair", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak,
+                         pair=(gamma2, beta2, nsplit))
 
 
 def instnorm_fwd_partial_pair(x, partial, gamma, beta, gamma2, beta2, nsplit, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
-    N, H, W, Cp = x.shape
-    assert gamma.numel() == Cp and gamma2.numel() == Cp and partial.shape[0] == N and partial.shape[2] == Cp and 0 < nsplit < N
-    y = torch.empty_like(x)
-    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
-    pr = _prof("instnorm_fwd_partial_pair", (tuple(x.shape), residual is not None))
-    if pr: pr.start()
-    A.check(A.lib().sgg_instnorm_fwd_partial_pair(_p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(residual), _p(y), _p(stats),
-                                                  _p(partial), partial.shape[1], N, H * W, Cp, eps, act, leak, dt(x), _s()), "instnorm_fwd_partial_pair")
-    if pr: pr.stop()
-    return y, stats
+    return _instnorm_fwd(("instnorm_fwd_partial_pair", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak,
+                         partial=partial, pair=(gamma2, beta2, nsplit))
 
 
 def instnorm_bwd_pair(dy, x, gamma, beta, gamma2, beta2, nsplit, stats, dgamma, dbeta, dgamma2, dbeta2, accumulate=False,
                       act=A.ACT_NONE, leak=0.0):
-    N, H, W, Cp = x.shape
-    assert dy.dtype == x.dtype and dgamma.numel() == dgamma2.numel() and 0 < nsplit < N
-    dx = torch.empty_like(x)
-    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-    A.check(A.lib().sgg_instnorm_bwd_pair(_p(dy), _p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(stats), _p(dx), _p(dgamma), _p(dbeta),
-                                          _p(dgamma2), _p(dbeta2), N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak, dt(x),
-                                          _p(ws), ws.numel(), _s()), "instnorm_bwd_pair")
-    return dx
+    return _instnorm_bwd(None, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, pair=(gamma2, beta2, nsplit, dgamma2, dbeta2))
 
 
 def instnorm_fwd_skip_pair(x, gamma, beta, gamma2, beta2, nsplit, skip, eps=1e-3, act=A.ACT_NONE, leak=0.0, partial=None):
     """instnorm_fwd_skip of two networks on one stacked batch: y = act(IN(x) + skip) with the affine set picked by image index."""
-    N, H, W, Cp = x.shape
-    assert gamma.numel() == Cp and gamma2.numel() == Cp and 0 < nsplit < N
-    assert tuple(skip.shape) == tuple(x.shape) and skip.dtype == x.dtype
-    y = torch.empty_like(x)
-    stats = torch.empty((N, Cp, 2), dtype=torch.float32, device=x.device)
-    pr = _prof("instnorm_fwd_skip_pair", (tuple(x.shape), partial is not None))
-    if pr: pr.start()
-    if partial is not None:
-        assert partial.shape[0] == N and partial.shape[2] == Cp
-        A.check(A.lib().sgg_instnorm_fwd_skip_partial_pair(_p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(skip), _p(y), _p(stats),
-                                                           _p(partial), partial.shape[1], N, H * W, Cp, eps, act, leak, dt(x), _s()),
-                "instnorm_fwd_skip_partial_pair")
-    else:
-        ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-        A.check(A.lib().sgg_instnorm_fwd_skip_pair(_p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(skip), _p(y), _p(stats),
-                                                   N, H * W, Cp, eps, act, leak, dt(x), _p(ws), ws.numel(), _s()), "instnorm_fwd_skip_pair")
-    if pr: pr.stop()
-    return y, stats
+    return _instnorm_fwd(("instnorm_fwd_skip_pair", (tuple(x.shape), partial is not None)), x, gamma, beta, skip, eps, act, leak,
+                         skip=True, partial=partial, pair=(gamma2, beta2, nsplit))
 
 
 def instnorm_bwd_skip_pair(dy, y, x, gamma, beta, gamma2, beta2, nsplit, stats, dgamma, dbeta, dgamma2, dbeta2, accumulate=False,
                            act=A.ACT_NONE, leak=0.0):
     """Backward of instnorm_fwd_skip_pair from its stored output y: (dx, dskip), both stacked like x."""
-    N, H, W, Cp = x.shape
-    assert dy.dtype == x.dtype and y.dtype == x.dtype and tuple(dy.shape) == tuple(x.shape) == tuple(y.shape)
-    assert dgamma.numel() == dgamma2.numel() and 0 < nsplit < N
-    dx, dskip = torch.empty_like(x), torch.empty_like(x)
-    ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
-    pr = _prof("instnorm_bwd_skip_pair", tuple(x.shape))
-    if pr: pr.start()
-    A.check(A.lib().sgg_instnorm_bwd_skip_pair(_p(dy), _p(y), _p(x), _p(gamma), _p(beta), _p(gamma2), _p(beta2), nsplit, _p(stats), _p(dx), _p(dskip),
-                                               _p(dgamma), _p(dbeta), _p(dgamma2), _p(dbeta2), N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak,
-                                               dt(x), _p(ws), ws.numel(), _s()), "instnorm_bwd_skip_pair")
-    if pr: pr.stop()
-    return dx, dskip
+    return _instnorm_bwd(("instnorm_bwd_skip_pair", tuple(x.shape)), dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak,
+                         y=y, pair=(gamma2, beta2, nsplit, dgamma2, dbeta2))
 
 
 def act_fwd(x, act, leak=0.0):

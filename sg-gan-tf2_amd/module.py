@@ -377,17 +377,20 @@ class _ConvUnit:
         record_only: the caller only wants the forward record (activation checkpointing re-runs a residual block's second
         conv for its backward pass: the block's output is not needed again) -- where the conv's epilogue delivers the norm's
         sums, the norm's apply pass is skipped (same statistics, bit for bit) and y is None."""
-        P, n = self.net.P, self.name
         g, xc, part = self._conv(x, out)
         if not self.norm:
             return xc, (g, x, xc, None)
         if part is None:
-            y, stats = K.instnorm_fwd(xc, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
+            y, stats = K.instnorm_fwd(xc, *self.affine(), residual, self.net.eps, self.act, self.leak)
         elif record_only:
             return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], self.net.eps))
         else:
-            y, stats = K.instnorm_fwd_partial(xc, part, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak)
+            y, stats = K.instnorm_fwd_partial(xc, part, *self.affine(), residual, self.net.eps, self.act, self.leak)
         return y, (g, x, xc, stats)
+
+    def affine(self):
+        """(gamma, beta) of this unit's norm."""
+        return self.net.P.p(self.name + "_g"), self.net.P.p(self.name + "_beta")
 
     def weight_grad(self, g, x, dxc, gbuf=None):
         """dW += wgrad(x, dxc).  When the net is applied twice this step (pair_wgrads) the first application's operands are
@@ -420,9 +423,9 @@ class _ConvUnit:
             else:   # gradients w.r.t. gamma/beta not wanted: send them to scratch
                 dg = db = self.net.scratch_vec(K.cpad(self.cout))
             if dy_partial is not None:
-                dxc = K.instnorm_bwd_partial(dy, xc, dy_partial, P.p(n + "_g"), P.p(n + "_beta"), stats, dg, db, param_grads, self.act, self.leak)
+                dxc = K.instnorm_bwd_partial(dy, xc, dy_partial, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
             else:
-                dxc = K.instnorm_bwd(dy, xc, P.p(n + "_g"), P.p(n + "_beta"), stats, dg, db, param_grads, self.act, self.leak)
+                dxc = K.instnorm_bwd(dy, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
             # the conv bias feeds an InstanceNorm: its gradient is identically 0 -> left at 0
         else:
             if dy.dtype != xc.dtype:
@@ -443,9 +446,7 @@ class _ConvUnit:
                 nu, nrec = next_norm
                 if (not out_f32 and self.net.fuse_in_stats and self.net.fuse_in_bwd and g.bwd_stats_chunks and nu.norm
                         and tuple(nrec[2].shape) == g.x_shape):
-                    NP = nu.net.P
-                    return K.conv_dgrad_stats(g, dxc, wd, addend, nrec[2], nrec[3], NP.p(nu.name + "_g"), NP.p(nu.name + "_beta"),
-                                              nu.act, nu.leak)
+                    return K.conv_dgrad_stats(g, dxc, wd, addend, nrec[2], nrec[3], *nu.affine(), nu.act, nu.leak)
                 return K.conv_dgrad(g, dxc, wd, addend, out_f32=out_f32), None
             return K.conv_dgrad(g, dxc, wd, addend)
         dx = K.deconv_dgrad(g, dxc, wf)
@@ -462,9 +463,8 @@ class _SkipActUnit(_ConvUnit):
 
     def forward(self, x, residual=None, record_only=False, out=None):
         assert residual is not None and out is None and not record_only and self.norm
-        P, n = self.net.P, self.name
         g, xc, part = self._conv(x)
-        y, stats = K.instnorm_fwd_skip(xc, P.p(n + "_g"), P.p(n + "_beta"), residual, self.net.eps, self.act, self.leak, partial=part)
+        y, stats = K.instnorm_fwd_skip(xc, *self.affine(), residual, self.net.eps, self.act, self.leak, partial=part)
         return y, (g, x, xc, stats, y)
 
     def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
@@ -476,7 +476,7 @@ class _SkipActUnit(_ConvUnit):
             dg, db = P.g(n + "_g", buf=gbuf), P.g(n + "_beta", buf=gbuf)
         else:
             dg = db = self.net.scratch_vec(K.cpad(self.cout))
-        dxc, dskip = K.instnorm_bwd_skip(dy, y, xc, P.p(n + "_g"), P.p(n + "_beta"), stats, dg, db, param_grads, self.act, self.leak)
+        dxc, dskip = K.instnorm_bwd_skip(dy, y, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
         if param_grads:
             self.weight_grad(g, x, dxc, gbuf)
         if not want_dx:
@@ -906,20 +906,21 @@ class _PairUnit:
     def forward(self, x, residual=None, record_only=False, out=None):
         ua, ub = self.ua, self.ub
         n = x.shape[0] // 2
-        na, nb = ua.name, ub.name
-        PA, PB = ua.net.P, ub.net.P
         g, xc, part, one_launch = self._conv(x, out)
         if not ua.norm:
             return xc, (g, x, xc, None)
         if part is not None:
             if record_only and one_launch:          # (_ConvUnit.forward: the statistics without the apply pass)
                 return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], ua.net.eps))
-            y, stats = K.instnorm_fwd_partial_pair(xc, part, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
-                                                   residual, ua.net.eps, ua.act, ua.leak)
+            y, stats = K.instnorm_fwd_partial_pair(xc, part, *self.affine(), n, residual, ua.net.eps, ua.act, ua.leak)
             return y, (g, x, xc, stats)
-        y, stats = K.instnorm_fwd_pair(xc, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n,
-                                       residual, ua.net.eps, ua.act, ua.leak)
+        y, stats = K.instnorm_fwd_pair(xc, *self.affine(), n, residual, ua.net.eps, ua.act, ua.leak)
         return y, (g, x, xc, stats)
+
+    def affine(self):
+        """(gamma, beta) of the first network's norm, then the second's."""
+        ua, ub = self.ua, self.ub
+        return (ua.net.P.p(ua.name + "_g"), ua.net.P.p(ua.name + "_beta"), ub.net.P.p(ub.name + "_g"), ub.net.P.p(ub.name + "_beta"))
 
     def _norm_grads(self, param_grads):
         """Where the norm backward puts (dgamma, dbeta) of the two networks."""
@@ -941,8 +942,7 @@ class _PairUnit:
         na, nb = ua.name, ub.name
         PA, PB = ua.net.P, ub.net.P
         if ua.norm:
-            dxc = K.instnorm_bwd_pair(dy, xc, PA.p(na + "_g"), PA.p(na + "_beta"), PB.p(nb + "_g"), PB.p(nb + "_beta"), n, stats,
-                                      *self._norm_grads(param_grads), param_grads, ua.act, ua.leak)
+            dxc = K.instnorm_bwd_pair(dy, xc, *self.affine(), n, stats, *self._norm_grads(param_grads), param_grads, ua.act, ua.leak)
             # (the conv bias in front of an instance norm has an identically zero gradient: left at 0)
         else:
             dxc = K.act_bwd(dy, xc, ua.act, ua.leak) if ua.act != A.ACT_NONE else dy
@@ -1005,20 +1005,16 @@ class _PairSkipActUnit(_PairUnit):
 
     def forward(self, x, residual=None, record_only=False, out=None):
         assert residual is not None and out is None and not record_only and self.ua.norm
-        ua, ub = self.ua, self.ub
-        PA, PB = ua.net.P, ub.net.P
+        ua = self.ua
         g, xc, part, _ = self._conv(x)
-        y, stats = K.instnorm_fwd_skip_pair(xc, PA.p(ua.name + "_g"), PA.p(ua.name + "_beta"), PB.p(ub.name + "_g"), PB.p(ub.name + "_beta"),
-                                            x.shape[0] // 2, residual, ua.net.eps, ua.act, ua.leak, partial=part)
+        y, stats = K.instnorm_fwd_skip_pair(xc, *self.affine(), x.shape[0] // 2, residual, ua.net.eps, ua.act, ua.leak, partial=part)
         return y, (g, x, xc, stats, y)
 
     def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
         assert gbuf is None and addend is None and dy_partial is None and next_norm is None
-        ua, ub = self.ua, self.ub
-        PA, PB = ua.net.P, ub.net.P
+        ua = self.ua
         g, x, xc, stats, y = rec
-        dxc, dskip = K.instnorm_bwd_skip_pair(dy, y, xc, PA.p(ua.name + "_g"), PA.p(ua.name + "_beta"), PB.p(ub.name + "_g"),
-                                              PB.p(ub.name + "_beta"), x.shape[0] // 2, stats, *self._norm_grads(param_grads),
+        dxc, dskip = K.instnorm_bwd_skip_pair(dy, y, xc, *self.affine(), x.shape[0] // 2, stats, *self._norm_grads(param_grads),
                                               param_grads, ua.act, ua.leak)
         return self._conv_backward(g, x, dxc, want_dx, param_grads, None), dskip
 
