@@ -95,7 +95,13 @@ int sgg_pack_conv_weights_batch(const sgg_pack_item* items_dev, int n_items, int
 
 /* ---- conv2d: tf.keras.layers.Conv2D (+ tf.pad REFLECT) ---- module.py:210-216,230-232,236,240,262-264,284-311
  * fwd: y = act(conv(x) + bias);  bias may be NULL; bias has Kpad f32 entries.
- * ws: sgg_conv2d_fwd_workspace() bytes (non-zero only for small outputs, which are computed split-K). */
+ * ws: sgg_conv2d_fwd_workspace() bytes (non-zero only for small outputs, which are computed split-K).
+ * Status of every conv2d / deconv2d forward and data-gradient entry below (plain, _stats, _mixed, _pair, _normload, _group2),
+ * decided in this order before anything is launched: SGG_EINVAL -- a NULL or invalid descriptor, a transposed conv with a
+ * padding mode other than zero, a NULL pointer among the required operands, nsplit outside 1..N-1 where a second weight set
+ * is given; SGG_EUNSUPPORTED -- the shape or dtype has no such form (the *_supported / *_stats_chunks queries say so
+ * beforehand); SGG_EWORKSPACE -- ws is NULL or smaller than the call needs, which is at most what the entry's workspace query reports (a
+ * _group2 call: twice that). */
 size_t sgg_conv2d_fwd_workspace(const sgg_conv_desc* d);
 int sgg_conv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w_fwd, const float* bias,
                    void* y, int act, float leak, void* ws, size_t ws_bytes, void* stream);

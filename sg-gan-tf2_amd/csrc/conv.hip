@@ -889,12 +889,13 @@ __global__ __launch_bounds__(512) void deconv_s2_stats_kernel(ConvArgs a) {
     }
 }
 
-static bool s2halo_ok(const ConvArgs& a, bool is_bf16) {
-    const int en = sgg_config().s2halo;
-    if (!en || !is_bf16 || a.ksplit > 1 || SGG_ABLATE_OF(a) || a.reflect) return false;
-    if (a.R != 3 || a.S != 3 || a.stride != 2 || a.H != 2 * a.Ho || a.W != 2 * a.Wo) return false;
-    if (a.pad_t != 0 || a.pad_l != 0) return false;     // TF 'SAME' with an even input pads bottom/right only
-    return a.K % 64 == 0 && a.C % 64 == 0 && a.Wo % S2_TJ == 0 && a.Ho % S2_TI == 0;
+// (a question about the shape alone, like halo3_ok: plan_conv never splits K for a shape this kernel takes)
+static bool s2halo_ok(const sgg_conv_desc* d) {
+    const SggConfig& cfg = sgg_config();
+    if (!cfg.s2halo || d->dtype != SGG_BF16 || cfg.ablate || d->pad_mode == SGG_PAD_REFLECT) return false;
+    if (d->R != 3 || d->S != 3 || d->stride != 2 || d->H != 2 * d->Ho || d->W != 2 * d->Wo) return false;
+    if (d->pad_t != 0 || d->pad_l != 0) return false;     // TF 'SAME' with an even input pads bottom/right only
+    return d->K % 64 == 0 && d->C % 64 == 0 && d->Wo % S2_TJ == 0 && d->Ho % S2_TI == 0;
 }
 
 template <int PT, int PL>
@@ -1411,7 +1412,7 @@ static bool halo_fwd_ok(const sgg_conv_desc* d) {
 }
 
 template <typename T>
-static int launch_halo_fwd(const sgg_conv_desc* d, const ConvArgs& a, hipStream_t s, int flip = 0) {
+static int launch_halo_fwd_t(const sgg_conv_desc* d, const ConvArgs& a, int flip, hipStream_t s) {
     size_t lds = 2 * (size_t)HALO_MAXR * 16 * 128 + (size_t)(HALO_TH + d->R - 1) * (HALO_TW + d->S - 1) * 128 + 1024;
     auto kern = conv_halo_fwd_kernel<T>;
     SGG_LDS_ATTR(kern, 160 * 1024);
@@ -1634,7 +1635,7 @@ static bool halo_narrow_in_ok(const sgg_conv_desc* d, int src_ch, int dst_ch) {
 }
 
 template <typename T>
-static int launch_halo_narrow_in(const sgg_conv_desc* d, const ConvArgs& a, int flip, hipStream_t s) {
+static int launch_halo_narrow_in_t(const sgg_conv_desc* d, const ConvArgs& a, int flip, hipStream_t s) {
     const int cpv = 8 / (16 / (int)sizeof(T));
     const int ksteps = (d->R * d->S * cpv + 3) / 4;
     size_t lds = (size_t)64 * (((ksteps * 4) | 1) * 16) + (size_t)(HALO_TH + d->R - 1) * (HALO_TW + d->S - 1) * 8 * sizeof(T)
@@ -1766,17 +1767,6 @@ static bool desc_ok(const sgg_conv_desc* d) {
     return true;
 }
 
-static ConvArgs make_args(const sgg_conv_desc* d, const void* src, const void* w, const float* bias, void* dst, int act, float leak) {
-    ConvArgs a;
-    a.src = (const char*)src; a.wmat = (const char*)w; a.bias = bias; a.dst = (char*)dst; a.addend = nullptr; a.fold = nullptr; a.stats = nullptr; a.nx = nullptr; a.nstats = nullptr; a.ngamma = nullptr; a.nbeta = nullptr; a.nact = 0; a.nleak = 0.f; a.nout = nullptr; a.ngamma2 = nullptr; a.nbeta2 = nullptr; a.partial = nullptr; a.ksplit = 1; a.pdst = 0; a.dst_f32 = 0; a.addend_f32 = 0; a.wmat2 = nullptr; a.bias2 = nullptr; a.nsplit = 0x7fffffff;
-    a.grp = 1; a.net_src = a.net_dst = a.net_add = a.net_part = 0;
-    a.ablate = sgg_config().ablate;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->C; a.K = d->K; a.R = d->R; a.S = d->S; a.stride = d->stride;
-    a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.Ho = d->Ho; a.Wo = d->Wo; a.reflect = d->pad_mode == SGG_PAD_REFLECT;
-    a.act = act; a.leak = leak;
-    return a;
-}
-
 // REFLECT data gradient behind a main launch that padded with zeros: add the mirrored terms to the border pixels of dx
 // (conv_border_fold_kernel); few pixels and short K loops, hence the small tiles
 template <typename T>
@@ -1854,30 +1844,21 @@ static int launch_glds_cfg(const ConvArgs& a, int64_t Mmax, int DC, int classes,
     return sgg_check_launch();
 }
 
-// rows, result channels and parity classes of the GEMM a launch of `mode` runs
-static void gemm_dims(const ConvArgs& a, int mode, int& DC, int& classes, int64_t& Mmax) {
-    if (mode == MODE_FWD) { DC = a.K; classes = 1; Mmax = (int64_t)a.N * a.Ho * a.Wo; }
-    else {
-        DC = a.C; classes = a.stride * a.stride;
-        Mmax = (int64_t)a.N * ((a.H + a.stride - 1) / a.stride) * ((a.W + a.stride - 1) / a.stride);
-    }
-}
+// -------------------------------------------------------------------------------------------------
+// The launch layer of the forward and the data gradient.  plan_conv() states every decision about a call once: the kernel, the
+// split, the workspace, how a grouped call runs and which fused forms the shape has (the table is in DESIGN.md section 3).
+// run_conv() validates a ConvCall, asks the plan, checks the workspace and launches; the 15 launch exports fill a ConvCall,
+// the 12 queries return fields of the plan.  (The weight gradients have their own plan, plan_wgrad in conv_wgrad.hip.)
 
-// The kernel launch_gemm() runs for these arguments (an sgg_route without the split-K bit): launch_gemm switches on it and
-// sgg_conv2d_route() reports it, so there is one copy of the conditions.
-static int gemm_route(const ConvArgs& a, int mode, bool is_bf16) {
-    if (mode == MODE_DGRAD && s2halo_ok(a, is_bf16)) return SGG_ROUTE_S2HALO;
-    if (halo3_ok(a, mode, is_bf16)) return SGG_ROUTE_HALO3;
-    int DC, classes;
-    int64_t Mmax;
-    gemm_dims(a, mode, DC, classes, Mmax);
+// The generic GEMM's block tile for `DC` result channels and `Mmax` rows per parity class (an sgg_route)
+static int glds_route(const sgg_conv_desc* d, int dir, int DC, int64_t Mmax) {
     // big square tiles (8 waves, 1 block per CU) when there is enough work to fill the chip with them
     // (a 4-stage ring of 64-byte K-slices was measured 3-5 % slower on the residual conv and is not built)
     if (DC >= 256 && Mmax * ((DC + 255) / 256) >= 256 * 160) return SGG_ROUTE_GLDS_256x256;
     // short reductions (<= 16 K-tiles: the 64-channel stride-2 layers c2 forward / d2 data gradient / D.h1 forward): a
     // 256x128 block is alone on its CU and spends a third of its life in prologue and epilogue; two 128x128 blocks per
     // CU cover each other: 93.7 -> 84.4 us (c2), 25.3 -> 22.7 us (D.h1); the 4-wave 128x64 tile (three blocks): 115 us
-    if (DC >= 128 && (mode == MODE_FWD ? a.R * a.S * a.C : a.R * a.S * a.K) <= 1024) return SGG_ROUTE_GLDS_128x128;
+    if (DC >= 128 && (dir == MODE_FWD ? d->R * d->S * d->C : d->R * d->S * d->K) <= 1024) return SGG_ROUTE_GLDS_128x128;
     if (DC >= 128 && Mmax * ((DC + 127) / 128) >= 256 * 160) return SGG_ROUTE_GLDS_256x128;
     // 128x128 with 8 waves (2 per SIMD, two blocks per CU): the 4-wave variant ran at one wave per SIMD with
     // nothing to cover its LDS latencies (D.h3 data gradient 86 -> 60 us, D.h2 forward 36 -> 23 us)
@@ -1886,111 +1867,291 @@ static int gemm_route(const ConvArgs& a, int mode, bool is_bf16) {
     return SGG_ROUTE_GLDS_256x16;
 }
 
-template <typename T, int MODE>
-static int launch_gemm(const ConvArgs& a, hipStream_t s) {
-    int DC, classes;
-    int64_t Mmax;
-    gemm_dims(a, MODE, DC, classes, Mmax);
-    if constexpr (sizeof(T) == 2) {
-        // grouped launch of a shape whose kernel takes a STACKED batch with per-image weights (the LDS-resident 3x3 / stride-2
-        // halo kernels): the two groups are contiguous, so it is that kernel on 2N images with the split at N
-        if (a.grp == 2 && a.ksplit == 1 && (halo3_ok(a, MODE, true) || (MODE == MODE_DGRAD && s2halo_ok(a, true)))) {
-            ConvArgs b = a;
-            b.N = 2 * a.N; b.nsplit = a.N; b.grp = 1;
-            return launch_gemm<T, MODE>(b, s);
-        }
-    }
-    const int route = gemm_route(a, MODE, sizeof(T) == 2);
-    switch (route) {
-    case SGG_ROUTE_S2HALO:
-        if constexpr (MODE == MODE_DGRAD && sizeof(T) == 2) return launch_s2halo(a, s);
-        break;
-    case SGG_ROUTE_HALO3:
-        if constexpr (sizeof(T) == 2) return launch_halo3(a, MODE, s);
-        break;
-    case SGG_ROUTE_GLDS_256x256:
-        return launch_glds_cfg<T, MODE, 256, 256, 2, 8, 128, 2>(a, Mmax, DC, classes, s);
-    case SGG_ROUTE_GLDS_256x128:
-        // three LDS stages (48 KB each): its layers (c2 forward, d2 data gradient, D.h1 forward) gather their pixel operand from HBM
-        // with 9 short K-tiles per block; two tiles in flight instead of one: 96.8 -> 93.4 us (c2), 26.4 -> 25.3 us (D.h1)
-        return launch_glds_cfg<T, MODE, 256, 128, 4, 8, 128, 3>(a, Mmax, DC, classes, s);
-    case SGG_ROUTE_GLDS_128x128:
-        return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, Mmax, DC, classes, s);
-    case SGG_ROUTE_GLDS_128x64:
-        return launch_glds_cfg<T, MODE, 128, 64, 4, 4>(a, Mmax, DC, classes, s);
-    case SGG_ROUTE_GLDS_256x16:
-        return launch_glds_cfg<T, MODE, 256, 16, 4, 4>(a, Mmax, DC, classes, s);
-    default: break;
-    }
-    return SGG_EUNSUPPORTED;                           // (a route this instantiation has no kernel for: gemm_route never returns one)
-}
-
-// split-K planning shared by the workspace queries and the launches
-struct GemmPlan { int DC, classes, ktot_max, ksplit; int64_t Mmax; size_t pdst, ws_bytes; };
-static GemmPlan plan_gemm(const sgg_conv_desc* d, int mode) {
-    GemmPlan g;
-    const int vec = d->dtype == SGG_BF16 ? 8 : 4;
-    if (mode == MODE_FWD) {
-        g.DC = d->K; g.classes = 1; g.Mmax = (int64_t)d->N * d->Ho * d->Wo; g.pdst = (size_t)g.Mmax;
-        g.ktot_max = (d->R * d->S * (d->C / vec) + 7) / 8;
-    } else {
-        const int st = d->stride;
-        g.DC = d->C; g.classes = st * st;
-        g.Mmax = (int64_t)d->N * ((d->H + st - 1) / st) * ((d->W + st - 1) / st);
-        g.pdst = (size_t)d->N * d->H * d->W;
-        g.ktot_max = (((d->R + st - 1) / st) * ((d->S + st - 1) / st) * (d->K / vec) + 7) / 8;
-    }
-    g.ksplit = conv_ksplit(g.Mmax, g.DC, g.classes, g.ktot_max);
-    if (g.ksplit > 1) {
-        // shapes the halo-resident kernels take are never split (they only occur at sizes that fill the chip; it also
-        // keeps the small parity-test shapes on the same kernels as the full-size layers)
-        ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-        const bool bf = d->dtype == SGG_BF16;
-        if (halo3_ok(a, mode, bf) || (mode == MODE_DGRAD && s2halo_ok(a, bf))) g.ksplit = 1;
-    }
-    g.ws_bytes = g.ksplit > 1 ? (size_t)g.ksplit * g.pdst * g.DC * sizeof(float) : 0;
-    return g;
-}
-
-template <typename T, int MODE>
-static int run_gemm(const sgg_conv_desc* d, ConvArgs a, void* ws, size_t ws_bytes, hipStream_t s) {
-    GemmPlan g = plan_gemm(d, MODE);
-    if (g.ksplit > 1) {
-        if (!ws || ws_bytes < g.ws_bytes * a.grp) return SGG_EWORKSPACE;
-        a.ksplit = g.ksplit; a.partial = (float*)ws; a.pdst = g.pdst; a.net_part = g.ws_bytes;
-    }
-    int rc = launch_gemm<T, MODE>(a, s);
-    if (rc || g.ksplit <= 1) return rc;
-    int64_t nvec4 = (int64_t)g.pdst * g.DC / 4;
-    int blocks = (int)((nvec4 + 255) / 256); if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(blocks, a.grp), dim3(256), 0, s, (const float*)ws, a.bias, a.addend, a.dst, nvec4, g.DC, g.ksplit,
-                       g.pdst * g.DC, a.act, a.leak, SplitKGroup{a.bias2, a.net_part, a.net_dst, a.net_add});
-    return sgg_check_launch();
-}
-
-// the route of a plain run_gemm() call: plan_gemm()'s split factor, then launch_gemm()'s choice for the arguments it is given
-static int run_gemm_route(const sgg_conv_desc* d, int mode) {
-    const GemmPlan g = plan_gemm(d, mode);
-    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-    if (g.ksplit > 1) a.ksplit = g.ksplit;
-    return gemm_route(a, mode, d->dtype == SGG_BF16) | (g.ksplit > 1 ? SGG_ROUTE_SPLITK : 0);
-}
-
-// Kernels taken AHEAD of the GEMM planner by sgg_conv2d_fwd / conv2d_bwd_data_impl (an sgg_route), 0: run_gemm() decides
-// (run_gemm_route).  The launchers switch on these; sgg_conv2d_route() reports them.
-static int conv_fwd_head_route(const sgg_conv_desc* d) {
+// Kernels taken AHEAD of the GEMM planner by the conv entries (an sgg_route), 0: the GEMM planner decides.  A transposed conv
+// takes none.  stats: the call emits statistics rows -- forward (sum, sumsq), data gradient the norm-backward sums
+static int conv_fwd_head_route(const sgg_conv_desc* d, bool stats) {
     if (halo_narrow_in_ok(d, d->C, d->K)) return SGG_ROUTE_HALO_NARROW_IN;   // narrow input (stem): halo + whole weight matrix resident in LDS
+    if (stats) return 0;                                           // (the other two have no statistics epilogue)
     if (conv7_head_ok(d)) return SGG_ROUTE_N7;                     // the 7x7 head: (channel, tap column) in the GEMM N dimension
-    if (halo_fwd_ok(d)) return SGG_ROUTE_HALO_FWD;             // narrow output at full resolution: input halo resident in LDS
+    if (halo_fwd_ok(d)) return SGG_ROUTE_HALO_FWD;                 // narrow output at full resolution: input halo resident in LDS
     return 0;
 }
-// addend: a skip gradient is joined in the epilogue; stats: the norm-backward sums are wanted
+// addend: a skip gradient is joined in the epilogue
 static int conv_dgrad_head_route(const sgg_conv_desc* d, bool addend, bool stats) {
     if (!addend && halo_narrow_in_ok(d, d->K, d->C)) return SGG_ROUTE_HALO_NARROW_IN;   // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
     if (!stats && s2n_dgrad_ok(d)) return SGG_ROUTE_S2N;
     if (!stats && conv7_stem_ok(d)) return SGG_ROUTE_N7;         // (addend: joined in the fold pass, before its one rounding)
     if (!addend && halo_dgrad_narrow_ok(d)) return SGG_ROUTE_HALO_DGRAD_NARROW;
     return 0;
+}
+
+static size_t fold_bytes(const sgg_conv_desc* d) {
+    if (d->pad_mode != SGG_PAD_REFLECT) return 0;
+    size_t es = d->dtype == SGG_BF16 ? 2 : 4;
+    return align_up((size_t)d->N * fold_border_per_image(d->H, d->W, d->pad_t) * d->R * d->S * d->K * es, 256);
+}
+
+// How a grouped call (two networks' call sites of one shape, sgg_*_group2) runs
+enum {
+    GROUP_ONE_LAUNCH = 0,    // the generic GEMM with grp = 2: the grid's z dimension doubles, each group is exactly the single launch
+    GROUP_STACKED,           // a kernel that picks the weights per image (HALO3, S2HALO, S2N): the single launch on 2N images, split at N
+    GROUP_TWO_CALLS          // the head routes and the REFLECT data gradient (its fold tensor is per call): two single calls
+};
+
+struct ConvPlan {
+    int route;               // the kernel a call runs (an sgg_route): a head route, or the GEMM planner's with the SGG_ROUTE_SPLITK bit
+    int gemm;                // the GEMM planner's route for the shape: == route unless a head route is taken ahead of it
+    int DC, classes, ksplit; // result channels, parity classes and split factor (1: none) of the GEMM
+    int64_t Mmax;            // its rows per class
+    size_t pdst;             // destination pixels (slab stride)
+    size_t fold_bytes;       // workspace, first part: the pre-folded gather rows of a REFLECT data gradient on the GEMM
+    size_t splitk_bytes;     //            second part: the split-K slabs
+    size_t ws_bytes;         // what a single call on `route` needs; a grouped call: twice that
+    int group;               // GROUP_*
+    // the fused forms of this direction
+    size_t stats_chunks;     // statistics rows per image (0: no such epilogue)
+    bool mixed, pair, normload;
+};
+
+// dir: the GEMM direction the call runs.  deconv: a transposed conv (it plans the opposite direction of the equivalent conv and
+// takes no head route).  addend, stats: see the head routes.
+static ConvPlan plan_conv(const sgg_conv_desc* d, int dir, bool addend, bool stats, bool deconv = false) {
+    ConvPlan p{};
+    const int vec = d->dtype == SGG_BF16 ? 8 : 4, st = d->stride;
+    int ktot_max;
+    if (dir == MODE_FWD) {
+        p.DC = d->K; p.classes = 1; p.Mmax = (int64_t)d->N * d->Ho * d->Wo; p.pdst = (size_t)p.Mmax;
+        ktot_max = (d->R * d->S * (d->C / vec) + 7) / 8;
+    } else {
+        p.DC = d->C; p.classes = st * st;
+        p.Mmax = (int64_t)d->N * ((d->H + st - 1) / st) * ((d->W + st - 1) / st);
+        p.pdst = (size_t)d->N * d->H * d->W;
+        ktot_max = (((d->R + st - 1) / st) * ((d->S + st - 1) / st) * (d->K / vec) + 7) / 8;
+    }
+    // shapes the halo-resident kernels take are never split (they only occur at sizes that fill the chip; it also
+    // keeps the small parity-test shapes on the same kernels as the full-size layers)
+    const bool s2 = dir == MODE_DGRAD && s2halo_ok(d), h3 = halo3_ok(d, dir);
+    p.ksplit = (s2 || h3) ? 1 : conv_ksplit(p.Mmax, p.DC, p.classes, ktot_max);
+    p.gemm = (s2 ? SGG_ROUTE_S2HALO : h3 ? SGG_ROUTE_HALO3 : glds_route(d, dir, p.DC, p.Mmax)) | (p.ksplit > 1 ? SGG_ROUTE_SPLITK : 0);
+    const int head = deconv ? 0 : dir == MODE_FWD ? conv_fwd_head_route(d, stats) : conv_dgrad_head_route(d, addend, stats);
+    p.route = head ? head : p.gemm;
+    p.fold_bytes = dir == MODE_DGRAD ? fold_bytes(d) : 0;
+    p.splitk_bytes = p.ksplit > 1 ? (size_t)p.ksplit * p.pdst * p.DC * sizeof(float) : 0;
+    p.ws_bytes = !head ? p.fold_bytes + p.splitk_bytes : (head == SGG_ROUTE_N7 && dir == MODE_DGRAD) ? n7_dgrad_ws(d) : 0;
+    p.group = head == SGG_ROUTE_S2N ? GROUP_STACKED : (head || p.fold_bytes) ? GROUP_TWO_CALLS : (s2 || h3) ? GROUP_STACKED : GROUP_ONE_LAUNCH;
+    // The forms hang on the GEMM planner's kernel, also where a head route runs the plain call of the shape.  (A 3x3 layer of
+    // <= 16 channels and 128 | W has both HALO_DGRAD_NARROW and these forms; no network has such a layer.)
+    if (deconv) {
+        if (s2) p.stats_chunks = (size_t)(d->Ho / S2_TI) * (d->Wo / S2_TJ);   // a row per 16 x 64 output tile (deconv_s2_stats_kernel)
+    } else if (head == SGG_ROUTE_HALO_NARROW_IN && dir == MODE_FWD) {
+        if (d->dtype == SGG_BF16) p.stats_chunks = (size_t)(d->H / HALO_TH) * (d->W / HALO_TW);   // the stem: a row per 16 x 32 tile
+    } else if (h3) p.stats_chunks = halo3_stats_chunks(d);           // a row per (2 x 128 tile, tile row)
+    p.mixed = h3 && dir == MODE_DGRAD;
+    p.pair = d->N >= 2 && (deconv ? s2 : halo3_ok(d, MODE_FWD) && halo3_ok(d, MODE_DGRAD));
+    p.normload = h3 && dir == MODE_FWD && d->pad_mode == SGG_PAD_REFLECT && d->C <= halo3_norm_maxc();
+    return p;
+}
+// What the *_workspace queries report.  They do not know the operands, and an addend moves a head shape's data gradient to the
+// GEMM, so a shape whose head route needs no workspace reports the GEMM's.
+static size_t plan_ws_query(const ConvPlan& p) {
+    return p.route == SGG_ROUTE_N7 && p.ws_bytes ? p.ws_bytes : p.fold_bytes + p.splitk_bytes;
+}
+
+// One call of any of the 15 entries.  `form` says which operands below are required and which epilogue is wanted.
+enum {
+    FORM_STATS = 1,          // stats: (sum, sumsq) rows of the stored output
+    FORM_NORM_BWD = 2,       // stats: the norm-backward sums of the data gradient, from nx / nstats / ngamma / nbeta / nact / nleak
+    FORM_MIXED = 4,          // data gradient: dst is f32, and so is the addend when addend_f32
+    FORM_PAIR = 8,           // a stacked batch of two networks: images >= nsplit use w2 / bias2 (/ ngamma2 / nbeta2)
+    FORM_NORMLOAD = 16,      // forward: src is raw, relu(instnorm(src)) from nstats / ngamma / nbeta is applied on load and written to nout
+    FORM_GROUP = 32,         // sgg_*_group2: d is ONE network's call, the tensors hold 2N images, the second network uses w2 / bias2
+    FORM_DECONV = 64         // a transposed conv
+};
+struct ConvCall {
+    int form;
+    const void* src; const void* w; const float* bias; void* dst; const void* addend;
+    int act; float leak;
+    const void* w2; const float* bias2; int nsplit;
+    float* stats;
+    const void* nx; const float* nstats; const float* ngamma; const float* nbeta; int nact; float nleak;
+    void* nout; const float* ngamma2; const float* nbeta2;
+    int addend_f32;
+    void* ws; size_t ws_bytes; void* stream;
+};
+static ConvCall conv_call(int form, const void* src, const void* w, const float* bias, void* dst, void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c{};
+    c.form = form; c.src = src; c.w = w; c.bias = bias; c.dst = dst; c.act = SGG_ACT_NONE; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+    return c;
+}
+static void conv_call_pair(ConvCall& c, const void* w2, const float* bias2, int nsplit) {
+    c.w2 = w2; c.bias2 = bias2; c.nsplit = nsplit;
+}
+
+static bool conv_call_ok(const sgg_conv_desc* d, const ConvCall& c) {
+    const int f = c.form;
+    if (!desc_ok(d) || ((f & FORM_DECONV) && d->pad_mode != SGG_PAD_ZERO)) return false;
+    if (!c.src || !c.w || !c.dst) return false;
+    if ((f & (FORM_STATS | FORM_NORM_BWD)) && !c.stats) return false;
+    if ((f & FORM_NORM_BWD) && (!c.nx || !c.nstats || !c.ngamma || !c.nbeta)) return false;
+    if ((f & FORM_NORMLOAD) && (!c.nstats || !c.ngamma || !c.nbeta || !c.nout || (c.w2 && (!c.ngamma2 || !c.nbeta2)))) return false;
+    if ((f & (FORM_PAIR | FORM_GROUP)) && !c.w2) return false;
+    if ((f & FORM_PAIR) && (c.nsplit <= 0 || c.nsplit >= d->N)) return false;
+    return true;
+}
+
+static ConvArgs make_args(const sgg_conv_desc* d, const ConvCall& c) {
+    ConvArgs a;
+    a.src = (const char*)c.src; a.wmat = (const char*)c.w; a.bias = c.bias; a.dst = (char*)c.dst; a.addend = (const char*)c.addend; a.fold = nullptr;
+    a.stats = c.stats; a.nx = (const char*)c.nx; a.nstats = c.nstats; a.ngamma = c.ngamma; a.nbeta = c.nbeta; a.nact = c.nact; a.nleak = c.nleak;
+    a.nout = (char*)c.nout; a.ngamma2 = c.ngamma2; a.nbeta2 = c.nbeta2;
+    a.partial = nullptr; a.ksplit = 1; a.pdst = 0;
+    a.wmat2 = (const char*)c.w2; a.bias2 = c.bias2; a.nsplit = 0x7fffffff;
+    a.grp = 1; a.net_src = a.net_dst = a.net_add = a.net_part = 0;
+    a.dst_f32 = (c.form & FORM_MIXED) != 0; a.addend_f32 = c.addend_f32;
+    a.ablate = sgg_config().ablate;
+    a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->C; a.K = d->K; a.R = d->R; a.S = d->S; a.stride = d->stride;
+    a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.Ho = d->Ho; a.Wo = d->Wo; a.reflect = d->pad_mode == SGG_PAD_REFLECT;
+    a.act = c.act; a.leak = c.leak;
+    return a;
+}
+
+// conv7_narrow_out_kernel's arguments: the head's forward, or the stem's data gradient on the PADDED grid (a zero-padded "full"
+// correlation of dy with the mirrored taps, f32, into ws)
+static N7Args n7_args(const sgg_conv_desc* d, int dir, const ConvCall& c) {
+    const bool fwd = dir == MODE_FWD;
+    N7Args q;
+    q.src = (const char*)c.src; q.wmat = (const char*)c.w; q.bias = fwd ? c.bias : nullptr; q.dst = fwd ? c.dst : c.ws;
+    q.N = d->N; q.H = d->H; q.W = d->W; q.Ho = fwd ? d->Ho : d->H + 6; q.Wo = fwd ? d->Wo : d->W + 6; q.pt = q.pl = fwd ? 3 : 6; q.K = 3;
+    q.reflect = fwd && d->pad_mode == SGG_PAD_REFLECT; q.flip = !fwd; q.act = fwd ? c.act : SGG_ACT_NONE; q.leak = fwd ? c.leak : 0.f; q.dst_f32 = !fwd;
+    return q;
+}
+
+// ---- one dtype switch per kernel family
+static int launch_halo_narrow_in(const sgg_conv_desc* d, const ConvArgs& a, int flip, hipStream_t s) {
+    return d->dtype == SGG_BF16 ? launch_halo_narrow_in_t<bf16>(d, a, flip, s) : launch_halo_narrow_in_t<float>(d, a, flip, s);
+}
+static int launch_halo_fwd(const sgg_conv_desc* d, const ConvArgs& a, int flip, hipStream_t s) {
+    return d->dtype == SGG_BF16 ? launch_halo_fwd_t<bf16>(d, a, flip, s) : launch_halo_fwd_t<float>(d, a, flip, s);
+}
+template <typename T, int MODE>
+static int launch_glds(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    switch (p.gemm & ~SGG_ROUTE_SPLITK) {
+    case SGG_ROUTE_GLDS_256x256:
+        return launch_glds_cfg<T, MODE, 256, 256, 2, 8, 128, 2>(a, p.Mmax, p.DC, p.classes, s);
+    case SGG_ROUTE_GLDS_256x128:
+        // three LDS stages (48 KB each): its layers (c2 forward, d2 data gradient, D.h1 forward) gather their pixel operand from HBM
+        // with 9 short K-tiles per block; two tiles in flight instead of one: 96.8 -> 93.4 us (c2), 26.4 -> 25.3 us (D.h1)
+        return launch_glds_cfg<T, MODE, 256, 128, 4, 8, 128, 3>(a, p.Mmax, p.DC, p.classes, s);
+    case SGG_ROUTE_GLDS_128x128:
+        return launch_glds_cfg<T, MODE, 128, 128, 2, 8>(a, p.Mmax, p.DC, p.classes, s);
+    case SGG_ROUTE_GLDS_128x64:
+        return launch_glds_cfg<T, MODE, 128, 64, 4, 4>(a, p.Mmax, p.DC, p.classes, s);
+    case SGG_ROUTE_GLDS_256x16:
+        return launch_glds_cfg<T, MODE, 256, 16, 4, 4>(a, p.Mmax, p.DC, p.classes, s);
+    default: return SGG_EUNSUPPORTED;                    // (plan_conv names no other GEMM route)
+    }
+}
+// the GEMM planner's kernel
+static int launch_gemm(const sgg_conv_desc* d, int dir, const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    if (p.gemm == SGG_ROUTE_S2HALO) return launch_s2halo(a, s);
+    if (p.gemm == SGG_ROUTE_HALO3) return launch_halo3(a, dir, s);
+    if (d->dtype == SGG_BF16) return dir == MODE_FWD ? launch_glds<bf16, MODE_FWD>(a, p, s) : launch_glds<bf16, MODE_DGRAD>(a, p, s);
+    return dir == MODE_FWD ? launch_glds<float, MODE_FWD>(a, p, s) : launch_glds<float, MODE_DGRAD>(a, p, s);
+}
+// the side tensor of a REFLECT data gradient on the GEMM: the gather rows of the border pixels, pre-folded, which ONE GEMM
+// launch then reads like any other source (the LDS-resident 3x3 kernel reads a smaller one of its own layout)
+static int launch_fold_gather(const sgg_conv_desc* d, const ConvPlan& p, const void* dy, void* fold, hipStream_t s) {
+    const size_t es = d->dtype == SGG_BF16 ? 2 : 4;
+    const bool halo3 = p.gemm == SGG_ROUTE_HALO3;
+    const int64_t total = halo3 ? ((int64_t)d->N * d->H * 18 + (int64_t)d->N * 2 * d->W) * d->K * es / 16
+                                : (int64_t)d->N * fold_border_per_image(d->H, d->W, d->pad_t) * d->R * d->S * d->K * es / 16;
+    int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
+    if (halo3) hipLaunchKernelGGL(fold_halo_gather_kernel<bf16>, dim3(blocks), dim3(256), 0, s, (const char*)dy, (char*)fold, d->N, d->H, d->W, d->K);
+    else if (d->dtype == SGG_BF16) hipLaunchKernelGGL(fold_gather_kernel<bf16>, dim3(blocks), dim3(256), 0, s, (const char*)dy, (char*)fold, d->N, d->H, d->W, d->K, d->R, d->S, d->pad_t, d->Ho, d->Wo);
+    else hipLaunchKernelGGL(fold_gather_kernel<float>, dim3(blocks), dim3(256), 0, s, (const char*)dy, (char*)fold, d->N, d->H, d->W, d->K, d->R, d->S, d->pad_t, d->Ho, d->Wo);
+    return sgg_check_launch();
+}
+static int launch_splitk_reduce(const sgg_conv_desc* d, const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const int64_t nvec4 = (int64_t)p.pdst * p.DC / 4;
+    int blocks = (int)((nvec4 + 255) / 256); if (blocks > 2048) blocks = 2048;
+    const SplitKGroup g2{a.bias2, a.net_part, a.net_dst, a.net_add};
+    if (d->dtype == SGG_BF16) hipLaunchKernelGGL(splitk_reduce_kernel<bf16>, dim3(blocks, a.grp), dim3(256), 0, s, (const float*)a.partial, a.bias, a.addend, a.dst, nvec4, p.DC, p.ksplit, p.pdst * p.DC, a.act, a.leak, g2);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks, a.grp), dim3(256), 0, s, (const float*)a.partial, a.bias, a.addend, a.dst, nvec4, p.DC, p.ksplit, p.pdst * p.DC, a.act, a.leak, g2);
+    return sgg_check_launch();
+}
+
+// Every conv launch entry.  Before anything is launched, in this order: SGG_EINVAL (descriptor, required pointers, nsplit),
+// SGG_EUNSUPPORTED (the shape or dtype has no such form), SGG_EWORKSPACE (ws is NULL or shorter than the plan's total).
+static int run_conv(const sgg_conv_desc* d, int dir, const ConvCall& c) {
+    const int f = c.form;
+    if (!conv_call_ok(d, c)) return SGG_EINVAL;
+    const ConvPlan p = plan_conv(d, dir, c.addend != nullptr, (f & (FORM_STATS | FORM_NORM_BWD)) != 0, (f & FORM_DECONV) != 0);
+    if ((f & FORM_NORM_BWD) && c.nact == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
+    if (((f & (FORM_STATS | FORM_NORM_BWD)) && !p.stats_chunks) || ((f & FORM_MIXED) && !p.mixed) || ((f & FORM_PAIR) && !p.pair) ||
+        ((f & FORM_NORMLOAD) && !p.normload)) return SGG_EUNSUPPORTED;
+    const bool group = (f & FORM_GROUP) != 0;
+    const size_t need = p.ws_bytes * (group ? 2 : 1);
+    if (need && (!c.ws || c.ws_bytes < need)) return SGG_EWORKSPACE;
+    hipStream_t s = (hipStream_t)c.stream;
+
+    // the second network of a grouped call reads / writes at these byte offsets (dir DGRAD: src is the conv's output side)
+    const size_t es = d->dtype == SGG_BF16 ? 2 : 4;
+    const size_t in_bytes = (size_t)d->N * d->H * d->W * d->C * es, out_bytes = (size_t)d->N * d->Ho * d->Wo * d->K * es;
+    const size_t net_src = dir == MODE_FWD ? in_bytes : out_bytes, net_dst = dir == MODE_FWD ? out_bytes : in_bytes;
+    if (group && p.group == GROUP_TWO_CALLS) {
+        ConvCall one = c;
+        one.form = f & ~FORM_GROUP;
+        conv_call_pair(one, nullptr, nullptr, 0);
+        const int rc = run_conv(d, dir, one);
+        if (rc) return rc;
+        one.src = (const char*)c.src + net_src; one.w = c.w2; one.bias = c.bias2; one.dst = (char*)c.dst + net_dst;
+        if (c.addend) one.addend = (const char*)c.addend + net_dst;
+        return run_conv(d, dir, one);
+    }
+    const bool stacked = group && p.group == GROUP_STACKED;
+    sgg_conv_desc ds = *d;
+    if (stacked) ds.N = 2 * d->N;
+    ConvArgs a = make_args(&ds, c);
+    if (stacked) a.nsplit = d->N;
+    else if (group) { a.grp = 2; a.net_src = net_src; a.net_dst = a.net_add = net_dst; }
+    else if (c.w2) a.nsplit = c.nsplit;
+
+    switch (p.route) {
+    case SGG_ROUTE_HALO_NARROW_IN:                       // forward of a narrow-INPUT conv (the stem), data gradient of a narrow-OUTPUT one (the head)
+    case SGG_ROUTE_HALO_DGRAD_NARROW: {
+        int rc;
+        if (p.route == SGG_ROUTE_HALO_NARROW_IN) rc = launch_halo_narrow_in(d, a, dir == MODE_DGRAD, s);
+        else {
+            ConvArgs h = a;                              // the same computation written as a forward conv over dy
+            h.C = d->K; h.K = d->C; h.reflect = 0;
+            rc = launch_halo_fwd(d, h, 1, s);
+        }
+        if (rc || dir == MODE_FWD || !a.reflect) return rc;
+        return launch_border(d, a, s);                   // REFLECT: + the mirrored (MirrorPadGrad) terms of the border pixels
+    }
+    case SGG_ROUTE_S2N:                                  // (D.h0; a grouped call: the stacked batch, weights picked per image)
+        return launch_s2n_dgrad(&ds, c.src, c.w, stacked ? c.w2 : nullptr, d->N, c.addend, c.dst, s);
+    case SGG_ROUTE_N7: {
+        const int rc = launch_n7(n7_args(d, dir, c), s);
+        if (rc || dir == MODE_FWD) return rc;
+        // the stem: then MirrorPadGrad as a fold of the 3-pixel frame onto the image (the addend joins here) -- one rounding, no separate border GEMM
+        const int64_t total = (int64_t)d->N * d->H * d->W;
+        int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
+        hipLaunchKernelGGL(pad3_fold_kernel, dim3(blocks), dim3(256), 0, s, (const f32x4*)c.ws, (const char*)c.addend, (char*)c.dst, d->N, d->H, d->W);
+        return sgg_check_launch();
+    }
+    case SGG_ROUTE_HALO_FWD: return launch_halo_fwd(d, a, 0, s);
+    default: break;                                      // the GEMM planner's kernel
+    }
+    if (p.fold_bytes) {
+        const int rc = launch_fold_gather(d, p, c.src, c.ws, s);
+        if (rc) return rc;
+        a.fold = (const char*)c.ws;
+    }
+    if (p.ksplit > 1) { a.ksplit = p.ksplit; a.partial = (float*)((char*)c.ws + p.fold_bytes); a.pdst = p.pdst; a.net_part = p.splitk_bytes; }
+    const int rc = launch_gemm(d, dir, a, p, s);
+    if (rc || p.ksplit <= 1) return rc;
+    return launch_splitk_reduce(d, a, p, s);             // out = act(sum of the slabs + bias) + addend, in a fixed order
 }
 
 extern "C" {
@@ -2028,286 +2189,159 @@ int sgg_pack_conv_weights_batch(const sgg_pack_item* items_dev, int n_items, int
     return sgg_check_launch();
 }
 
-size_t sgg_conv2d_fwd_workspace(const sgg_conv_desc* d) {
-    return desc_ok(d) ? plan_gemm(d, MODE_FWD).ws_bytes : 0;
-}
+// ---- the queries: fields of the plan (0 / SGG_EINVAL for a descriptor the library rejects)
+static inline bool deconv_desc_ok(const sgg_conv_desc* d) { return desc_ok(d) && d->pad_mode == SGG_PAD_ZERO; }
 
-int sgg_conv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float leak,
-                   void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || !x || !w || !y) return SGG_EINVAL;
-    ConvArgs a = make_args(d, x, w, bias, y, act, leak);
-    switch (conv_fwd_head_route(d)) {
-    case SGG_ROUTE_HALO_NARROW_IN:
-        return d->dtype == SGG_BF16 ? launch_halo_narrow_in<bf16>(d, a, 0, (hipStream_t)stream) : launch_halo_narrow_in<float>(d, a, 0, (hipStream_t)stream);
-    case SGG_ROUTE_N7: {
-        N7Args q;
-        q.src = (const char*)x; q.wmat = (const char*)w; q.bias = bias; q.dst = y;
-        q.N = d->N; q.H = d->H; q.W = d->W; q.Ho = d->Ho; q.Wo = d->Wo; q.pt = 3; q.pl = 3; q.K = 3;
-        q.reflect = d->pad_mode == SGG_PAD_REFLECT; q.flip = 0; q.act = act; q.leak = leak; q.dst_f32 = 0;
-        return launch_n7(q, (hipStream_t)stream);
-    }
-    case SGG_ROUTE_HALO_FWD:
-        return d->dtype == SGG_BF16 ? launch_halo_fwd<bf16>(d, a, (hipStream_t)stream) : launch_halo_fwd<float>(d, a, (hipStream_t)stream);
-    default:
-        return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                    : run_gemm<float, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
-    }
-}
+size_t sgg_conv2d_fwd_workspace(const sgg_conv_desc* d) { return desc_ok(d) ? plan_ws_query(plan_conv(d, MODE_FWD, false, false)) : 0; }
+size_t sgg_conv2d_bwd_data_workspace(const sgg_conv_desc* d) { return desc_ok(d) ? plan_ws_query(plan_conv(d, MODE_DGRAD, false, false)) : 0; }
+// a transposed conv runs the conv's data-gradient GEMM forwards and its forward GEMM backwards, without the conv entry points' head routes
+size_t sgg_deconv2d_fwd_workspace(const sgg_conv_desc* d) { return desc_ok(d) ? plan_conv(d, MODE_DGRAD, false, false, true).splitk_bytes : 0; }
+size_t sgg_deconv2d_bwd_data_workspace(const sgg_conv_desc* d) { return desc_ok(d) ? plan_conv(d, MODE_FWD, false, false, true).splitk_bytes : 0; }
 
 int sgg_conv2d_route(const sgg_conv_desc* d, int op) {
     if (!desc_ok(d) || op < 0 || op > 2) return SGG_EINVAL;
     if (op == 2) return wgrad_route(d);      // C_real <= 4 assumed where it matters (S2N), see include/sggan.h
-    const int head = op == 0 ? conv_fwd_head_route(d) : conv_dgrad_head_route(d, false, false);
-    return head ? head : run_gemm_route(d, op == 0 ? MODE_FWD : MODE_DGRAD);
+    return plan_conv(d, op == 0 ? MODE_FWD : MODE_DGRAD, false, false).route;
 }
-// a transposed conv runs the conv's data-gradient GEMM forwards and its forward GEMM backwards, without the conv entry points' special kernels
 int sgg_deconv2d_route(const sgg_conv_desc* d, int op) {
-    if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || op < 0 || op > 2) return SGG_EINVAL;
+    if (!deconv_desc_ok(d) || op < 0 || op > 2) return SGG_EINVAL;
     if (op == 2) return wgrad_route(d);      // C_real <= 4 assumed where it matters (S2N), see include/sggan.h
-    return run_gemm_route(d, op == 0 ? MODE_DGRAD : MODE_FWD);
+    return plan_conv(d, op == 0 ? MODE_DGRAD : MODE_FWD, false, false, true).route;
 }
 
-// Pixel chunks per image of the (sum, sumsq) rows sgg_conv2d_fwd_stats() emits; 0 = this shape has no such epilogue
-static size_t halo3_fwd_stats_chunks(const sgg_conv_desc* d) {           // the LDS-resident 3x3 kernel: a row per (2 x 128 tile, tile row)
-    if (!desc_ok(d) || d->dtype != SGG_BF16) return 0;
-    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-    if (plan_gemm(d, MODE_FWD).ksplit > 1 || !halo3_ok(a, MODE_FWD, true)) return 0;
-    return halo3_stats_chunks(d);
-}
-size_t sgg_conv2d_fwd_stats_chunks(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16) return 0;
-    if (halo_narrow_in_ok(d, d->C, d->K)) return (size_t)(d->H / HALO_TH) * (d->W / HALO_TW);   // the stem: a row per 16 x 32 tile
-    return halo3_fwd_stats_chunks(d);
+// Pixel chunks per image of the statistics rows the *_stats entries emit; 0 = this shape has no such epilogue
+size_t sgg_conv2d_fwd_stats_chunks(const sgg_conv_desc* d) { return desc_ok(d) ? plan_conv(d, MODE_FWD, false, true).stats_chunks : 0; }
+size_t sgg_conv2d_bwd_data_stats_chunks(const sgg_conv_desc* d) { return desc_ok(d) ? plan_conv(d, MODE_DGRAD, false, true).stats_chunks : 0; }
+size_t sgg_deconv2d_fwd_stats_chunks(const sgg_conv_desc* d) { return deconv_desc_ok(d) ? plan_conv(d, MODE_DGRAD, false, true, true).stats_chunks : 0; }
+
+int sgg_conv2d_bwd_data_mixed_supported(const sgg_conv_desc* d) { return desc_ok(d) && plan_conv(d, MODE_DGRAD, false, false).mixed; }
+int sgg_conv2d_pair_supported(const sgg_conv_desc* d) { return desc_ok(d) && plan_conv(d, MODE_FWD, false, true).pair; }
+int sgg_conv2d_fwd_normload_supported(const sgg_conv_desc* d) { return desc_ok(d) && plan_conv(d, MODE_FWD, false, true).normload; }
+
+// ---- the launch entries: each fills a ConvCall
+int sgg_conv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float leak,
+                   void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c = conv_call(0, x, w, bias, y, ws, ws_bytes, stream);
+    c.act = act; c.leak = leak;
+    return run_conv(d, MODE_FWD, c);
 }
 
 int sgg_conv2d_fwd_stats(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* partial,
                          void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || !x || !w || !y || !partial) return SGG_EINVAL;
-    if (sgg_conv2d_fwd_stats_chunks(d) == 0) return SGG_EUNSUPPORTED;
-    ConvArgs a = make_args(d, x, w, bias, y, SGG_ACT_NONE, 0.f);
-    a.stats = partial;
-    if (halo_narrow_in_ok(d, d->C, d->K)) return launch_halo_narrow_in<bf16>(d, a, 0, (hipStream_t)stream);
-    return run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    ConvCall c = conv_call(FORM_STATS, x, w, bias, y, ws, ws_bytes, stream);
+    c.stats = partial;
+    return run_conv(d, MODE_FWD, c);
 }
 
-static size_t fold_bytes(const sgg_conv_desc* d) {
-    if (d->pad_mode != SGG_PAD_REFLECT) return 0;
-    size_t es = d->dtype == SGG_BF16 ? 2 : 4;
-    return align_up((size_t)d->N * fold_border_per_image(d->H, d->W, d->pad_t) * d->R * d->S * d->K * es, 256);
+// Two networks of one shape on a stacked batch (images >= nsplit use the second weight set): one launch of the LDS-resident
+// 3x3 kernels instead of two -- 512 blocks, so a CU's second block loads its halo while the first one's stores drain.
+int sgg_conv2d_fwd_stats_pair(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, const void* w2, const float* bias2,
+                              int nsplit, void* y, float* partial, void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c = conv_call(FORM_STATS | FORM_PAIR, x, w, bias, y, ws, ws_bytes, stream);
+    c.stats = partial;
+    conv_call_pair(c, w2, bias2, nsplit);
+    return run_conv(d, MODE_FWD, c);
 }
 
-size_t sgg_conv2d_bwd_data_workspace(const sgg_conv_desc* d) {
-    if (!desc_ok(d)) return 0;
-    if (conv7_stem_ok(d)) return n7_dgrad_ws(d);
-    return fold_bytes(d) + plan_gemm(d, MODE_DGRAD).ws_bytes;
-}
-
-struct NormBwdStats { const void* nx; const float* nstats; const float* ngamma; const float* nbeta; int nact; float nleak; float* partial; int mixed; const void* w2; int nsplit; };
-
-static int conv2d_bwd_data_impl(const sgg_conv_desc* d, const void* dy, const void* w, const void* addend, void* dx, const NormBwdStats* nb,
-                                void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || !dy || !w || !dx) return SGG_EINVAL;
-    ConvArgs a = make_args(d, dy, w, nullptr, dx, SGG_ACT_NONE, 0.f);
-    a.addend = (const char*)addend;
-    if (nb && nb->w2) { a.wmat2 = (const char*)nb->w2; a.nsplit = nb->nsplit; }
-    if (nb && nb->mixed) { a.dst_f32 = nb->mixed & 1; a.addend_f32 = (nb->mixed >> 1) & 1; }
-    if (nb && nb->partial) {
-        a.stats = nb->partial; a.nx = (const char*)nb->nx; a.nstats = nb->nstats; a.ngamma = nb->ngamma; a.nbeta = nb->nbeta;
-        a.nact = nb->nact; a.nleak = nb->nleak;
-    } else nb = nullptr;                                 // from here on `nb` means: norm-backward sums wanted
-    const int head = conv_dgrad_head_route(d, addend != nullptr, nb != nullptr);
-    switch (head) {
-    case SGG_ROUTE_HALO_NARROW_IN: {                     // data-gradient of a narrow-OUTPUT conv (the head): dy has 8 channels
-        int rc0 = d->dtype == SGG_BF16 ? launch_halo_narrow_in<bf16>(d, a, 1, (hipStream_t)stream) : launch_halo_narrow_in<float>(d, a, 1, (hipStream_t)stream);
-        if (rc0 || !a.reflect) return rc0;
-        return launch_border(d, a, (hipStream_t)stream);   // REFLECT: + the mirrored (MirrorPadGrad) terms of the border pixels
-    }
-    case SGG_ROUTE_S2N: return launch_s2n_dgrad(d, dy, w, nullptr, 0, addend, dx, (hipStream_t)stream);
-    case SGG_ROUTE_N7: {                                 // (addend: joined in the fold pass, before its one rounding)
-        // the stem: data gradient on the PADDED grid (a zero-padded "full" correlation of dy with the mirrored taps, f32),
-        // then MirrorPadGrad as a fold of the 3-pixel frame onto the image -- one rounding, no separate border GEMM
-        if (!ws || ws_bytes < n7_dgrad_ws(d)) return SGG_EWORKSPACE;
-        N7Args q;
-        q.src = (const char*)dy; q.wmat = (const char*)w; q.bias = nullptr; q.dst = ws;
-        q.N = d->N; q.H = d->H; q.W = d->W; q.Ho = d->H + 6; q.Wo = d->W + 6; q.pt = 6; q.pl = 6; q.K = 3;
-        q.reflect = 0; q.flip = 1; q.act = SGG_ACT_NONE; q.leak = 0.f; q.dst_f32 = 1;
-        int rc0 = launch_n7(q, (hipStream_t)stream);
-        if (rc0) return rc0;
-        const int64_t total = (int64_t)d->N * d->H * d->W;
-        int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(pad3_fold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f32x4*)ws, (const char*)addend, (char*)dx, d->N, d->H, d->W);
-        return sgg_check_launch();
-    }
-    case SGG_ROUTE_HALO_DGRAD_NARROW: {
-        ConvArgs h = a;                                  // the same computation written as a forward conv over dy
-        h.C = d->K; h.K = d->C; h.reflect = 0;
-        int rc0 = d->dtype == SGG_BF16 ? launch_halo_fwd<bf16>(d, h, (hipStream_t)stream, 1) : launch_halo_fwd<float>(d, h, (hipStream_t)stream, 1);
-        if (rc0 || !a.reflect) return rc0;
-        return launch_border(d, a, (hipStream_t)stream);
-    }
-    default: break;                                      // the GEMM planner decides (run_gemm)
-    }
-    const size_t fb = fold_bytes(d);
-    if (fb) {
-        // pre-fold the gather rows of the border pixels, then ONE GEMM launch reads them like any other source
-        if (!ws || ws_bytes < fb) return SGG_EWORKSPACE;
-        size_t es = d->dtype == SGG_BF16 ? 2 : 4;
-        int64_t total = (int64_t)d->N * fold_border_per_image(d->H, d->W, d->pad_t) * d->R * d->S * d->K * es / 16;
-        GemmPlan gp = plan_gemm(d, MODE_DGRAD);
-        ConvArgs probe = a; probe.ksplit = gp.ksplit;
-        const bool halo3 = halo3_ok(probe, MODE_DGRAD, d->dtype == SGG_BF16);
-        if (halo3) total = ((int64_t)d->N * d->H * 18 + (int64_t)d->N * 2 * d->W) * d->K * es / 16;   // smaller side tensor
-        int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
-        if (halo3) hipLaunchKernelGGL(fold_halo_gather_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const char*)dy, (char*)ws, d->N, d->H, d->W, d->K);
-        else if (d->dtype == SGG_BF16) hipLaunchKernelGGL(fold_gather_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const char*)dy, (char*)ws, d->N, d->H, d->W, d->K, d->R, d->S, d->pad_t, d->Ho, d->Wo);
-        else hipLaunchKernelGGL(fold_gather_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const char*)dy, (char*)ws, d->N, d->H, d->W, d->K, d->R, d->S, d->pad_t, d->Ho, d->Wo);
-        a.fold = (const char*)ws;
-    }
-    void* ws2 = ws ? (char*)ws + fb : nullptr;
-    size_t ws2_bytes = ws_bytes > fb ? ws_bytes - fb : 0;
-    int rc = d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_DGRAD>(d, a, ws2, ws2_bytes, (hipStream_t)stream)
-                                  : run_gemm<float, MODE_DGRAD>(d, a, ws2, ws2_bytes, (hipStream_t)stream);
-    return rc;
+// "Normalise on load": conv(relu(instnorm(x_raw))) without the norm's apply pass -- x_raw is the previous conv's raw output,
+// x_stats its (mean, rstd) (sgg_instnorm_finalize), and the normalised tensor comes out in x_norm as a by-product.
+int sgg_conv2d_fwd_stats_normload(const sgg_conv_desc* d, const void* x_raw, const float* x_stats, const float* x_gamma, const float* x_beta,
+                                  const float* x_gamma2, const float* x_beta2, void* x_norm, const void* w, const float* bias,
+                                  const void* w2, const float* bias2, int nsplit, void* y, float* partial,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c = conv_call(FORM_STATS | FORM_NORMLOAD | (w2 ? FORM_PAIR : 0), x_raw, w, bias, y, ws, ws_bytes, stream);
+    c.stats = partial; c.nstats = x_stats; c.ngamma = x_gamma; c.nbeta = x_beta; c.nout = x_norm;
+    if (w2) { conv_call_pair(c, w2, bias2, nsplit); c.ngamma2 = x_gamma2; c.nbeta2 = x_beta2; }
+    return run_conv(d, MODE_FWD, c);
 }
 
 int sgg_conv2d_bwd_data(const sgg_conv_desc* d, const void* dy, const void* w, const void* addend, void* dx, void* ws, size_t ws_bytes, void* stream) {
-    return conv2d_bwd_data_impl(d, dy, w, addend, dx, nullptr, ws, ws_bytes, stream);
+    ConvCall c = conv_call(0, dy, w, nullptr, dx, ws, ws_bytes, stream);
+    c.addend = addend;
+    return run_conv(d, MODE_DGRAD, c);
 }
 
 // Mixed-precision data gradient (bf16 operands, f32 result): only the LDS-resident 3x3 halo GEMM has the epilogue
-int sgg_conv2d_bwd_data_mixed_supported(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16) return 0;
-    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-    return (plan_gemm(d, MODE_DGRAD).ksplit == 1 && halo3_ok(a, MODE_DGRAD, true)) ? 1 : 0;
-}
 int sgg_conv2d_bwd_data_mixed(const sgg_conv_desc* d, const void* dy, const void* w, const void* addend, int addend_is_f32, float* dx,
                               void* ws, size_t ws_bytes, void* stream) {
-    if (!sgg_conv2d_bwd_data_mixed_supported(d)) return SGG_EUNSUPPORTED;
-    NormBwdStats flags{};                            // nb == nullptr semantics, but carries the two mixed flags
-    flags.mixed = 1 | (addend_is_f32 ? 2 : 0);
-    return conv2d_bwd_data_impl(d, dy, w, addend, dx, &flags, ws, ws_bytes, stream);
-}
-
-// Pixel chunks per image of the instance-norm-backward partial sums sgg_conv2d_bwd_data_stats() emits; 0 = unsupported shape
-size_t sgg_conv2d_bwd_data_stats_chunks(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16) return 0;
-    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-    if (plan_gemm(d, MODE_DGRAD).ksplit > 1 || !halo3_ok(a, MODE_DGRAD, true)) return 0;
-    return halo3_stats_chunks(d);
+    ConvCall c = conv_call(FORM_MIXED, dy, w, nullptr, dx, ws, ws_bytes, stream);
+    c.addend = addend; c.addend_f32 = addend_is_f32 ? 1 : 0;
+    return run_conv(d, MODE_DGRAD, c);
 }
 
 int sgg_conv2d_bwd_data_stats(const sgg_conv_desc* d, const void* dy, const void* w, const void* addend, void* dx,
                               const void* norm_x, const float* norm_stats, const float* norm_gamma, const float* norm_beta,
                               int norm_act, float norm_leak, float* partial, void* ws, size_t ws_bytes, void* stream) {
-    if (!norm_x || !norm_stats || !norm_gamma || !norm_beta || !partial) return SGG_EINVAL;
-    if (norm_act == SGG_ACT_TANH) return SGG_EUNSUPPORTED;
-    if (sgg_conv2d_bwd_data_stats_chunks(d) == 0) return SGG_EUNSUPPORTED;
-    NormBwdStats nb{norm_x, norm_stats, norm_gamma, norm_beta, norm_act, norm_leak, partial, 0, nullptr, 0};
-    return conv2d_bwd_data_impl(d, dy, w, addend, dx, &nb, ws, ws_bytes, stream);
+    ConvCall c = conv_call(FORM_NORM_BWD, dy, w, nullptr, dx, ws, ws_bytes, stream);
+    c.addend = addend; c.stats = partial;
+    c.nx = norm_x; c.nstats = norm_stats; c.ngamma = norm_gamma; c.nbeta = norm_beta; c.nact = norm_act; c.nleak = norm_leak;
+    return run_conv(d, MODE_DGRAD, c);
 }
 
-// Two networks of one shape on a stacked batch (images >= nsplit use the second weight set): one launch of the LDS-resident
-// 3x3 kernels instead of two -- 512 blocks, so a CU's second block loads its halo while the first one's stores drain.
-int sgg_conv2d_pair_supported(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16 || d->N < 2) return 0;
-    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-    return (plan_gemm(d, MODE_FWD).ksplit == 1 && plan_gemm(d, MODE_DGRAD).ksplit == 1 && halo3_ok(a, MODE_FWD, true) && halo3_ok(a, MODE_DGRAD, true)) ? 1 : 0;
-}
-int sgg_conv2d_fwd_stats_pair(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, const void* w2, const float* bias2,
-                              int nsplit, void* y, float* partial, void* ws, size_t ws_bytes, void* stream) {
-    if (!sgg_conv2d_pair_supported(d)) return SGG_EUNSUPPORTED;
-    if (!x || !w || !w2 || !y || !partial || nsplit <= 0 || nsplit >= d->N) return SGG_EINVAL;
-    ConvArgs a = make_args(d, x, w, bias, y, SGG_ACT_NONE, 0.f);
-    a.stats = partial; a.wmat2 = (const char*)w2; a.bias2 = bias2; a.nsplit = nsplit;
-    return run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
-}
-// "Normalise on load": conv(relu(instnorm(x_raw))) without the norm's apply pass -- x_raw is the previous conv's raw output,
-// x_stats its (mean, rstd) (sgg_instnorm_finalize), and the normalised tensor comes out in x_norm as a by-product.
-int sgg_conv2d_fwd_normload_supported(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_REFLECT || d->C > halo3_norm_maxc()) return 0;
-    return halo3_fwd_stats_chunks(d) != 0;
-}
-int sgg_conv2d_fwd_stats_normload(const sgg_conv_desc* d, const void* x_raw, const float* x_stats, const float* x_gamma, const float* x_beta,
-                                  const float* x_gamma2, const float* x_beta2, void* x_norm, const void* w, const float* bias,
-                                  const void* w2, const float* bias2, int nsplit, void* y, float* partial,
-                                  void* ws, size_t ws_bytes, void* stream) {
-    if (!sgg_conv2d_fwd_normload_supported(d)) return SGG_EUNSUPPORTED;
-    if (!x_raw || !x_stats || !x_gamma || !x_beta || !x_norm || !w || !y || !partial) return SGG_EINVAL;
-    ConvArgs a = make_args(d, x_raw, w, bias, y, SGG_ACT_NONE, 0.f);
-    a.stats = partial; a.nstats = x_stats; a.ngamma = x_gamma; a.nbeta = x_beta; a.nout = (char*)x_norm;
-    if (w2) {
-        if (!sgg_conv2d_pair_supported(d) || !x_gamma2 || !x_beta2 || nsplit <= 0 || nsplit >= d->N) return SGG_EINVAL;
-        a.wmat2 = (const char*)w2; a.bias2 = bias2; a.nsplit = nsplit; a.ngamma2 = x_gamma2; a.nbeta2 = x_beta2;
-    }
-    return run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
-}
 int sgg_conv2d_bwd_data_pair(const sgg_conv_desc* d, const void* dy, const void* w, const void* w2, int nsplit, const void* addend, void* dx,
                              void* ws, size_t ws_bytes, void* stream) {
-    if (!sgg_conv2d_pair_supported(d)) return SGG_EUNSUPPORTED;
-    if (!w2 || nsplit <= 0 || nsplit >= d->N) return SGG_EINVAL;
-    NormBwdStats flags{};
-    flags.w2 = w2; flags.nsplit = nsplit;
-    return conv2d_bwd_data_impl(d, dy, w, addend, dx, &flags, ws, ws_bytes, stream);
+    ConvCall c = conv_call(FORM_PAIR, dy, w, nullptr, dx, ws, ws_bytes, stream);
+    c.addend = addend;
+    conv_call_pair(c, w2, nullptr, nsplit);
+    return run_conv(d, MODE_DGRAD, c);
 }
 
 // ---- grouped launches: the same call site of TWO networks of one architecture (G_A->B beside G_B->A, D_A beside D_B).  `d`
 // describes ONE network's call (N images); x / y (dy / dx, addend) hold 2N images, the first network's first; the result is
-// exactly that of two single calls (bit for bit: each group runs the single call's tiles and split-K), in ONE launch for the
-// generic GEMM and the stacked-batch halo kernels -- two half-size launches of the discriminators' small maps are latency
-// bound -- and as two launches for the special 7x7 / narrow kernels.  ws >= 2 x the single call's workspace.
-static inline size_t tensor_bytes(const sgg_conv_desc* d, bool out_side) {
-    const size_t es = d->dtype == SGG_BF16 ? 2 : 4;
-    return out_side ? (size_t)d->N * d->Ho * d->Wo * d->K * es : (size_t)d->N * d->H * d->W * d->C * es;
-}
+// exactly that of two single calls (bit for bit: each group runs the single call's tiles and split-K).  How it runs is the
+// plan's `group`; ws >= 2 x the single call's workspace.
 int sgg_conv2d_fwd_group2(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, const void* w2, const float* bias2,
                           void* y, int act, float leak, void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || !x || !w || !w2 || !y) return SGG_EINVAL;
-    const size_t xin = tensor_bytes(d, false), yout = tensor_bytes(d, true);
-    if (halo_narrow_in_ok(d, d->C, d->K) || conv7_head_ok(d) || halo_fwd_ok(d)) {
-        int rc = sgg_conv2d_fwd(d, x, w, bias, y, act, leak, ws, ws_bytes, stream);
-        return rc ? rc : sgg_conv2d_fwd(d, (const char*)x + xin, w2, bias2, (char*)y + yout, act, leak, ws, ws_bytes, stream);
-    }
-    ConvArgs a = make_args(d, x, w, bias, y, act, leak);
-    a.grp = 2; a.wmat2 = (const char*)w2; a.bias2 = bias2; a.net_src = xin; a.net_dst = yout;
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    ConvCall c = conv_call(FORM_GROUP, x, w, bias, y, ws, ws_bytes, stream);
+    c.act = act; c.leak = leak;
+    conv_call_pair(c, w2, bias2, 0);
+    return run_conv(d, MODE_FWD, c);
 }
 int sgg_conv2d_bwd_data_group2(const sgg_conv_desc* d, const void* dy, const void* w, const void* w2, const void* addend, void* dx,
                                void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || !dy || !w || !w2 || !dx) return SGG_EINVAL;
-    const size_t xin = tensor_bytes(d, false), yout = tensor_bytes(d, true);
-    if (s2n_dgrad_ok(d)) {                               // D.h0: one launch over the stacked batch, weights picked per image
-        sgg_conv_desc d2 = *d;
-        d2.N = 2 * d->N;
-        return launch_s2n_dgrad(&d2, dy, w, w2, d->N, addend, dx, (hipStream_t)stream);
-    }
-    const bool special = conv7_stem_ok(d) || (!addend && (halo_narrow_in_ok(d, d->K, d->C) || halo_dgrad_narrow_ok(d))) || fold_bytes(d) > 0;
-    if (special) {                                       // (REFLECT shapes of the 3x3 halo kernel: sgg_conv2d_bwd_data_pair)
-        int rc = sgg_conv2d_bwd_data(d, dy, w, addend, dx, ws, ws_bytes, stream);
-        return rc ? rc : sgg_conv2d_bwd_data(d, (const char*)dy + yout, w2, addend ? (const char*)addend + xin : nullptr, (char*)dx + xin, ws, ws_bytes, stream);
-    }
-    ConvArgs a = make_args(d, dy, w, nullptr, dx, SGG_ACT_NONE, 0.f);
-    a.addend = (const char*)addend;
-    a.grp = 2; a.wmat2 = (const char*)w2; a.net_src = yout; a.net_dst = xin; a.net_add = xin;
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    ConvCall c = conv_call(FORM_GROUP, dy, w, nullptr, dx, ws, ws_bytes, stream);
+    c.addend = addend;
+    conv_call_pair(c, w2, nullptr, 0);
+    return run_conv(d, MODE_DGRAD, c);
 }
-// Conv2DTranspose: `d` is the equivalent forward conv of ONE network (sgg_deconv2d_fwd); x: (2N,Ho,Wo,K), y: (2N,H,W,C)
+
+// ---- Conv2DTranspose: `d` is the equivalent forward conv; x: (N,Ho,Wo,K), y: (N,H,W,C)
+int sgg_deconv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float leak,
+                     void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c = conv_call(FORM_DECONV, x, w, bias, y, ws, ws_bytes, stream);
+    c.act = act; c.leak = leak;
+    return run_conv(d, MODE_DGRAD, c);
+}
+// ... that also emits the per-chunk (sum, sumsq) rows of its stored output for the instance norm behind it (module.py:254-260):
+// one row per (image, 16 x 64 output-pixel tile) of the stride-2 halo kernel, from deconv_s2_stats_kernel.  w2: a stacked batch.
+int sgg_deconv2d_fwd_stats(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, const void* w2, const float* bias2, int nsplit,
+                           void* y, float* partial, void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c = conv_call(FORM_DECONV | FORM_STATS | (w2 ? FORM_PAIR : 0), x, w, bias, y, ws, ws_bytes, stream);
+    c.stats = partial;
+    if (w2) conv_call_pair(c, w2, bias2, nsplit);
+    return run_conv(d, MODE_DGRAD, c);
+}
 int sgg_deconv2d_fwd_group2(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, const void* w2, const float* bias2,
                             void* y, int act, float leak, void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || !x || !w || !w2 || !y) return SGG_EINVAL;
-    ConvArgs a = make_args(d, x, w, bias, y, act, leak);
-    a.grp = 2; a.wmat2 = (const char*)w2; a.bias2 = bias2; a.net_src = tensor_bytes(d, true); a.net_dst = tensor_bytes(d, false);
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    ConvCall c = conv_call(FORM_DECONV | FORM_GROUP, x, w, bias, y, ws, ws_bytes, stream);
+    c.act = act; c.leak = leak;
+    conv_call_pair(c, w2, bias2, 0);
+    return run_conv(d, MODE_DGRAD, c);
+}
+int sgg_deconv2d_bwd_data(const sgg_conv_desc* d, const void* dy, const void* w, void* dx, void* ws, size_t ws_bytes, void* stream) {
+    return run_conv(d, MODE_FWD, conv_call(FORM_DECONV, dy, w, nullptr, dx, ws, ws_bytes, stream));
 }
 int sgg_deconv2d_bwd_data_group2(const sgg_conv_desc* d, const void* dy, const void* w, const void* w2, void* dx,
                                  void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || !dy || !w || !w2 || !dx) return SGG_EINVAL;
-    ConvArgs a = make_args(d, dy, w, nullptr, dx, SGG_ACT_NONE, 0.f);
-    a.grp = 2; a.wmat2 = (const char*)w2; a.net_src = tensor_bytes(d, false); a.net_dst = tensor_bytes(d, true);
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
+    ConvCall c = conv_call(FORM_DECONV | FORM_GROUP, dy, w, nullptr, dx, ws, ws_bytes, stream);
+    conv_call_pair(c, w2, nullptr, 0);
+    return run_conv(d, MODE_FWD, c);
+}
+
+// ---- the weight gradients (conv_wgrad.hip)
+static inline size_t tensor_bytes(const sgg_conv_desc* d, bool out_side) {
+    const size_t es = d->dtype == SGG_BF16 ? 2 : 4;
+    return out_side ? (size_t)d->N * d->Ho * d->Wo * d->K * es : (size_t)d->N * d->H * d->W * d->C * es;
 }
 
 size_t sgg_conv2d_bwd_weight_workspace(const sgg_conv_desc* d) {
@@ -2351,50 +2385,6 @@ int sgg_conv2d_bwd_weight_pair2(const sgg_conv_desc* d, const void* xa0, const v
     if (!w9_pair2_ok(d)) return SGG_EUNSUPPORTED;
     const W9Net nb{xb0, dyb0, xb1, dyb1, dwb};
     return run_w9(d, W9Net{xa0, dya0, xa1, dya1, dwa}, &nb, Cr, Kr, accumulate, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t sgg_deconv2d_fwd_workspace(const sgg_conv_desc* d) {
-    return desc_ok(d) ? plan_gemm(d, MODE_DGRAD).ws_bytes : 0;
-}
-size_t sgg_deconv2d_bwd_data_workspace(const sgg_conv_desc* d) {
-    return desc_ok(d) ? plan_gemm(d, MODE_FWD).ws_bytes : 0;
-}
-
-int sgg_deconv2d_fwd(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float leak,
-                     void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || !x || !w || !y) return SGG_EINVAL;
-    ConvArgs a = make_args(d, x, w, bias, y, act, leak);
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_DGRAD>(d, a, ws, ws_bytes, (hipStream_t)stream);
-}
-
-// Conv2DTranspose forward that also emits the per-chunk (sum, sumsq) rows of its stored output for the instance norm behind it
-// (module.py:254-260): one row per (image, 16 x 64 output-pixel tile) of the stride-2 halo kernel, from deconv_s2_stats_kernel.
-size_t sgg_deconv2d_fwd_stats_chunks(const sgg_conv_desc* d) {
-    if (!desc_ok(d) || d->dtype != SGG_BF16 || d->pad_mode != SGG_PAD_ZERO) return 0;
-    ConvArgs a = make_args(d, nullptr, nullptr, nullptr, nullptr, SGG_ACT_NONE, 0.f);
-    if (!s2halo_ok(a, true)) return 0;
-    return (size_t)(d->Ho / S2_TI) * (d->Wo / S2_TJ);
-}
-int sgg_deconv2d_fwd_stats(const sgg_conv_desc* d, const void* x, const void* w, const float* bias, const void* w2, const float* bias2, int nsplit,
-                           void* y, float* partial, void* ws, size_t ws_bytes, void* stream) {
-    (void)ws; (void)ws_bytes;
-    if (!desc_ok(d) || !x || !w || !y || !partial) return SGG_EINVAL;
-    if (sgg_deconv2d_fwd_stats_chunks(d) == 0) return SGG_EUNSUPPORTED;
-    ConvArgs a = make_args(d, x, w, bias, y, SGG_ACT_NONE, 0.f);
-    a.stats = partial;
-    if (w2) {
-        if (nsplit <= 0 || nsplit >= d->N) return SGG_EINVAL;
-        a.wmat2 = (const char*)w2; a.bias2 = bias2; a.nsplit = nsplit;
-    }
-    return launch_s2halo(a, (hipStream_t)stream);
-}
-
-int sgg_deconv2d_bwd_data(const sgg_conv_desc* d, const void* dy, const void* w, void* dx, void* ws, size_t ws_bytes, void* stream) {
-    if (!desc_ok(d) || d->pad_mode != SGG_PAD_ZERO || !dy || !w || !dx) return SGG_EINVAL;
-    ConvArgs a = make_args(d, dy, w, nullptr, dx, SGG_ACT_NONE, 0.f);
-    return d->dtype == SGG_BF16 ? run_gemm<bf16, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream)
-                                : run_gemm<float, MODE_FWD>(d, a, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int sgg_deconv2d_bwd_weight(const sgg_conv_desc* d, const void* x, const void* dy, float* dw, int Cr, int Kr, int accumulate, void* ws, size_t ws_bytes, void* stream) {

@@ -617,7 +617,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
             }
         }
     }
-    // STATS 2 (data gradient; no bias, no activation -- run_gemm checks).  The norm's input tile (2 rows x 128 pixels x 256
+    // STATS 2 (data gradient; no bias, no activation -- the entry point passes none).  The norm's input tile (2 rows x 128 pixels x 256
     // channels = 128 KB) is first DMA'd into LDS -- the halo and the weight stages are free now -- with coalesced 16-byte
     // pieces, and each lane then picks its 8-byte (pixel, 4 channels) groups out of LDS: 512-byte pixel rows, 16-byte chunk c
     // of pixel p at position c ^ (p & 31), so the 16 pixels a ds_read_b64 touches hit 16 different chunks.
@@ -727,17 +727,18 @@ __global__ __launch_bounds__(512) void conv3x3_halo_gemm_kernel(ConvArgs a) {
 
 // shapes the halo-resident kernel takes: 3x3, stride 1, pad 1 on a same-size output, bf16, 64 | source channels,
 // 128 | W, even H; REFLECT only forward (the REFLECT data gradient needs the mirrored border terms)
-bool halo3_ok(const ConvArgs& a, int mode, bool is_bf16) {
+// (a question about the shape alone: plan_conv never splits K for a shape this kernel takes)
+bool halo3_ok(const sgg_conv_desc* d, int mode) {
     const int en = sgg_config().halo3;
-    if (!en || !is_bf16 || a.ksplit > 1) return false;
-    if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad_t != 1 || a.pad_l != 1 || a.Ho != a.H || a.Wo != a.W) return false;
-    if (a.W % H3_TW || (a.H & 1) || a.H < 4) return false;
-    const int SC = mode == MODE_FWD ? a.C : a.K;
+    if (!en || d->dtype != SGG_BF16) return false;
+    if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->Ho != d->H || d->Wo != d->W) return false;
+    if (d->W % H3_TW || (d->H & 1) || d->H < 4) return false;
+    const int SC = mode == MODE_FWD ? d->C : d->K;
     if (SC % 64) return false;
     // one image of the source and one tile's weight rows below 1 GiB.  The bound dates from a DMA addressing form that is gone
     // (the kernel's addresses are 64-bit); it stays because it decides which kernel a shape is dispatched to
     constexpr int64_t kMaxBytes = (int64_t)1 << 30;
-    if ((int64_t)a.H * a.W * SC * 2 >= kMaxBytes || (int64_t)256 * 9 * SC * 2 >= kMaxBytes) return false;
+    if ((int64_t)d->H * d->W * SC * 2 >= kMaxBytes || (int64_t)256 * 9 * SC * 2 >= kMaxBytes) return false;
     return mode == MODE_FWD || mode == MODE_DGRAD;
 }
 

@@ -76,7 +76,7 @@ static inline bool conv7_stem_ok(const sgg_conv_desc* d) {      // <= 3 (stored 
 }
 
 // ---- conv_halo3.hip: the LDS-resident 3x3 stride-1 GEMM
-bool halo3_ok(const ConvArgs& a, int mode, bool is_bf16);
+bool halo3_ok(const sgg_conv_desc* d, int mode);                                       // the shape runs this kernel in direction `mode`
 int launch_halo3(const ConvArgs& a, int mode, hipStream_t s);                          // picks FOLD / STATS / PAIR / SRC from the arguments
 size_t halo3_stats_chunks(const sgg_conv_desc* d);                                     // statistics rows per image: one per (2 x 128 tile, tile row)
 int halo3_norm_maxc();                                                                 // most source channels "normalise on load" takes

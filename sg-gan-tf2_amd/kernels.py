@@ -197,14 +197,28 @@ def _out(out, shape, dtype, device):
     return out
 
 
+def _conv_launch(span, g, name, nbytes, device, *args, allow=()):
+    """One call of a conv-family entry point sgg_<name>(desc, *args, ws, ws_bytes, stream): the shared workspace (nbytes = 0:
+    NULL), the profiler span (span None: none), the call and the check.  A status in `allow` is returned instead of raised."""
+    ws = workspace(nbytes, device) if nbytes else None
+    pr = _prof(span, g) if span else None
+    if pr: pr.start()
+    rc = getattr(A.lib(), "sgg_" + name)(C.byref(g.desc), *args, _p(ws), nbytes, _s())
+    if rc not in allow:
+        A.check(rc, name)
+    if pr: pr.stop()
+    return rc
+
+
+def _stats_rows(g, chunks, out_partial, device, side="y"):
+    shape = g.y_shape if side == "y" else g.x_shape
+    return _out(out_partial, (shape[0], chunks, shape[3], 2), torch.float32, device)
+
+
 def conv_fwd(g: ConvGeom, x, w_fwd, bias, act=A.ACT_NONE, leak=0.0, out=None):
     assert tuple(x.shape) == g.x_shape and not g.is_deconv, (tuple(x.shape), g.x_shape)
     y = _out(out, g.y_shape, x.dtype, x.device)
-    pr = _prof("conv2d_fwd", g)
-    if pr: pr.start()
-    ws = workspace(g.ws_fwd, x.device) if g.ws_fwd else None
-    A.check(A.lib().sgg_conv2d_fwd(C.byref(g.desc), _p(x), _p(w_fwd), _p(bias), _p(y), act, leak, _p(ws), g.ws_fwd, _s()), "conv2d_fwd")
-    if pr: pr.stop()
+    _conv_launch("conv2d_fwd", g, "conv2d_fwd", g.ws_fwd, x.device, _p(x), _p(w_fwd), _p(bias), _p(y), act, leak)
     return y
 
 
@@ -212,12 +226,8 @@ def conv_fwd_stats(g: ConvGeom, x, w_fwd, bias, out=None, out_partial=None):
     """conv forward (no activation) + the per-chunk (sum, sumsq) rows of its output for the instance norm that follows."""
     assert tuple(x.shape) == g.x_shape and not g.is_deconv and g.stats_chunks > 0
     y = _out(out, g.y_shape, x.dtype, x.device)
-    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x.device)
-    pr = _prof("conv2d_fwd", g)
-    if pr: pr.start()
-    ws = workspace(g.ws_fwd, x.device) if g.ws_fwd else None
-    A.check(A.lib().sgg_conv2d_fwd_stats(C.byref(g.desc), _p(x), _p(w_fwd), _p(bias), _p(y), _p(partial), _p(ws), g.ws_fwd, _s()), "conv2d_fwd_stats")
-    if pr: pr.stop()
+    partial = _stats_rows(g, g.stats_chunks, out_partial, x.device)
+    _conv_launch("conv2d_fwd", g, "conv2d_fwd_stats", g.ws_fwd, x.device, _p(x), _p(w_fwd), _p(bias), _p(y), _p(partial))
     return y, partial
 
 
@@ -225,13 +235,9 @@ def conv_fwd_stats_pair(g: ConvGeom, x, w_fwd, bias, w_fwd2, bias2, nsplit, out=
     """conv_fwd_stats over a stacked batch of two networks: images [:nsplit] with (w_fwd, bias), the rest with (w_fwd2, bias2)."""
     assert tuple(x.shape) == g.x_shape and g.pair_ok and g.stats_chunks > 0 and 0 < nsplit < g.x_shape[0]
     y = _out(out, g.y_shape, x.dtype, x.device)
-    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x.device)
-    pr = _prof("conv2d_fwd_pair", g)
-    if pr: pr.start()
-    ws = workspace(g.ws_fwd, x.device) if g.ws_fwd else None
-    A.check(A.lib().sgg_conv2d_fwd_stats_pair(C.byref(g.desc), _p(x), _p(w_fwd), _p(bias), _p(w_fwd2), _p(bias2), nsplit, _p(y), _p(partial),
-                                              _p(ws), g.ws_fwd, _s()), "conv2d_fwd_stats_pair")
-    if pr: pr.stop()
+    partial = _stats_rows(g, g.stats_chunks, out_partial, x.device)
+    _conv_launch("conv2d_fwd_pair", g, "conv2d_fwd_stats_pair", g.ws_fwd, x.device,
+                 _p(x), _p(w_fwd), _p(bias), _p(w_fwd2), _p(bias2), nsplit, _p(y), _p(partial))
     return y, partial
 
 
@@ -243,15 +249,11 @@ def conv_fwd_stats_normload(g: ConvGeom, x_raw, x_stats, gamma, beta, w_fwd, bia
     assert tuple(x_raw.shape) == g.x_shape and g.normload_ok and g.stats_chunks > 0
     x_norm = _out(out_norm, g.x_shape, x_raw.dtype, x_raw.device)
     y = _out(out, g.y_shape, x_raw.dtype, x_raw.device)
-    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x_raw.device)
+    partial = _stats_rows(g, g.stats_chunks, out_partial, x_raw.device)
     gamma2, beta2, w2, bias2, nsplit = pair if pair is not None else (None, None, None, None, 0)
-    pr = _prof("conv2d_fwd_normload" + ("_pair" if pair is not None else ""), g)
-    if pr: pr.start()
-    ws = workspace(g.ws_fwd, x_raw.device) if g.ws_fwd else None
-    A.check(A.lib().sgg_conv2d_fwd_stats_normload(C.byref(g.desc), _p(x_raw), _p(x_stats), _p(gamma), _p(beta), _p(gamma2), _p(beta2),
-                                                  _p(x_norm), _p(w_fwd), _p(bias), _p(w2), _p(bias2), nsplit, _p(y), _p(partial),
-                                                  _p(ws), g.ws_fwd, _s()), "conv2d_fwd_stats_normload")
-    if pr: pr.stop()
+    _conv_launch("conv2d_fwd_normload" + ("_pair" if pair is not None else ""), g, "conv2d_fwd_stats_normload", g.ws_fwd, x_raw.device,
+                 _p(x_raw), _p(x_stats), _p(gamma), _p(beta), _p(gamma2), _p(beta2), _p(x_norm), _p(w_fwd), _p(bias), _p(w2), _p(bias2), nsplit,
+                 _p(y), _p(partial))
     return x_norm, y, partial
 
 
@@ -267,12 +269,8 @@ def conv_dgrad_pair(g: ConvGeom, dy, w_dgrad, w_dgrad2, nsplit, addend=None, out
     assert tuple(dy.shape) == g.y_shape and g.pair_ok and 0 < nsplit < g.y_shape[0]
     assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype == dy.dtype)
     dx = _out(out, g.x_shape, dy.dtype, dy.device)
-    pr = _prof("conv2d_bwd_data_pair", g)
-    if pr: pr.start()
-    ws = workspace(g.ws_dgrad, dy.device) if g.ws_dgrad else None
-    A.check(A.lib().sgg_conv2d_bwd_data_pair(C.byref(g.desc), _p(dy), _p(w_dgrad), _p(w_dgrad2), nsplit, _p(addend), _p(dx), _p(ws), g.ws_dgrad, _s()),
-            "conv2d_bwd_data_pair")
-    if pr: pr.stop()
+    _conv_launch("conv2d_bwd_data_pair", g, "conv2d_bwd_data_pair", g.ws_dgrad, dy.device,
+                 _p(dy), _p(w_dgrad), _p(w_dgrad2), nsplit, _p(addend), _p(dx))
     return dx
 
 
@@ -280,23 +278,16 @@ def conv_dgrad(g: ConvGeom, dy, w_dgrad, addend=None, out_f32=False, out=None):
     """dx = conv^T(dy) (+ addend: the skip-connection gradient, fused into the epilogue).  out_f32 (mixed mode, needs
     g.dgrad_mixed): bf16 operands, dx in float32; the addend may then be bf16 or float32."""
     assert tuple(dy.shape) == g.y_shape and not g.is_deconv
-    pr = _prof("conv2d_bwd_data", g)
-    ws = workspace(g.ws_dgrad, dy.device) if g.ws_dgrad else None
     if out_f32:
         assert g.dgrad_mixed and dy.dtype == torch.bfloat16
         assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype in (torch.bfloat16, torch.float32))
         dx = _out(out, g.x_shape, torch.float32, dy.device)
-        if pr: pr.start()
-        A.check(A.lib().sgg_conv2d_bwd_data_mixed(C.byref(g.desc), _p(dy), _p(w_dgrad), _p(addend),
-                                                  int(addend is not None and addend.dtype == torch.float32), _p(dx), _p(ws), g.ws_dgrad, _s()),
-                "conv2d_bwd_data_mixed")
-        if pr: pr.stop()
+        _conv_launch("conv2d_bwd_data", g, "conv2d_bwd_data_mixed", g.ws_dgrad, dy.device,
+                     _p(dy), _p(w_dgrad), _p(addend), int(addend is not None and addend.dtype == torch.float32), _p(dx))
         return dx
     assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype == dy.dtype)
     dx = _out(out, g.x_shape, dy.dtype, dy.device)
-    if pr: pr.start()
-    A.check(A.lib().sgg_conv2d_bwd_data(C.byref(g.desc), _p(dy), _p(w_dgrad), _p(addend), _p(dx), _p(ws), g.ws_dgrad, _s()), "conv2d_bwd_data")
-    if pr: pr.stop()
+    _conv_launch("conv2d_bwd_data", g, "conv2d_bwd_data", g.ws_dgrad, dy.device, _p(dy), _p(w_dgrad), _p(addend), _p(dx))
     return dx
 
 
@@ -307,26 +298,16 @@ def conv_dgrad_stats(g: ConvGeom, dy, w_dgrad, addend, norm_x, norm_stats, norm_
     assert tuple(norm_x.shape) == g.x_shape and norm_x.dtype == dy.dtype
     assert addend is None or (tuple(addend.shape) == g.x_shape and addend.dtype == dy.dtype)
     dx = _out(out, g.x_shape, dy.dtype, dy.device)
-    partial = _out(out_partial, (g.x_shape[0], g.bwd_stats_chunks, g.x_shape[3], 2), torch.float32, dy.device)
-    pr = _prof("conv2d_bwd_data", g)
-    if pr: pr.start()
-    ws = workspace(g.ws_dgrad, dy.device) if g.ws_dgrad else None
-    A.check(A.lib().sgg_conv2d_bwd_data_stats(C.byref(g.desc), _p(dy), _p(w_dgrad), _p(addend), _p(dx), _p(norm_x), _p(norm_stats),
-                                              _p(norm_gamma), _p(norm_beta), norm_act, norm_leak, _p(partial), _p(ws), g.ws_dgrad, _s()),
-            "conv2d_bwd_data_stats")
-    if pr: pr.stop()
+    partial = _stats_rows(g, g.bwd_stats_chunks, out_partial, dy.device, side="x")
+    _conv_launch("conv2d_bwd_data", g, "conv2d_bwd_data_stats", g.ws_dgrad, dy.device, _p(dy), _p(w_dgrad), _p(addend), _p(dx),
+                 _p(norm_x), _p(norm_stats), _p(norm_gamma), _p(norm_beta), norm_act, norm_leak, _p(partial))
     return dx, partial
 
 
 def conv_wgrad(g: ConvGeom, x, dy, dw, accumulate=False):
     """dw: f32 (R,S,C_real,K_real) view to write / accumulate into."""
     assert tuple(x.shape) == g.x_shape and tuple(dy.shape) == g.y_shape and dw.dtype == torch.float32
-    ws = workspace(g.ws_wgrad, x.device)
-    pr = _prof("conv2d_bwd_weight", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_conv2d_bwd_weight(C.byref(g.desc), _p(x), _p(dy), _p(dw), dw.shape[2], dw.shape[3], int(accumulate),
-                                          _p(ws), ws.numel(), _s()), "conv2d_bwd_weight")
-    if pr: pr.stop()
+    _conv_launch("conv2d_bwd_weight", g, "conv2d_bwd_weight", g.ws_wgrad, x.device, _p(x), _p(dy), _p(dw), dw.shape[2], dw.shape[3], int(accumulate))
 
 
 def conv_wgrad_pair(g: ConvGeom, x0, dy0, x1, dy1, dw, accumulate=False):
@@ -334,12 +315,8 @@ def conv_wgrad_pair(g: ConvGeom, x0, dy0, x1, dy1, dw, accumulate=False):
     assert g.wgrad_pair and dw.dtype == torch.float32
     for x, dy in ((x0, dy0), (x1, dy1)):
         assert tuple(x.shape) == g.x_shape and tuple(dy.shape) == g.y_shape
-    ws = workspace(g.ws_wgrad, x0.device)
-    pr = _prof("conv2d_bwd_weight_pair", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_conv2d_bwd_weight_pair(C.byref(g.desc), _p(x0), _p(dy0), _p(x1), _p(dy1), _p(dw), dw.shape[2], dw.shape[3],
-                                               int(accumulate), _p(ws), ws.numel(), _s()), "conv2d_bwd_weight_pair")
-    if pr: pr.stop()
+    _conv_launch("conv2d_bwd_weight_pair", g, "conv2d_bwd_weight_pair", g.ws_wgrad, x0.device,
+                 _p(x0), _p(dy0), _p(x1), _p(dy1), _p(dw), dw.shape[2], dw.shape[3], int(accumulate))
 
 
 def conv_wgrad_pair2(g: ConvGeom, net_a, net_b, accumulate=False):
@@ -351,17 +328,9 @@ def conv_wgrad_pair2(g: ConvGeom, net_a, net_b, accumulate=False):
     for x0, d0, x1, d1, _ in (net_a, net_b):
         for x, dy in ((x0, d0), (x1, d1)):
             assert tuple(x.shape) == g.x_shape and tuple(dy.shape) == g.y_shape
-    ws = workspace(g.ws_wgrad, dwa.device)
-    pr = _prof("conv2d_bwd_weight_pair2", g)
-    if pr: pr.start()
-    rc = A.lib().sgg_conv2d_bwd_weight_pair2(C.byref(g.desc), *[_p(t) for t in net_a], *[_p(t) for t in net_b], dwa.shape[2], dwa.shape[3],
-                                             int(accumulate), _p(ws), ws.numel(), _s())
-    if rc == A.EUNSUPPORTED:
-        if pr: pr.stop()
-        return False
-    A.check(rc, "conv2d_bwd_weight_pair2")
-    if pr: pr.stop()
-    return True
+    rc = _conv_launch("conv2d_bwd_weight_pair2", g, "conv2d_bwd_weight_pair2", g.ws_wgrad, dwa.device,
+                      *[_p(t) for t in net_a], *[_p(t) for t in net_b], dwa.shape[2], dwa.shape[3], int(accumulate), allow=(A.EUNSUPPORTED,))
+    return rc != A.EUNSUPPORTED
 
 
 # ---- grouped launches (sgg_*_group2): the same call site of two networks in one call.  `g` is ONE network's geometry; the tensors
@@ -373,12 +342,8 @@ def _stacked(shape):
 def conv_fwd_group2(g: ConvGeom, x, w_fwd, bias, w_fwd2, bias2, act=A.ACT_NONE, leak=0.0, out=None):
     assert tuple(x.shape) == _stacked(g.x_shape) and not g.is_deconv
     y = _out(out, _stacked(g.y_shape), x.dtype, x.device)
-    ws = workspace(2 * g.ws_fwd, x.device) if g.ws_fwd else None
-    pr = _prof("conv2d_fwd_group2", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_conv2d_fwd_group2(C.byref(g.desc), _p(x), _p(w_fwd), _p(bias), _p(w_fwd2), _p(bias2), _p(y), act, leak,
-                                          _p(ws), 2 * g.ws_fwd, _s()), "conv2d_fwd_group2")
-    if pr: pr.stop()
+    _conv_launch("conv2d_fwd_group2", g, "conv2d_fwd_group2", 2 * g.ws_fwd, x.device,
+                 _p(x), _p(w_fwd), _p(bias), _p(w_fwd2), _p(bias2), _p(y), act, leak)
     return y
 
 
@@ -386,56 +351,37 @@ def conv_dgrad_group2(g: ConvGeom, dy, w_dgrad, w_dgrad2, addend=None, out=None)
     assert tuple(dy.shape) == _stacked(g.y_shape) and not g.is_deconv
     assert addend is None or (tuple(addend.shape) == _stacked(g.x_shape) and addend.dtype == dy.dtype)
     dx = _out(out, _stacked(g.x_shape), dy.dtype, dy.device)
-    ws = workspace(2 * g.ws_dgrad, dy.device) if g.ws_dgrad else None
-    pr = _prof("conv2d_bwd_data_group2", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_conv2d_bwd_data_group2(C.byref(g.desc), _p(dy), _p(w_dgrad), _p(w_dgrad2), _p(addend), _p(dx),
-                                               _p(ws), 2 * g.ws_dgrad, _s()), "conv2d_bwd_data_group2")
-    if pr: pr.stop()
+    _conv_launch("conv2d_bwd_data_group2", g, "conv2d_bwd_data_group2", 2 * g.ws_dgrad, dy.device,
+                 _p(dy), _p(w_dgrad), _p(w_dgrad2), _p(addend), _p(dx))
     return dx
 
 
 def conv_wgrad_group2(g: ConvGeom, x, dy, dw, dw2, accumulate=False):
     """dw (+)= wgrad(x[:N], dy[:N]), dw2 (+)= wgrad(x[N:], dy[N:]): both networks' slabs, one reduce launch."""
     assert tuple(x.shape) == _stacked(g.x_shape) and tuple(dy.shape) == _stacked(g.y_shape) and dw.shape == dw2.shape
-    ws = workspace(2 * g.ws_wgrad, x.device)
-    fn = A.lib().sgg_deconv2d_bwd_weight_group2 if g.is_deconv else A.lib().sgg_conv2d_bwd_weight_group2
-    pr = _prof("bwd_weight_group2", g)
-    if pr: pr.start()
-    A.check(fn(C.byref(g.desc), _p(x), _p(dy), _p(dw), _p(dw2), dw.shape[2], dw.shape[3], int(accumulate), _p(ws), ws.numel(), _s()),
-            "bwd_weight_group2")
-    if pr: pr.stop()
+    _conv_launch("bwd_weight_group2", g, ("deconv2d" if g.is_deconv else "conv2d") + "_bwd_weight_group2", 2 * g.ws_wgrad, x.device,
+                 _p(x), _p(dy), _p(dw), _p(dw2), dw.shape[2], dw.shape[3], int(accumulate))
 
 
 def deconv_fwd_group2(g: ConvGeom, x, w_dgrad, bias, w_dgrad2, bias2, act=A.ACT_NONE, leak=0.0, out=None):
     assert tuple(x.shape) == _stacked(g.x_shape) and g.is_deconv
     y = _out(out, _stacked(g.y_shape), x.dtype, x.device)
-    ws = workspace(2 * g.ws_fwd, x.device) if g.ws_fwd else None
-    pr = _prof("deconv2d_fwd_group2", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_deconv2d_fwd_group2(C.byref(g.desc), _p(x), _p(w_dgrad), _p(bias), _p(w_dgrad2), _p(bias2), _p(y), act, leak,
-                                            _p(ws), 2 * g.ws_fwd, _s()), "deconv2d_fwd_group2")
-    if pr: pr.stop()
+    _conv_launch("deconv2d_fwd_group2", g, "deconv2d_fwd_group2", 2 * g.ws_fwd, x.device,
+                 _p(x), _p(w_dgrad), _p(bias), _p(w_dgrad2), _p(bias2), _p(y), act, leak)
     return y
 
 
 def deconv_dgrad_group2(g: ConvGeom, dy, w_fwd, w_fwd2, out=None):
     assert tuple(dy.shape) == _stacked(g.y_shape) and g.is_deconv
     dx = _out(out, _stacked(g.x_shape), dy.dtype, dy.device)
-    ws = workspace(2 * g.ws_dgrad, dy.device) if g.ws_dgrad else None
-    pr = _prof("deconv2d_bwd_data_group2", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_deconv2d_bwd_data_group2(C.byref(g.desc), _p(dy), _p(w_fwd), _p(w_fwd2), _p(dx), _p(ws), 2 * g.ws_dgrad, _s()),
-            "deconv2d_bwd_data_group2")
-    if pr: pr.stop()
+    _conv_launch("deconv2d_bwd_data_group2", g, "deconv2d_bwd_data_group2", 2 * g.ws_dgrad, dy.device, _p(dy), _p(w_fwd), _p(w_fwd2), _p(dx))
     return dx
 
 
 def deconv_fwd(g: ConvGeom, x, w_dgrad, bias, act=A.ACT_NONE, leak=0.0, out=None):
     assert tuple(x.shape) == g.x_shape and g.is_deconv
     y = _out(out, g.y_shape, x.dtype, x.device)
-    ws = workspace(g.ws_fwd, x.device) if g.ws_fwd else None
-    A.check(A.lib().sgg_deconv2d_fwd(C.byref(g.desc), _p(x), _p(w_dgrad), _p(bias), _p(y), act, leak, _p(ws), g.ws_fwd, _s()), "deconv2d_fwd")
+    _conv_launch(None, g, "deconv2d_fwd", g.ws_fwd, x.device, _p(x), _p(w_dgrad), _p(bias), _p(y), act, leak)
     return y
 
 
@@ -444,30 +390,23 @@ def deconv_fwd_stats(g: ConvGeom, x, w_dgrad, bias, pair=None, out=None, out_par
     pair = (w_dgrad2, bias2, nsplit): `g` describes a stacked batch of two networks, images >= nsplit use the second weight set."""
     assert tuple(x.shape) == g.x_shape and g.is_deconv and g.stats_chunks > 0
     y = _out(out, g.y_shape, x.dtype, x.device)
-    partial = _out(out_partial, (g.y_shape[0], g.stats_chunks, g.y_shape[3], 2), torch.float32, x.device)
+    partial = _stats_rows(g, g.stats_chunks, out_partial, x.device)
     w2, b2, ns = pair if pair is not None else (None, None, 0)
-    pr = _prof("deconv2d_fwd_stats", g)
-    if pr: pr.start()
-    A.check(A.lib().sgg_deconv2d_fwd_stats(C.byref(g.desc), _p(x), _p(w_dgrad), _p(bias), _p(w2), _p(b2), int(ns), _p(y), _p(partial),
-                                           None, 0, _s()), "deconv2d_fwd_stats")
-    if pr: pr.stop()
+    _conv_launch("deconv2d_fwd_stats", g, "deconv2d_fwd_stats", 0, x.device, _p(x), _p(w_dgrad), _p(bias), _p(w2), _p(b2), int(ns), _p(y), _p(partial))
     return y, partial
 
 
 def deconv_dgrad(g: ConvGeom, dy, w_fwd, out=None):
     assert tuple(dy.shape) == g.y_shape and g.is_deconv
     dx = _out(out, g.x_shape, dy.dtype, dy.device)
-    ws = workspace(g.ws_dgrad, dy.device) if g.ws_dgrad else None
-    A.check(A.lib().sgg_deconv2d_bwd_data(C.byref(g.desc), _p(dy), _p(w_fwd), _p(dx), _p(ws), g.ws_dgrad, _s()), "deconv2d_bwd_data")
+    _conv_launch(None, g, "deconv2d_bwd_data", g.ws_dgrad, dy.device, _p(dy), _p(w_fwd), _p(dx))
     return dx
 
 
 def deconv_wgrad(g: ConvGeom, x, dy, dw, accumulate=False):
     """dw: f32 (R,S,Cout_real,Cin_real) -- the Keras transpose-kernel layout."""
     assert tuple(x.shape) == g.x_shape and tuple(dy.shape) == g.y_shape
-    ws = workspace(g.ws_wgrad, x.device)
-    A.check(A.lib().sgg_deconv2d_bwd_weight(C.byref(g.desc), _p(x), _p(dy), _p(dw), dw.shape[2], dw.shape[3], int(accumulate),
-                                            _p(ws), ws.numel(), _s()), "deconv2d_bwd_weight")
+    _conv_launch(None, g, "deconv2d_bwd_weight", g.ws_wgrad, x.device, _p(x), _p(dy), _p(dw), dw.shape[2], dw.shape[3], int(accumulate))
 
 
 def bias_grad(dy, db, accumulate=False):

@@ -145,6 +145,42 @@ BENCH_WS_WGRAD = {
     "G.c1_7x7_3_64": 46273024, "G.out_7x7_64_3": 28901376, "D.h0_s2_3_64": 9437184, "D.h1_s2_64_128": 75497472, "D.h2_s2_128_256": 60162048,
     "D.h3_s1_256_512": 75497472, "D.h31_s2v_512": 66060288, "D.h32_s2v_512": 66060288, "D.h33_s1v_512": 47185920, "D.h4_s1_512_34": 2211840,
 }
+# The workspaces of the forward and the data gradient, {dtype: (ws_fwd, ws_dgrad)} in bytes as sgg_conv2d_fwd_workspace /
+# sgg_conv2d_bwd_data_workspace (a transposed conv: the sgg_deconv2d_* queries) report them: the split-K slabs, a REFLECT data
+# gradient's fold tensor in front of them, the padded grid of the N7 stem.  Recorded, for every row and dtype and for the bench layers
+# in bf16, from the library before the forward and the data gradient were given one plan; rows and layers not listed need none: (0, 0).
+WS_FWD_DGRAD = {
+    "glds_256x256_fwd_ragged": {"bf16": (0, 2663168), "f32": (0, 2663168)}, "glds_256x256_dgrad": {"bf16": (2663168, 0), "f32": (2663168, 0)},
+    "glds_256x256_dgrad_s2": {"bf16": (2689536, 0), "f32": (2689536, 0)}, "glds_256x128_3stage": {"bf16": (0, 9935040), "f32": (0, 9935040)},
+    "splitk_fwd_dc40": {"bf16": (50400, 0), "f32": (100800, 0)}, "splitk_dgrad_dc40": {"bf16": (0, 50400), "f32": (0, 100800)},
+    "splitk_fwd_dc264": {"bf16": (686400, 711360), "f32": (1372800, 1264640)}, "splitk_dgrad_dc264": {"bf16": (711360, 686400), "f32": (1264640, 1372800)},
+    "pointwise_c512": {"f32": (156672, 0)}, "halo3_min_reflect": {"bf16": (0, 299520)}, "halo3_n3_dtail_reflect": {"bf16": (0, 16850432)},
+    "halo3_n3_dtail_same": {"bf16": (0, 9437184)}, "halo3_dgrad_dtail_reflect": {"bf16": (1179648, 299520)},
+    "halo3_dgrad_dtail_same": {"bf16": (1179648, 0)}, "halo3_pair_n3_reflect": {"bf16": (0, 8916480)},
+    "halo3_normload_c512": {"bf16": (0, 599040)}, "halo3_normload_out_c576": {"bf16": (0, 599040)}, "halo3_out_h5": {"bf16": (0, 301824)},
+    "halo3_out_h2_reflect": {"bf16": (0, 294912)}, "halo3_out_w136": {"bf16": (0, 317952)}, "halo3_out_c72": {"bf16": (0, 337152)},
+    "s2halo_deconv_n3": {"bf16": (0, 6291456)}, "s2halo_tail_tile": {"bf16": (9699328, 0)}, "head7_min": {"bf16": (24576, 47104)},
+    "head7_ragged": {"bf16": (449280, 639744)}, "head7_16x32": {"bf16": (196608, 197632), "f32": (262144, 395264)},
+    "head7_out_7x9": {"bf16": (24192, 49408)}, "stem7_16x32": {"bf16": (0, 13376), "f32": (0, 3423232)}, "stem7_32x64_n2": {"bf16": (0, 85120)},
+    "stem7_17x33": {"bf16": (0, 14352)}, "stem7_min": {"bf16": (0, 6272)}, "narrow5_16x32": {"bf16": (98304, 0), "f32": (196608, 0)},
+    "narrow5_17x32": {"bf16": (104448, 0)}, "narrow5_in16_16x32": {"bf16": (0, 196608), "f32": (0, 393216)},
+    "narrow5_in16_reflect": {"bf16": (0, 759808), "f32": (0, 1519616)}, "narrow5_in16_17x32": {"bf16": (0, 208896)},
+    "w9_min_reflect": {"bf16": (0, 425984)}, "w9_min_same": {"bf16": (0, 131072)}, "w9_two_splits": {"bf16": (0, 566272)},
+    "w9_odd_splits": {"bf16": (0, 19543040)}, "w9_out_odd_h": {"bf16": (0, 1474560)}, "rowfast_valid": {"bf16": (0, 1824768)},
+    "rowfast_7x7": {"bf16": (0, 10196992)}, "rowfast_f32_wo32": {"bf16": (0, 368640), "f32": (0, 655360)}, "wgrad_v2_wo63": {"bf16": (0, 580608)},
+    "wgrad_v2_wo65": {"bf16": (0, 599040)}, "wgrad_128x128_cr3": {"bf16": (0, 15840), "f32": (0, 28512)},
+    # the bench layers
+    "G.res_3x3_256": {"bf16": (0, 14008320)}, "G.c1_7x7_3_64": {"bf16": (0, 17371648)}, "G.out_7x7_64_3": {"bf16": (0, 28675584)},
+    "D.h31_s2v_512": {"bf16": (22855680, 0)}, "D.h32_s2v_512": {"bf16": (17203200, 15237120)}, "D.h33_s1v_512": {"bf16": (13844480, 17203200)},
+    "D.h4_s1_512_34": {"bf16": (1331200, 0)},
+}
+
+
+def ws_fwd_dgrad(name, dtype):
+    """The two workspaces the table records for a row or a bench layer."""
+    return WS_FWD_DGRAD.get(name, {}).get(dtype, (0, 0))
+
+
 # Rows whose dx passes bf16's exact-integer range: 49 taps x 256 output channels of +-1 products have a standard deviation of 75,
 # so no draw keeps 4000 of them within 256.  The row is there for its weight gradient; its dx (at most 2^24: exact in f32 in any
 # order) is compared after the ONE round-to-nearest-even to bf16 of store(), as test_gpu_exact.py compares the bench layers'.

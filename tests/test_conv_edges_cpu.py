@@ -56,6 +56,24 @@ def test_bench_layers_keep_their_weight_gradient_plan():
         assert 2 * g.desc.N * g.desc.Ho * g.desc.Wo <= 2 ** 24
 
 
+def test_rows_and_bench_layers_keep_their_forward_and_data_gradient_workspaces():
+    """sgg_*_fwd_workspace / sgg_*_bwd_data_workspace for every row and dtype and every bench layer, against the recorded values:
+    the split factor of the four split-K rows (_ktiles divides these), the fold tensor in front of the slabs, the N7 stem's grid."""
+    from tests.test_gpu_exact import LAYERS
+    names = {r[0] for r in E.ROWS} | {l[0] for l in LAYERS}
+    assert set(E.WS_FWD_DGRAD) <= names, set(E.WS_FWD_DGRAD) - names
+    for row, dtype in E.CASES:
+        assert set(E.WS_FWD_DGRAD.get(row[0], {})) <= set(row[10]), row[0]
+        g = E.geom(row, dtype)
+        assert (g.ws_fwd, g.ws_dgrad) == E.ws_fwd_dgrad(row[0], dtype), (row[0], dtype)
+    for l in LAYERS:
+        g = E.geom(l + ({},), "bf16")
+        assert (g.ws_fwd, g.ws_dgrad) == E.ws_fwd_dgrad(l[0], "bf16"), l[0]
+    for row, dtype in E.CASES:                           # a split-K route has slabs
+        for route, ws in zip(E.row_routes(row, dtype)[:2], E.ws_fwd_dgrad(row[0], dtype)):
+            assert ws > 0 or not route.endswith("+SPLITK"), (row[0], dtype, route)
+
+
 def test_route_query_rejects_bad_arguments():
     L = A.lib()
     ok = A.ConvDesc(1, 4, 128, 64, 64, 3, 3, 1, 1, 1, 4, 128, A.PAD_REFLECT, A.SGG_BF16)
@@ -87,7 +105,7 @@ def test_bench_layers_keep_their_routes():
 
 
 def _ktiles(g, mode):
-    """K-tile count and split factor of a zero-padded conv's forward (0) / data-gradient (1) GEMM: plan_gemm's arithmetic, and
+    """K-tile count and split factor of a zero-padded conv's forward (0) / data-gradient (1) GEMM: plan_conv's arithmetic, and
     its workspace (one f32 slab of the result per split, nothing else)."""
     d, vec = g.desc, 8 if g.dtype == torch.bfloat16 else 4
     assert not g.is_deconv and d.pad_mode == A.PAD_ZERO and d.stride == 1

@@ -324,7 +324,7 @@ def test_grouped_two_network_calls_bit_exact(sg, row, dtype):
 
 def test_grouped_split_k_call_refuses_the_single_workspace(sg):
     """splitk_fwd_dc40: the grouped call splits K for each network into slabs of its own and needs twice the single call's
-    workspace; with the single call's size run_gemm returns the workspace error before anything is launched."""
+    workspace; with the single call's size run_conv returns the workspace error before anything is launched."""
     from sggan_amd import _abi as A
     row = E.BY_NAME["splitk_fwd_dc40"]
     K, _, _, g, x, _, (wfa, _, ba), (wfb, _, bb) = group2_operands(sg, row, "bf16")
@@ -335,3 +335,27 @@ def test_grouped_split_k_call_refuses_the_single_workspace(sg):
     rc = A.lib().sgg_conv2d_fwd_group2(C.byref(g.desc), p(x), p(wfa), p(ba), p(wfb), p(bb), p(y.t), A.ACT_NONE, 0.0, p(ws), g.ws_fwd, K._s())
     assert rc == A.EWORKSPACE
     y.untouched("splitk_fwd_dc40 group2 y with the single call's workspace")
+
+
+def test_short_workspace_is_refused_before_the_fold_gather(sg):
+    """halo3_n3_dtail_reflect: a REFLECT data gradient on the split-K GEMM, so its workspace has both parts, the pre-folded
+    gather rows of the border pixels and behind them the slabs.  A workspace that holds the first part and not all of the second
+    is refused before anything is launched: the fold gather, the call's first launch, has not written into it."""
+    from sggan_amd import _abi as A
+    row = E.BY_NAME["halo3_n3_dtail_reflect"]
+    pinned(row, "bf16")
+    e = E.expected(row[0])
+    g, _, dy, _, wd, _ = E.operands(sg, row, "bf16", e)
+    d = g.desc
+    assert E.routes(g)[1] == "GLDS_128x64+SPLITK" and (d.N, d.H, d.W, d.C, d.K) == (3, 6, 256, 64, 264) and d.pad_mode == A.PAD_REFLECT
+    border = 2 * d.pad_t * d.W + (d.H - 2 * d.pad_t) * 2 * d.pad_t           # the 2p border rows, then the 2p border columns of the rest
+    fold = -(-(d.N * border * d.R * d.S * d.K * 2) // 256) * 256
+    assert g.ws_dgrad > fold + 256                       # the short workspace below still covers the fold part
+    K = sg.kernels
+    ws = torch.full((g.ws_dgrad,), 0x5A, dtype=torch.uint8, device="cuda")
+    dx = Guarded(g.x_shape, BF)
+    rc = A.lib().sgg_conv2d_bwd_data(C.byref(d), K._p(dy), K._p(wd), None, K._p(dx.t), K._p(ws), g.ws_dgrad - 256, K._s())
+    assert rc == A.EWORKSPACE
+    torch.cuda.synchronize()
+    assert bool((ws == 0x5A).all()), "the workspace was written before it was found too short"
+    dx.untouched("halo3_n3_dtail_reflect dx with a short workspace")
