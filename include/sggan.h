@@ -375,6 +375,29 @@ size_t sgg_gradloss_workspace(int N, int H, int W, int C_real);
 int sgg_gradloss(const void* in, const void* target, const float* weight, int N, int H, int W, int C_real, int Cpad,
                  float lambda, float gscale, float* loss, void* din, int accumulate, int dtype,
                  void* ws, size_t ws_bytes, void* stream);
+/* structural-similarity loss (csrc/ssimloss.hip): sgg_image_quality's SSIM -- 11 x 11 separable Gaussian window,
+ * sigma 1.5, the (H-10) * (W-10) windows wholly inside the image -- on the float values as they are, with its gradient.
+ *   target, x: (N,H,W,Cpad) in dtype (SGG_F32 | SGG_BF16), Cpad == SGG_CPAD, 1 <= C_real <= Cpad, 16-byte aligned; target is a
+ *   constant, x the differentiable operand.  Per image, channel c < C_real and window, with the window means ux (target), uy (x),
+ *   exx, eyy, exy:  vx = exx - ux^2, vy = eyy - uy^2, vxy = exy - ux*uy,
+ *     A1 = 2 ux uy + C1, A2 = 2 vxy + C2, B1 = ux^2 + uy^2 + C1, B2 = vx + vy + C2, S = A1 A2 / (B1 B2),
+ *     C1 = (0.01 * data_range)^2, C2 = (0.03 * data_range)^2;       L = 1 - mean S.
+ *   *loss (+)= weight * L, one rounding to f32 (accumulate bit 0: the old value is added before it).  Identical operands: S == 1
+ *   exactly, so *loss == 0.0f with accumulate 0.
+ *   dx (NULL: loss only, two launches instead of three): (N,H,W,Cpad) in dtype, 16-byte aligned, not x or target;
+ *     dx (+)= gscale * weight * dL/dx, one rounding to dtype, where with Nw the number of (image, channel, window) triples
+ *     alpha = (2ux A2 - 2ux A1)/(B1 B2) - 2 S uy / B1 + 2 S uy / B2,  beta = 2 A1 / (B1 B2),  gamma = -2 S / B2  per window and
+ *     dL/dx[q] = -( (G^T alpha)[q] + target[q] (G^T beta)[q] + x[q] (G^T gamma)[q] ) / Nw,  G^T the adjoint of the valid filter.
+ *     accumulate bit 1 clear: padded channels are written as 0; set: dx = round(dx + g), padded channels keep their bits.
+ *   Moments, S, coefficients, both adjoint passes and the join are double, every sum in a fixed order (ssimloss.hip's header):
+ *   equal operands give equal bits.  No atomics, no allocation, no host sync: capturable.
+ *   ws: sgg_ssim_loss_workspace(N, H, W, C_real) bytes (0: the shape is not supported), 16-byte aligned; need not be initialised.
+ * Refusals, before any launch and in this order: SGG_EINVAL (a NULL target, x, loss or ws; a misaligned buffer; dx aliasing x or
+ * target; N <= 0; C_real outside [1, Cpad]; a dtype other than the two; data_range not finite or <= 0), SGG_EUNSUPPORTED
+ * (Cpad != SGG_CPAD, H < 11, W < 11, H * W > 2^22, a grid past the launch limit), SGG_EWORKSPACE (ws_bytes too small). */
+size_t sgg_ssim_loss_workspace(int N, int H, int W, int C_real);
+int sgg_ssim_loss(const void* target, const void* x, int N, int H, int W, int C_real, int Cpad, float data_range, float weight,
+                  float gscale, float* loss, void* dx, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- optimizer: tf.keras.optimizers.Adam.apply_gradients ---- model.py:199-200,205-207
  * Keras form, over one flat f32 buffer:  m=b1*m+(1-b1)*g; v=b2*v+(1-b2)*g^2;

@@ -7,10 +7,10 @@ from . import _abi  # noqa: F401
 from ._abi import SggError, lib  # noqa: F401
 from .model import default_args, sggan  # noqa: F401
 from .module import Discriminator, Generator, GeneratorUNet, discriminator, generator_resnet, generator_unet  # noqa: F401
-from .ops import conv2d, deconv2d, diff_augment, instance_norm, lrelu, relu, tanh  # noqa: F401
+from .ops import conv2d, deconv2d, diff_augment, instance_norm, lrelu, relu, ssim_loss, tanh  # noqa: F401
 
 __all__ = ["sggan", "default_args", "generator_resnet", "generator_unet", "discriminator", "Generator", "GeneratorUNet", "Discriminator",
-           "conv2d", "deconv2d", "instance_norm", "lrelu", "relu", "tanh", "diff_augment", "lib", "SggError", "LIB_PATH"]
+           "conv2d", "deconv2d", "instance_norm", "lrelu", "relu", "tanh", "diff_augment", "ssim_loss", "lib", "SggError", "LIB_PATH"]
 
 
 def __getattr__(name):

@@ -125,6 +125,8 @@ SIGNATURES = {
     "sgg_seg_edge_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sgg_gradloss_workspace": (_sz, [_i, _i, _i, _i]),
     "sgg_gradloss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "sgg_ssim_loss_workspace": (_sz, [_i, _i, _i, _i]),
+    "sgg_ssim_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "sgg_adam": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _f, _f, _f, _f, _vp]),
     "sgg_adam_iter": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _vp]),
     "sgg_adam_sched": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _f, _vp]),

@@ -636,6 +636,20 @@ def gradloss(x, target, weight, C_real, loss, dx=None, lam=1.0, gscale=1.0, accu
                                  int(bool(accumulate_loss)) | (int(bool(accumulate_grad)) << 1), dt(x), _p(ws), ws.numel(), _s()), "gradloss")
 
 
+def ssim_loss(target, x, C_real, loss, dx=None, weight=1.0, gscale=1.0, data_range=1.0, accumulate_loss=False, accumulate_grad=False):
+    """sgg_ssim_loss (csrc/ssimloss.hip): loss (+)= weight * (1 - mean SSIM(target, x)) over the 11 x 11 Gaussian
+    windows inside the image; optional gradient w.r.t. x.  target, x, dx internal (N,H,W,8); loss a 1-element f32 tensor."""
+    N, H, W, Cp = x.shape
+    assert target.shape == x.shape and target.dtype == x.dtype and (dx is None or (dx.shape == x.shape and dx.dtype == x.dtype))
+    need = int(A.lib().sgg_ssim_loss_workspace(N, H, W, int(C_real)))
+    if not need:
+        A.check(A.EUNSUPPORTED, f"ssim_loss {N}x{H}x{W}x{C_real}")
+    ws = workspace(need, x.device)
+    A.check(A.lib().sgg_ssim_loss(_p(target), _p(x), N, H, W, int(C_real), Cp, float(data_range), float(weight), float(gscale), _p(loss),
+                                  _p(dx), int(bool(accumulate_loss)) | (int(bool(accumulate_grad)) << 1), dt(x), _p(ws), ws.numel(), _s()),
+            "ssim_loss")
+
+
 def adam(theta, g, m, v, t, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0):
     assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
     A.check(A.lib().sgg_adam(_p(theta), _p(g), _p(m), _p(v), theta.numel(), int(t), lr, beta1, beta2, eps, grad_scale, _s()), "adam")

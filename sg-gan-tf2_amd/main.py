@@ -93,6 +93,15 @@ def build_parser():
            "Translation is not offered (D's class mask cannot follow a shift); not with --use_pool")
     a("--diffaug_brightness", dest="diffaug_brightness", type=float, default=argparse.SUPPRESS,
       help="--diffaug color: width of the brightness shift, b = (u - 0.5) * this (default 0.25: images live in [0,1])")
+    a("--ssim_lambda", dest="ssim_lambda", type=float, default=argparse.SUPPRESS,
+      help="add X * (1 - mean SSIM) to the generators' loss beside every L1 reconstruction term (default 0 = off): with --cycle "
+           "on (real_A, cyc_A) and (real_B, cyc_B), otherwise on (label image, fake).  SSIM as --image_scores measures it (11x11 "
+           "Gaussian window, sigma 1.5, the windows inside the image) but on the float images, with its exact gradient, in double "
+           "on the device; works under --graph, with data parallelism, --use_pool and --diffaug; training images must be at "
+           "least 11 pixels high and wide")
+    a("--ssim_data_range", dest="ssim_data_range", type=float, default=argparse.SUPPRESS,
+      help="--ssim_lambda: the span of the image values that fixes SSIM's constants C1 = (0.01 R)^2, C2 = (0.03 R)^2 "
+           "(default 1: the step's images live in [0,1])")
     a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
       help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "
            "class map) pairs and score it against the class map: 'Class Overall Accuracy' ... 'Class Mean IoU' scalars, "

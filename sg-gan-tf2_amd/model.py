@@ -9,6 +9,7 @@ parameter/gradient buffers and (optionally) overlaps the data-parallel gradient 
 from __future__ import annotations
 
 import contextlib
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -34,7 +35,7 @@ def default_args(**over):
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
              crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
-             diffaug_brightness=0.25, swd=False, swd_patches=128)
+             diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -112,6 +113,19 @@ class sggan(object):
             raise NotImplementedError("diffaug with use_pool: the draws are keyed by (discriminator step, global sample index), and a "
                                       "fake handed back by the image pool carries no sample identity (nor the step it was made at); "
                                       "train with one of the two")
+        # ssim_lambda (off by default): beside every L1 reconstruction term the generators' loss gets
+        # ssim_lambda * (1 - mean SSIM(target, reconstruction)) -- K.ssim_loss, one call after each K.l1_loss, into the same loss
+        # cell and the same gradient buffer.  The term never sees a discriminator and keeps no state: graph replay, the image
+        # pool, diffaug and data parallelism (a per-rank mean, averaged like L1) need nothing.  0: no launch, no buffer.
+        self.ssim_lambda = float(g("ssim_lambda", 0.0) or 0.0)
+        self.ssim_data_range = float(g("ssim_data_range", 1.0))
+        if not (math.isfinite(self.ssim_lambda) and self.ssim_lambda >= 0.0):
+            raise ValueError(f"ssim_lambda must be finite and >= 0, got {g('ssim_lambda')!r}")
+        if self.ssim_lambda and not (math.isfinite(self.ssim_data_range) and self.ssim_data_range > 0.0):
+            raise ValueError(f"ssim_data_range must be finite and > 0, got {g('ssim_data_range')!r}")
+        if self.ssim_lambda and min(self.image_height, self.image_width) < 11:
+            raise ValueError(f"--ssim_lambda: SSIM's 11x11 window needs training images of at least 11x11 pixels, "
+                             f"got {self.image_height}x{self.image_width}")
         self.pair_wgrads = bool(g("pair_wgrads", True))   # cycle step: one weight-gradient launch per layer for both applications of a G
         self.batch_d_real_fake = bool(g("batch_d_real_fake", True))   # pool mode: D(real) and D(pooled fakes) as one 2N pass
         self.d_quad = bool(g("d_quad", True))             # reals and fakes through the discriminator(s) as ONE stacked pass (both step flavours)
@@ -383,11 +397,21 @@ class sggan(object):
     def train_step(self, args=None):
         """model.py:169-200.  Reads ``real_A, seg_A`` (N,H,W,3) in [0,1] and ``mask_A`` (N,mh,mw,C);
         writes ``fake_A, gen_loss, disc_loss``; updates G, D and both Adam states."""
+        if self.ssim_lambda and self.real_A is not None and min(self.real_A.shape[1:3]) < 11:     # (not the kernel's status mid-step)
+            raise ValueError(f"--ssim_lambda: SSIM's 11x11 window needs training images of at least 11x11 pixels, "
+                             f"got {self.real_A.shape[1]}x{self.real_A.shape[2]}")
         if self.use_graph:
             return self._graph_step()
         if self.use_pool and self.pool_static:
             self.pool.stage(self.device)
         return self._step_body()
+
+    def _ssim_term(self, target, x, C, gl, dx):
+        """ssim_lambda * (1 - mean SSIM(target, x)) added to ``gl``, its gradient w.r.t. x added to ``dx`` (which the L1 term
+        in front of it has written).  Off: nothing is launched."""
+        if self.ssim_lambda:
+            K.ssim_loss(target, x, C, gl, dx, weight=self.ssim_lambda, data_range=self.ssim_data_range,
+                        accumulate_loss=True, accumulate_grad=True)
 
     def _step_body(self):
         if self.cycle:
@@ -436,6 +460,7 @@ class sggan(object):
         dfake_l1 = torch.empty_like(fake)
         K.bce_logits(da_fake, 1.0, gl, d_fake_g)                            # :153 gan_loss
         K.l1_loss(seg, fake, self.output_c_dim, gl, dfake_l1, weight=self.LAMBDA, accumulate=True)   # :155-156
+        self._ssim_term(seg, fake, self.output_c_dim, gl, dfake_l1)
         K.bce_logits(da_real, 1.0, dl, d_real_d)                            # :162
         K.bce_logits(da_fake, 0.0, dl, d_fake_d, accumulate_loss=True)      # :163-164 (adds to disc_loss)
 
@@ -575,7 +600,9 @@ class sggan(object):
         crit(DB_fake, 1.0, gl, gB_g, accumulate_loss=True)
         d_cycA, d_cycB = e(cyc_A), e(cyc_B)
         K.l1_loss(rA, cyc_A, C, gl, d_cycA, weight=self.L1_lambda, accumulate=True)
+        self._ssim_term(rA, cyc_A, C, gl, d_cycA)
         K.l1_loss(rB, cyc_B, C, gl, d_cycB, weight=self.L1_lambda, accumulate=True)
+        self._ssim_term(rB, cyc_B, C, gl, d_cycB)
         d_fA, d_fB = e(fake_A), e(fake_B)                    # gradient-sensitive terms write, the rest accumulate
         K.gradloss(fake_A, rB, wB, C, gl, d_fA, lam=self.Lg_lambda, accumulate_loss=True)
         K.gradloss(fake_B, rA, wA, C, gl, d_fB, lam=self.Lg_lambda, accumulate_loss=True)
@@ -705,7 +732,9 @@ class sggan(object):
         crit(Df[lo], 1.0, gl, g_g[lo], accumulate_loss=True)  # D_B(fake_B)
         d_cyc = e(c2)
         K.l1_loss(rA, c2[lo], C, gl, d_cyc[lo], weight=self.L1_lambda, accumulate=True)
+        self._ssim_term(rA, c2[lo], C, gl, d_cyc[lo])
         K.l1_loss(rB, c2[hi], C, gl, d_cyc[hi], weight=self.L1_lambda, accumulate=True)
+        self._ssim_term(rB, c2[hi], C, gl, d_cyc[hi])
         d_f = e(f1)                                           # gradient-sensitive terms write, the rest accumulate
         K.gradloss(f1[hi], rB, wB, C, gl, d_f[hi], lam=self.Lg_lambda, accumulate_loss=True)
         K.gradloss(f1[lo], rA, wA, C, gl, d_f[lo], lam=self.Lg_lambda, accumulate_loss=True)

@@ -158,6 +158,26 @@ class _DiffAugmentFn(torch.autograd.Function):
         return K.diffaug_bwd(dy, par, ctx.Cr)[..., :ctx.Cr], None
 
 
+class _SsimLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target, data_range):
+        Cr = x.shape[-1]
+        Cp = K.cpad(Cr)
+        xp = _padc(x.detach().to(torch.float32), Cp).contiguous()
+        tp = _padc(target.detach().to(torch.float32), Cp).contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(xp) if ctx.needs_input_grad[0] else None
+        K.ssim_loss(tp, xp, Cr, loss, dx, data_range=data_range)     # the gradient is the forward's by-product: kept for backward
+        ctx.Cr = Cr
+        ctx.save_for_backward(dx)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dl):
+        (dx,) = ctx.saved_tensors
+        return dx[..., :ctx.Cr] * dl, None, None
+
+
 _ACTS = {None: A.ACT_NONE, "none": A.ACT_NONE, "relu": A.ACT_RELU, "lrelu": A.ACT_LRELU, "tanh": A.ACT_TANH}
 
 
@@ -196,3 +216,12 @@ def diff_augment(x, params):
     with C <= 8, params (N,8) f32 rows [b, s, c, y0, x0, ch, cw, 0] (kernels.diffaug_draw fills them on the device).  The
     transform is affine in x for fixed rows; the gradient w.r.t. x is its adjoint, params get none."""
     return _DiffAugmentFn.apply(x, params)
+
+
+def ssim_loss(x, target, data_range=1.0):
+    """1 - mean SSIM(target, x) as a scalar (Wang et al.'s index, 11 x 11 Gaussian window of sigma 1.5, the windows
+    wholly inside the image): x, target (N,H,W,C) float32 with C <= 8 and H, W >= 11, values spanning ``data_range``.  target is
+    a constant; the gradient w.r.t. x is the kernel's closed form (sgg_ssim_loss)."""
+    if x.shape != target.shape or x.dim() != 4 or x.shape[-1] > A.CPAD:
+        raise ValueError(f"ssim_loss: x {tuple(x.shape)} and target {tuple(target.shape)} must be equal (N,H,W,C) with C <= {A.CPAD}")
+    return _SsimLossFn.apply(x, target, float(data_range))
