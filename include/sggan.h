@@ -456,6 +456,49 @@ int sgg_adam_ema(float* theta, const float* g, float* m, float* v, float* ema, i
 /* Exchange the contents of two n-element buffers (16-byte aligned, n > 0) bit for bit in one pass. */
 int sgg_swap_f32(float* a, float* b, int64_t n, void* stream);
 
+/* ---- spectral norm (no counterpart in the reference): Miyato et al. 2018 for every conv layer of a network, one
+ * call per network over a DEVICE table of items (as sgg_pack_conv_weights_batch).  A layer's kernel is the matrix M (rows x K,
+ * row-major f32: the HWIO kernel as it is stored, rows = R*S*C_real, K = K_real), u a persistent unit vector of length K.
+ *   sgg_spectral_sigma, per item, every sum in double and in an order the shapes alone fix (no atomics; the same bits each run):
+ *       t = M u            v = t / sqrt(max(|t|^2, 1e-12))
+ *       s = Mt v           u' = s / sqrt(max(|s|^2, 1e-12))
+ *     advance != 0: u <- u' in place, sigma = max(vt M u', 1e-12) (= |s|);  advance == 0: u keeps its bits and
+ *     sigma = max(vt M u, 1e-12) (= |t|): the value a freshly built or loaded network starts from.  v[rows], sigma[0] and
+ *     inv_sigma[0] = (float)(1 / sigma) (the division in double) are written as f32, each rounded once.  Three launches (two
+ *     with advance == 0): M is read once, by blocks that take SGG_SPECTRAL_BAND rows each and leave t and their share of Mt t and
+ *     |t|^2 in ws; a block per item and 64 columns folds the shares (v, s); one block per item finishes u and sigma.  The launch
+ *     shapes depend on (n_items, max_rows, max_K, advance) only: capturable.
+ *   sgg_spectral_grad, per item, with dWbar = g as it comes in (the gradient with respect to Wbar = W * inv_sigma):
+ *       lambda = (sum dWbar o W) * inv_sigma                  (double, fixed order)
+ *       g <- (float)((dWbar - lambda * (v ut)) * inv_sigma)   (in double, one rounding), in place.
+ *     u, v and inv_sigma are read as sgg_spectral_sigma left them: they are constants of the differentiation.
+ *   max_rows / max_K: upper bounds of the items' rows / K (they size grid and workspace; an item above them, or with a NULL
+ *   w / u / v / sigma / inv_sigma -- for sgg_spectral_grad also g -- is left untouched); K <= SGG_SPECTRAL_MAX_K.  w and g rows are read
+ *   with 16-byte loads where K % 4 == 0 and the base is 16-byte aligned, with 4-byte loads otherwise: any K, any rows >= 1.
+ *   ws: 8-byte aligned, the workspace query's bytes.  Status, before anything is launched: SGG_EINVAL -- items_dev NULL,
+ *   n_items <= 0, max_rows <= 0, max_K outside 1..SGG_SPECTRAL_MAX_K; SGG_EWORKSPACE -- ws NULL, misaligned or short. */
+#define SGG_SPECTRAL_BAND 32
+#define SGG_SPECTRAL_MAX_K 1024
+typedef struct sgg_spectral_item {
+    const float* w;      /* M */
+    float* g;            /* dWbar in, dW out (sgg_spectral_grad; sgg_spectral_sigma ignores it) */
+    float* u;            /* K */
+    float* v;            /* rows */
+    float* sigma;        /* 1 */
+    float* inv_sigma;    /* 1 */
+    int32_t rows, K;
+} sgg_spectral_item;
+size_t sgg_spectral_sigma_workspace(int n_items, int max_rows, int max_K);
+int sgg_spectral_sigma(const sgg_spectral_item* items_dev, int n_items, int max_rows, int max_K, int advance,
+                       void* ws, size_t ws_bytes, void* stream);
+size_t sgg_spectral_grad_workspace(int n_items, int max_rows);
+int sgg_spectral_grad(const sgg_spectral_item* items_dev, int n_items, int max_rows, int max_K,
+                      void* ws, size_t ws_bytes, void* stream);
+/* sgg_pack_conv_weights_batch with item i's elements multiplied by scale_dev[i] (a DEVICE float per item, read when the launch
+ * runs) in f32 before the single rounding to `dtype`: the same kernel body.  scale_dev NULL returns SGG_EINVAL. */
+int sgg_pack_conv_weights_batch_scaled(const sgg_pack_item* items_dev, const float* scale_dev, int n_items, int64_t max_elems,
+                                       int dtype, void* stream);
+
 /* ---- data side of the step ----
  * segment_class.py:60-70,95-97: colour -> class index, bit exact.  rgb: uint8 [n_pixels][channels>=3]. */
 int sgg_seg_class_map(const uint8_t* rgb, int channels, int64_t n_pixels, uint8_t* out, void* stream);

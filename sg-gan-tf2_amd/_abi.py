@@ -44,6 +44,13 @@ class PackItem(C.Structure):
                 ("taps", "C", "K", "Cpad", "Kpad", "reserved")]
 
 
+class SpectralItem(C.Structure):
+    """struct sgg_spectral_item (include/sggan.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w", "g", "u", "v", "sigma", "inv_sigma")] + [("rows", C.c_int32), ("K", C.c_int32)]
+
+
+SPECTRAL_BAND, SPECTRAL_MAX_K = 32, 1024           # SGG_SPECTRAL_BAND, SGG_SPECTRAL_MAX_K
+
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _dp = C.POINTER(ConvDesc)
 
@@ -58,6 +65,7 @@ SIGNATURES = {
     "sgg_stream_capture_nodes": (_i, [_vp, C.POINTER(C.c_int)]),
     "sgg_pack_conv_weights": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sgg_pack_conv_weights_batch": (_i, [_vp, _i, _i64, _i, _vp]),
+    "sgg_pack_conv_weights_batch_scaled": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
     "sgg_conv2d_fwd_workspace": (_sz, [_dp]),
     "sgg_conv2d_fwd": (_i, [_dp, _vp, _vp, _vp, _vp, _i, _f, _vp, _sz, _vp]),
     "sgg_conv2d_fwd_stats_chunks": (_sz, [_dp]),
@@ -135,6 +143,10 @@ SIGNATURES = {
     "sgg_adam_guard": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "sgg_adam_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _f, _i, _vp, _vp, _sz, _vp]),
     "sgg_swap_f32": (_i, [_vp, _vp, _i64, _vp]),
+    "sgg_spectral_sigma_workspace": (_sz, [_i, _i, _i]),
+    "sgg_spectral_sigma": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "sgg_spectral_grad_workspace": (_sz, [_i, _i]),
+    "sgg_spectral_grad": (_i, [_vp, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_seg_class_map": (_i, [_vp, _i, _i64, _vp, _vp]),
     "sgg_seg_class_table": (_i, [_vp, _vp, _i]),
     "sgg_onehot_resample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1714,9 +1714,10 @@ __global__ void pack_weights_kernel(const float* w, int taps, int C, int K, int 
 }
 
 // every conv layer of a network in ONE launch (blockIdx.y = layer): after each optimizer step all packed weights are stale,
-// and 16 separate 8-us launches per network were pure launch latency
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weights_batch_kernel(const sgg_pack_item* items) {
+// and 16 separate 8-us launches per network were pure launch latency.  SCALED: every element of item i times scale[i] in f32 before
+// the one rounding to T (sgg_pack_conv_weights_batch_scaled: a spectrally normalised network packs W / sigma)
+template <typename T, bool SCALED>
+__global__ __launch_bounds__(256) void pack_weights_batch_kernel(const sgg_pack_item* items, const float* scale) {
     // (tap, 64 c, 64 k) tiles: w[tap][c][k] is read along k, w_dgrad[c][tap][k] written along k, and w_fwd[k][tap][c] -- the
     // transposed layout -- written along c out of an LDS tile.  (One thread per element wrote w_fwd as 2-byte scatters, one
     // cache line per lane: 83 us for a generator's 11.4 M parameters, 1.1 TB/s.)
@@ -1726,6 +1727,8 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const sgg_pack_
     const float* w = it.w;
     T* wf = (T*)it.w_fwd;
     T* wd = (T*)it.w_dgrad;
+    float sc = 1.f;
+    if constexpr (SCALED) sc = scale[blockIdx.y];
     const int tc = (Cpad + 63) / 64, tk = (Kpad + 63) / 64;
     const int ntiles = taps * tc * tk;
     const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
@@ -1734,7 +1737,8 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const sgg_pack_
         const int k = kt * 64 + lx;
         for (int cy = ly; cy < 64; cy += 4) {
             const int c = ct * 64 + cy;
-            const float v = (c < C && k < K) ? w[((size_t)tap * C + c) * K + k] : 0.f;
+            float v = (c < C && k < K) ? w[((size_t)tap * C + c) * K + k] : 0.f;
+            if constexpr (SCALED) v = v * sc;
             tile[cy][lx] = v;
             if (wd && c < Cpad && k < Kpad) wd[((size_t)c * taps + tap) * Kpad + k] = (T)v;
         }
@@ -2154,6 +2158,18 @@ static int run_conv(const sgg_conv_desc* d, int dir, const ConvCall& c) {
     return launch_splitk_reduce(d, a, p, s);             // out = act(sum of the slabs + bias) + addend, in a fixed order
 }
 
+// every conv layer of a network in one launch, plain or scaled per item
+template <bool SCALED>
+static int launch_pack_batch(const sgg_pack_item* items_dev, const float* scale_dev, int n_items, int64_t max_elems, int dtype, void* stream) {
+    if (!items_dev || n_items <= 0 || max_elems <= 0 || (SCALED && !scale_dev)) return SGG_EINVAL;
+    int blocks = (int)((max_elems + 4095) / 4096); if (blocks > 1024) blocks = 1024;     // 64 x 64 tiles, grid-strided
+    dim3 grid((unsigned)blocks, (unsigned)n_items);
+    if (dtype == SGG_BF16) hipLaunchKernelGGL((pack_weights_batch_kernel<bf16, SCALED>), grid, dim3(256), 0, (hipStream_t)stream, items_dev, scale_dev);
+    else if (dtype == SGG_F32) hipLaunchKernelGGL((pack_weights_batch_kernel<float, SCALED>), grid, dim3(256), 0, (hipStream_t)stream, items_dev, scale_dev);
+    else return SGG_EINVAL;
+    return sgg_check_launch();
+}
+
 extern "C" {
 
 #ifdef SGG_LAB
@@ -2180,13 +2196,11 @@ int sgg_pack_conv_weights(const float* w, int R, int S, int C, int K, int Cpad, 
 }
 
 int sgg_pack_conv_weights_batch(const sgg_pack_item* items_dev, int n_items, int64_t max_elems, int dtype, void* stream) {
-    if (!items_dev || n_items <= 0 || max_elems <= 0) return SGG_EINVAL;
-    int blocks = (int)((max_elems + 4095) / 4096); if (blocks > 1024) blocks = 1024;     // 64 x 64 tiles, grid-strided
-    dim3 grid((unsigned)blocks, (unsigned)n_items);
-    if (dtype == SGG_BF16) hipLaunchKernelGGL(pack_weights_batch_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, items_dev);
-    else if (dtype == SGG_F32) hipLaunchKernelGGL(pack_weights_batch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, items_dev);
-    else return SGG_EINVAL;
-    return sgg_check_launch();
+    return launch_pack_batch<false>(items_dev, nullptr, n_items, max_elems, dtype, stream);
+}
+
+int sgg_pack_conv_weights_batch_scaled(const sgg_pack_item* items_dev, const float* scale_dev, int n_items, int64_t max_elems, int dtype, void* stream) {
+    return launch_pack_batch<true>(items_dev, scale_dev, n_items, max_elems, dtype, stream);
 }
 
 // ---- the queries: fields of the plan (0 / SGG_EINVAL for a descriptor the library rejects)

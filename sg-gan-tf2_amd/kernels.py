@@ -184,8 +184,13 @@ def pack_weights_batch(entries, dtype, device):
     return raw, len(entries), max_elems, bufs
 
 
-def repack_batch(table, n, max_elems, dtype):
-    A.check(A.lib().sgg_pack_conv_weights_batch(_p(table), n, max_elems, dt(dtype), _s()), "pack_conv_weights_batch")
+def repack_batch(table, n, max_elems, dtype, scale=None):
+    """scale: a device f32 vector, one factor per item, multiplied in f32 before the rounding (``sgg_pack_conv_weights_batch_scaled``)."""
+    if scale is None:
+        A.check(A.lib().sgg_pack_conv_weights_batch(_p(table), n, max_elems, dt(dtype), _s()), "pack_conv_weights_batch")
+    else:
+        assert scale.dtype == torch.float32 and scale.numel() == n
+        A.check(A.lib().sgg_pack_conv_weights_batch_scaled(_p(table), _p(scale), n, max_elems, dt(dtype), _s()), "pack_conv_weights_batch_scaled")
 
 
 # ----------------------------------------------------------------------------- conv / deconv
@@ -774,6 +779,49 @@ def swap_(a, b):
     """Exchange the contents of two float32 buffers of equal length bit for bit, in place, in one pass (``sgg_swap_f32``)."""
     assert a.dtype == b.dtype == torch.float32 and a.numel() == b.numel()
     A.check(A.lib().sgg_swap_f32(_p(a), _p(b), a.numel(), _s()), "swap_")
+
+
+# ----------------------------------------------------------------------------- spectral norm
+class SpectralTable:
+    """The device item table of ``sgg_spectral_sigma`` / ``sgg_spectral_grad`` for a list of layers, with the workspaces of both
+    calls.  entries: [(w, g, u, v, sigma, inv_sigma)] -- ``w`` (and ``g``, or None) the layer's f32 kernel (gradient) viewed as
+    (rows, K), contiguous; ``u`` (K,), ``v`` (rows,), ``sigma`` and ``inv_sigma`` one-element f32 views.  Everything is device
+    memory the caller keeps alive; the table holds the addresses, so the launches are the same every step (capturable)."""
+
+    def __init__(self, entries, device):
+        items = (A.SpectralItem * len(entries))()
+        self.max_rows = self.max_K = 0
+        for it, (w, g, u, v, sigma, inv_sigma) in zip(items, entries):
+            rows, Kc = w.shape
+            for t in (w, g, u, v, sigma, inv_sigma):
+                assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32)
+            assert g is None or tuple(g.shape) == (rows, Kc)
+            assert u.numel() == Kc and v.numel() == rows and sigma.numel() == 1 and inv_sigma.numel() == 1
+            if Kc > A.SPECTRAL_MAX_K:
+                raise A.SggError(f"spectral norm: {Kc} output channels, the kernels take at most {A.SPECTRAL_MAX_K}")
+            it.w, it.g, it.u, it.v = w.data_ptr(), (g.data_ptr() if g is not None else None), u.data_ptr(), v.data_ptr()
+            it.sigma, it.inv_sigma, it.rows, it.K = sigma.data_ptr(), inv_sigma.data_ptr(), rows, Kc
+            self.max_rows, self.max_K = max(self.max_rows, rows), max(self.max_K, Kc)
+        self.n = len(entries)
+        self.has_grad = all(e[1] is not None for e in entries)
+        self.table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(device)
+        L = A.lib()
+        self.ws_sigma = torch.empty(int(L.sgg_spectral_sigma_workspace(self.n, self.max_rows, self.max_K)), dtype=torch.uint8, device=device)
+        self.ws_grad = torch.empty(int(L.sgg_spectral_grad_workspace(self.n, self.max_rows)), dtype=torch.uint8, device=device)
+        self.keep = entries
+
+
+def spectral_sigma(tab: SpectralTable, advance=True):
+    """One power iteration per item (``sgg_spectral_sigma``): v, sigma and 1 / sigma are written, u is replaced when ``advance``."""
+    A.check(A.lib().sgg_spectral_sigma(_p(tab.table), tab.n, tab.max_rows, tab.max_K, 1 if advance else 0, _p(tab.ws_sigma),
+                                       tab.ws_sigma.numel(), _s()), "spectral_sigma")
+
+
+def spectral_grad(tab: SpectralTable):
+    """dWbar -> dW in place on every item's gradient slice (``sgg_spectral_grad``)."""
+    assert tab.has_grad
+    A.check(A.lib().sgg_spectral_grad(_p(tab.table), tab.n, tab.max_rows, tab.max_K, _p(tab.ws_grad), tab.ws_grad.numel(), _s()),
+            "spectral_grad")
 
 
 # ----------------------------------------------------------------------------- data side

@@ -102,6 +102,13 @@ def build_parser():
     a("--ssim_data_range", dest="ssim_data_range", type=float, default=argparse.SUPPRESS,
       help="--ssim_lambda: the span of the image values that fixes SSIM's constants C1 = (0.01 R)^2, C2 = (0.03 R)^2 "
            "(default 1: the step's images live in [0,1])")
+    a("--d_norm", dest="d_norm", choices=("instance", "spectral"), default=argparse.SUPPRESS,
+      help="normalisation of the discriminators (default instance, the reference's network).  spectral (Miyato et al. 2018): no "
+           "discriminator layer has an instance norm -- it would cancel any scale of the kernel in front of it -- and every "
+           "discriminator conv runs on W / sigma(W), sigma kept by one power iteration per discriminator per step on the device; "
+           "the per-layer vectors are saved with the checkpoint, so it works under --graph, with data parallelism (nothing to "
+           "exchange), --use_pool, the guard flags and after --continue_train; with --diffaug the draws stay keyed by the "
+           "discriminator's step counter, unchanged.  A checkpoint loads only into a model of the same --d_norm")
     a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
       help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "
            "class map) pairs and score it against the class map: 'Class Overall Accuracy' ... 'Class Mean IoU' scalars, "

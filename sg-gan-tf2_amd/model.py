@@ -18,7 +18,7 @@ import torch
 from . import _abi as A
 from . import kernels as K
 from .graph import StepProgram
-from .module import Adam, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet, GeneratorUNetPair
+from .module import Adam, check_d_norm, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet, GeneratorUNetPair
 from .utils import ImagePool, StaticImagePool
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32,
@@ -35,9 +35,15 @@ def default_args(**over):
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
              crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
-             diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0)
+             diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0, d_norm="instance")
     a.update(over)
     return SimpleNamespace(**a)
+
+
+def _spectral_state(net):
+    """The network's power-iteration vectors, or None for a network without spectral norm (any object with a ``P``)."""
+    f = getattr(net, "spectral_state", None)
+    return None if f is None else f()
 
 
 class sggan(object):
@@ -60,6 +66,13 @@ class sggan(object):
         # model.py:55-62: --use_resnet picks generator_resnet(), otherwise generator_unet() (the reference's flag-less default)
         self.arch = "resnet" if g("use_resnet", True) else "unet"
         self.cycle = bool(g("cycle", False))
+        # d_norm ("instance" is the reference's network): "spectral" builds the discriminators without instance
+        # norms and runs every one of their convs on W / sigma(W) -- one power iteration per discriminator per training step
+        # (Discriminator.spectral_step, first thing in the step bodies), the gradient transform directly before their Adam
+        # launch (_apply_gradients).  The whole state is one small vector per layer on the device, advanced by the step's own
+        # launches: graph replay and checkpoints carry it, and data-parallel ranks, which hold identical W and u, compute
+        # identical sigma without exchanging anything.  The generators never see it.
+        self.d_norm = check_d_norm(g("d_norm", "instance"))
         self.dtype = _DTYPES[g("dtype", "bf16")]
         self.device = torch.device(g("device", "cuda"))
         if self.device.type != "cuda":       # refused here, before any network (and so any buffer) is built
@@ -67,7 +80,7 @@ class sggan(object):
                                       "no host implementation, it runs on the MI355X HIP path only (device must be a cuda/hip device)")
         seed = g("seed", 19)
         self.discriminator = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
-                                           dtype=self.dtype, device=self.device, seed=seed + 1)          # model.py:54
+                                           dtype=self.dtype, device=self.device, seed=seed + 1, norm=self.d_norm)   # model.py:54
         def make_generator(in_c, out_c, seed):                  # :56 generator_resnet / :58 generator_unet
             kw = dict(gf_dim=g("ngf", 64), in_c=in_c, out_c=out_c, dtype=self.dtype, device=self.device, seed=seed)
             return Generator(n_blocks=g("n_blocks", 9), **kw) if self.arch == "resnet" else GeneratorUNet(**kw)
@@ -81,7 +94,7 @@ class sggan(object):
         if self.cycle:
             self.generator_BA = make_generator(self.output_c_dim, self.input_c_dim, seed + 2)
             self.discriminator_B = Discriminator(df_dim=g("ndf", 64), in_c=self.output_c_dim, segment_class=self.segment_class,
-                                                 dtype=self.dtype, device=self.device, seed=seed + 3)
+                                                 dtype=self.dtype, device=self.device, seed=seed + 3, norm=self.d_norm)
             self.real_B = self.seg_B = self.mask_B = self.fake_B = None
         # step I/O attributes (model.py:250-256 sets the inputs; :260 reads the losses)
         self.real_A = self.seg_A = self.mask_A = self.fake_A = None
@@ -163,7 +176,7 @@ class sggan(object):
         if self.ema_decay is not None:
             for net in self._ema_nets():
                 net.P.enable_ema()
-        self._ema_notice = False
+        self._ema_notice = self._sn_notice = False
         # cycle step: run the two generators (and the two discriminators) in lockstep on stacked batches (module._PairUnit);
         # bit-identical to the one-network-at-a-time sequencing, which stays for the image pool and for mixed mode.  paired=None
         # picks the default: on for the ResNet (the step bench.py times); off for the U-Net, whose step is bound by
@@ -326,6 +339,7 @@ class sggan(object):
         keep = [(n.P.flat.clone(), n.P.m.clone(), n.P.v.clone(), n.P.iterations.clone()) for n in nets]
         guard_keep = [None if n.P._guard is None else n.P._guard.clone() for n in nets]     # (the warm-up step counts as none)
         ema_keep = [None if n.P.ema is None else (n.P.ema.clone(), n.P._ema_state.clone()) for n in nets]
+        sn_keep = [None if n.spectral_state() is None else n.spectral_state().clone() for n in nets]    # (the warm-up step's power iteration too)
         loss_keep = self._loss.clone()
         hook, K.PROFILE = K.PROFILE, None          # timing hooks (bench.py) record events: not while recording
         try:
@@ -347,6 +361,9 @@ class sggan(object):
             for n, kept in zip(nets, ema_keep):
                 if kept is not None:
                     n.P.ema.copy_(kept[0]); n.P._ema_state.copy_(kept[1])
+            for n, u in zip(nets, sn_keep):
+                if u is not None:
+                    n.spectral_state().copy_(u)
             self._loss.copy_(loss_keep)
             prog = StepProgram(self.device)
             K._RECORDER = prog
@@ -417,6 +434,7 @@ class sggan(object):
         if self.cycle:
             return self._train_step_cycle()
         G, D = self.generator, self.discriminator
+        D.spectral_step()           # (d_norm="spectral": this step's sigma, before D's first use; else nothing)
         # :186-188.  d_quad: D sees [seg; fake] as ONE stacked pass (half the launches; its tail layers are launch-latency bound);
         # the generator's loss backpropagates through the fake slice of the same tape.  Per image the same arithmetic.  The
         # stacked input is one persistent buffer: seg is converted into its first half, G writes the fakes into the second.
@@ -491,11 +509,17 @@ class sggan(object):
         """(optimizer, its network's all-reduce handle or None) in update order: each Adam launch waits for that network's
         gradient exchange only, so the exchanges still in flight run under the updates in front of them.  A guarded update
         (clip_grad_norm / skip_nonfinite) measures the buffer AFTER the exchange: every rank sees the same summed bits and
-        1 / world enters the norm as grad_scale, so all ranks take the same decision without another collective."""
+        1 / world enters the norm as grad_scale, so all ranks take the same decision without another collective.  A spectrally
+        normalised discriminator's buffer holds gradients with respect to W / sigma until here: the transform to gradients with
+        respect to W is linear, so it runs once on the exchanged buffer (every rank holds the same W, u, v and sigma), after any
+        deferred weight gradient and directly before the update -- the guard measures the transformed gradient."""
         scale = 1.0 / self._world
         for opt, h in updates:
             if h is not None:
                 h.wait()
+            if _spectral_state(opt.net) is not None:
+                opt.net.flush_wgrads()
+                opt.net.spectral_grad()
             opt.apply_gradients(grad_scale=scale)
 
     def set_lr_schedule(self, steps_per_epoch, epoch_step, epochs):
@@ -574,6 +598,7 @@ class sggan(object):
         mA, mB = self._convert_input("mask_A", self.mask_A), self._convert_input("mask_B", self.mask_B)
         for net in (Gab, Gba, Da, Db):
             net.P.zero_grad()
+        Da.spectral_step(); Db.spectral_step()      # (d_norm="spectral": this step's sigma, before their first use)
         C = self.output_c_dim
 
         fake_B, t1 = Gab.forward(rA)
@@ -710,6 +735,7 @@ class sggan(object):
             m_ab = torch.cat([mA, mB])
         for net in (Gab, Gba, Da, Db):
             net.P.zero_grad()
+        Da.spectral_step(); Db.spectral_step()      # (d_norm="spectral": this step's sigma, before their first use)
         C = self.output_c_dim
         f1, t1 = Gp1.forward(x1, out=dq[n:3 * n] if quad else None)   # [fake_B; fake_A]
         c2, t2 = Gp2.forward(f1)                              # [cyc_A; cyc_B]
@@ -806,6 +832,8 @@ class sggan(object):
                 sd[key]["guard"] = [int(c) for c in P._guard[2:4].cpu().tolist()]
             if P.ema is not None:               # the moving average of the generator's parameters (ema_decay)
                 sd[key]["ema"] = P.ema.cpu()
+            if _spectral_state(net) is not None:    # a spectrally normalised discriminator: its kind and its power-iteration vectors
+                sd[key]["d_norm"], sd[key]["u"] = "spectral", _spectral_state(net).cpu()
         sd["G"]["arch"] = self.arch             # generator architecture tag (a checkpoint without one is a ResNet checkpoint)
         return sd
 
@@ -815,10 +843,22 @@ class sggan(object):
         if arch != self.arch:
             raise ValueError(f"checkpoint holds a {arch} generator, this model is built with a {self.arch} generator "
                              f"(--generator {self.arch}); load it into a model built with --generator {arch}")
+        for key in names[1::2]:                 # (before anything is copied)
+            kind = sd[key].get("d_norm", "instance")
+            mine = getattr(self, "d_norm", "instance")
+            if kind != mine:
+                raise ValueError(f"checkpoint holds {kind}-norm discriminators, this model is built with {mine}-norm "
+                                 f"discriminators (--d_norm {mine}); load it into a model built with --d_norm {kind}")
         for key, net in zip(names, self.networks()):
             P = net.P
             P.flat.copy_(sd[key]["flat"]); P.m.copy_(sd[key]["m"]); P.v.copy_(sd[key]["v"])
             P.step_count = int(sd[key]["t"]); P.version += 1
+            if _spectral_state(net) is not None:
+                u = sd[key].get("u")
+                if u is None and not self._sn_notice:
+                    self._sn_notice = True
+                    print(" [*] spectral-norm checkpoint without power-iteration vectors: they start from the seeded ones")
+                net.set_spectral_state(u)
             counters = sd[key].get("guard")     # (absent from a checkpoint of a run without the options)
             if counters is not None:
                 P.guard_buffers()[0][2:4].copy_(torch.tensor([float(c) for c in counters], dtype=torch.float64))

@@ -15,6 +15,7 @@ shape-agnostic, geometry is resolved per call.
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -42,6 +43,7 @@ class ParamStore:
         z = lambda: torch.zeros(self.numel, dtype=torch.float32, device=self.device)
         self.flat, self.grad, self.m, self.v = z(), z(), z(), z()
         self.version = 0            # bumped whenever parameter values change (re-pack trigger)
+        self.loaded = 0             # bumped whenever the values are replaced wholesale (init, load): derived state starts over
         # Adam's step number lives on the device (Keras: the `optimizer.iterations` variable), so the update launch
         # carries no host state and can be replayed from a captured HIP graph
         self._adam_state = torch.zeros(2, dtype=torch.int64, device=self.device)    # [iterations, scratch] (sgg_adam_iter)
@@ -95,6 +97,7 @@ class ParamStore:
                 host[off:off + shape[0]] = 1.0
         self.flat.copy_(host)
         self.version += 1
+        self.loaded += 1
 
     def load(self, params: dict):
         """name -> array in the reference layouts (HWIO kernels, (kh,kw,out,in) transpose kernels)."""
@@ -106,6 +109,7 @@ class ParamStore:
             host[off:off + a.numel()] = a
         self.flat.copy_(host)
         self.version += 1
+        self.loaded += 1
 
     def export(self, buf=None) -> dict:
         src = (self.flat if buf is None else buf).detach().cpu()
@@ -238,16 +242,28 @@ def unet_param_specs(gf_dim=64, in_c=3, out_c=3):
     return L
 
 
-def discriminator_param_specs(df_dim=64, in_c=3, segment_class=34):
-    """Creation order of discriminator (module.py:272-318)."""
+D_NORMS = ("instance", "spectral")
+
+
+def check_d_norm(norm):
+    """The discriminators' normalisation: 'instance' (the reference's) or 'spectral' (DESIGN.md 24)."""
+    if norm not in D_NORMS:
+        raise ValueError(f"d_norm must be one of {', '.join(D_NORMS)}, got {norm!r}")
+    return norm
+
+
+def discriminator_param_specs(df_dim=64, in_c=3, segment_class=34, norm="instance"):
+    """Creation order of discriminator (module.py:272-318).  norm="spectral": no layer has an instance norm, so every layer is
+    kernel and bias only."""
+    inorm = check_d_norm(norm) == "instance"
     L = []
     L += _layer_specs("h0", (3, 3, in_c, df_dim), df_dim, norm=False)
-    L += _layer_specs("h1", (3, 3, df_dim, df_dim * 2), df_dim * 2)
-    L += _layer_specs("h2", (3, 3, df_dim * 2, df_dim * 4), df_dim * 4)
-    L += _layer_specs("h3", (3, 3, df_dim * 4, df_dim * 8), df_dim * 8)
-    L += _layer_specs("h31", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8)
-    L += _layer_specs("h32", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8)
-    L += _layer_specs("h33", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8)
+    L += _layer_specs("h1", (3, 3, df_dim, df_dim * 2), df_dim * 2, norm=inorm)
+    L += _layer_specs("h2", (3, 3, df_dim * 2, df_dim * 4), df_dim * 4, norm=inorm)
+    L += _layer_specs("h3", (3, 3, df_dim * 4, df_dim * 8), df_dim * 8, norm=inorm)
+    L += _layer_specs("h31", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8, norm=inorm)
+    L += _layer_specs("h32", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8, norm=inorm)
+    L += _layer_specs("h33", (3, 3, df_dim * 8, df_dim * 8), df_dim * 8, norm=inorm)
     L += _layer_specs("h4", (3, 3, df_dim * 8, segment_class), segment_class, norm=False)
     return L
 
@@ -524,10 +540,23 @@ class _Net:
             st = K.pack_weights_batch(entries, dtype, self.device)
             self._pack_tables[dtype] = st
         table, n, max_elems, bufs = st
-        K.repack_batch(table, n, max_elems, dtype)
+        K.repack_batch(table, n, max_elems, dtype, scale=self.pack_scale())
         key = (self.P.version, dtype)
         for u, (wf, wd) in zip(units, bufs):
             u._packed = (key, wf, wd)
+
+    def pack_scale(self):
+        """A device f32 factor per conv layer (conv_units order) that the pack multiplies into the kernels, or None."""
+        return None
+
+    def spectral_step(self):
+        """A spectrally normalised network advances its power iteration here (Discriminator); every other network: nothing."""
+
+    def spectral_grad(self, gbuf=None):
+        """... and turns the gradient with respect to W / sigma into the gradient with respect to W here."""
+
+    def spectral_state(self):
+        return None
 
     def flush_wgrads(self):
         for u in self.conv_units():
@@ -797,18 +826,102 @@ class _DiscriminatorWalk:
 class Discriminator(_DiscriminatorWalk, _Net):
     """discriminator (module.py:272-318): 8 convs, mask multiply, channel sum."""
 
-    def __init__(self, df_dim=64, in_c=3, segment_class=34, dtype=torch.bfloat16, device="cuda", eps=1e-3, leak=0.3, seed=20):
-        super().__init__(discriminator_param_specs(df_dim, in_c, segment_class), dtype, device, eps, seed)
-        self.in_c, self.segment_class = in_c, segment_class
+    def __init__(self, df_dim=64, in_c=3, segment_class=34, dtype=torch.bfloat16, device="cuda", eps=1e-3, leak=0.3, seed=20,
+                 norm="instance"):
+        """norm="spectral" (DESIGN.md 24): h1..h33 lose their instance norm -- they become conv + LeakyReLU units like h0, their
+        bias now has a gradient -- and every layer runs on W / sigma(W), sigma being the estimate of W's largest singular value
+        that one power iteration per training step (spectral_step) keeps in a persistent vector u per layer."""
+        super().__init__(discriminator_param_specs(df_dim, in_c, segment_class, norm), dtype, device, eps, seed)
+        self.in_c, self.segment_class, self.norm = in_c, segment_class, norm
+        inorm = norm == "instance"
         U = lambda *a, **k: _ConvUnit(self, *a, act=A.ACT_LRELU, leak=leak, **k)
         self.units = [U("h0", "conv", stride=2, padding="SAME", norm=False),      # :284-285
-                      U("h1", "conv", stride=2, padding="SAME"),                  # :287-289
-                      U("h2", "conv", stride=2, padding="SAME"),                  # :291-293
-                      U("h3", "conv", stride=1, padding="SAME"),                  # :295-297
-                      U("h31", "conv", stride=2, padding="VALID"),                # :299-301
-                      U("h32", "conv", stride=2, padding="VALID"),                # :303-305
-                      U("h33", "conv", stride=1, padding="VALID")]                # :307-309
+                      U("h1", "conv", stride=2, padding="SAME", norm=inorm),      # :287-289
+                      U("h2", "conv", stride=2, padding="SAME", norm=inorm),      # :291-293
+                      U("h3", "conv", stride=1, padding="SAME", norm=inorm),      # :295-297
+                      U("h31", "conv", stride=2, padding="VALID", norm=inorm),    # :299-301
+                      U("h32", "conv", stride=2, padding="VALID", norm=inorm),    # :303-305
+                      U("h33", "conv", stride=1, padding="VALID", norm=inorm)]    # :307-309
         self.h4 = _ConvUnit(self, "h4", "conv", stride=1, padding="SAME", norm=False, act=A.ACT_NONE)   # :311
+        self._sn = None
+        if not inorm:
+            self._init_spectral(seed)
+
+    # ------------------------------------------------------------------ spectral norm (DESIGN.md 24)
+    def _init_spectral(self, seed):
+        """Per layer (conv_units order): u (K), v (R*S*C), sigma and 1 / sigma, all f32 on the device, in four flat buffers (every
+        vector starts on a 16-byte boundary), and the item table over them, the kernels and this network's own gradient buffer.
+        u: a normal draw from the network's seed, l2-normalised."""
+        P, dev = self.P, self.device
+        mats = [tuple(int(d) for d in (np.prod(P.index[u.name + "_w"][2][:-1]), P.index[u.name + "_w"][2][-1])) for u in self.conv_units()]
+        pad4 = lambda n: (n + 3) // 4 * 4
+        uo, vo = np.cumsum([0] + [pad4(k) for _, k in mats]), np.cumsum([0] + [pad4(r) for r, _ in mats])
+        gen = torch.Generator(device="cpu").manual_seed(int(seed if seed is not None else 0) + 7919)
+        host = torch.zeros(int(uo[-1]), dtype=torch.float32)
+        for (_, k), o in zip(mats, uo):
+            d = torch.randn(k, generator=gen, dtype=torch.float64)
+            host[o:o + k] = (d / d.norm()).to(torch.float32)
+        sn = self._sn = SimpleNamespace(mats=mats, uo=uo, vo=vo)
+        sn.u0 = host                                                             # (the seeded start: a checkpoint without u resumes from it)
+        sn.u = host.to(dev)
+        sn.v = torch.zeros(int(vo[-1]), dtype=torch.float32, device=dev)
+        sn.sigma = torch.ones(len(mats), dtype=torch.float32, device=dev)
+        sn.inv_sigma = torch.ones(len(mats), dtype=torch.float32, device=dev)
+        sn.table = K.SpectralTable(self._spectral_entries(P.grad), dev)
+        sn.seen = None               # P.loaded at the time sigma was last computed (None: never)
+
+    def _spectral_entries(self, gbuf):
+        sn, P = self._sn, self.P
+        out = []
+        for i, (unit, (rows, k)) in enumerate(zip(self.conv_units(), sn.mats)):
+            n = unit.name + "_w"
+            out.append((P.p(n).view(rows, k), P.g(n, buf=gbuf).view(rows, k), sn.u[sn.uo[i]:sn.uo[i] + k], sn.v[sn.vo[i]:sn.vo[i] + rows],
+                        sn.sigma[i:i + 1], sn.inv_sigma[i:i + 1]))
+        return out
+
+    def spectral_step(self):
+        """One power iteration per layer on the current parameters: u, v, sigma and 1 / sigma move, and the packed operands go
+        stale, so that every forward and gradient up to the next call runs on W / sigma with this sigma.  The step bodies call
+        it once per training step, before the network's first use."""
+        if self._sn is not None:
+            K.spectral_sigma(self._sn.table, advance=True)
+            self._sn.seen = self.P.loaded
+            self.P.version += 1
+
+    def pack_scale(self):
+        """1 / sigma per layer for the pack.  A network whose parameters were just initialised or loaded has no sigma yet: it
+        is computed from u as it stands, without advancing u."""
+        sn = self._sn
+        if sn is None:
+            return None
+        if sn.seen != self.P.loaded:
+            K.spectral_sigma(sn.table, advance=False)
+            sn.seen = self.P.loaded
+        return sn.inv_sigma
+
+    def spectral_grad(self, gbuf=None):
+        """The kernels' gradients are with respect to W / sigma: dW = (dWbar - <dWbar, W / sigma> v ut) / sigma, in place on the
+        kernel slices of the gradient buffer (this network's own, or ``gbuf``).  Linear in dWbar, so once per accumulated buffer."""
+        if self._sn is not None:
+            K.spectral_grad(self._sn.table if gbuf is None else K.SpectralTable(self._spectral_entries(gbuf), self.device))
+
+    def spectral_state(self):
+        """The u vectors, per layer in one flat device buffer (None for an instance-norm network)."""
+        return None if self._sn is None else self._sn.u
+
+    def set_spectral_state(self, u=None):
+        """Replace the u vectors (a flat buffer as spectral_state gives it; None: the seeded start); sigma is computed anew."""
+        sn = self._sn
+        sn.u.copy_(sn.u0 if u is None else u)
+        sn.seen = None
+        self.P.version += 1
+
+    def spectral_vectors(self):
+        """{layer: (u, v, sigma, 1 / sigma)} as host float32 arrays / floats (tests, logging; synchronises)."""
+        sn = self._sn
+        u, v, s, r = (t.cpu().numpy() for t in (sn.u, sn.v, sn.sigma, sn.inv_sigma))
+        return {unit.name: (u[sn.uo[i]:sn.uo[i] + k].copy(), v[sn.vo[i]:sn.vo[i] + rows].copy(), float(s[i]), float(r[i]))
+                for i, (unit, (rows, k)) in enumerate(zip(self.conv_units(), sn.mats))}
 
     def out_hw(self, H, W):
         """Spatial size of the h4 map for an HxW input (deviation D1: the mask grid to use above 128x128)."""
@@ -1078,6 +1191,7 @@ class _NetFn(torch.autograd.Function):
         net = ctx.net
         gbuf = torch.zeros_like(net.P.grad)
         dx = net._run_backward(ctx.tape, dy.to(torch.float32), gbuf, ctx.needs_input_grad[2])
+        net.spectral_grad(gbuf)                      # (a spectrally normalised network: gradients with respect to the stored kernels)
         grads = tuple(net.P.g(n, buf=gbuf) for n in net.P.names())
         return (None, None, dx) + grads
 
