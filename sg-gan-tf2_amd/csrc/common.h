@@ -226,6 +226,11 @@ template <int N> __device__ inline void sgg_wait_vm() {                 // until
 #define SGG_WAIT_LGKM0() do { __builtin_amdgcn_s_waitcnt(0xC07F); asm volatile("" ::: "memory"); } while (0)
 
 static inline int sgg_check_launch() { return hipGetLastError() == hipSuccess ? SGG_OK : SGG_ELAUNCH; }
+// blocks of 256 threads for a grid-stride walk over n elements, at most `cap` (misc.hip, adam.hip)
+static inline int grid_for(int64_t n, int cap = 4096) {
+    int64_t b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 // Kernels that need more than 64 KB of dynamic LDS must have the attribute raised once PER DEVICE (a process may drive
 // several GPUs, from several host threads).  `done` holds one bit per device ordinal; setting the attribute twice is

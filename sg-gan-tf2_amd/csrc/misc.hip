@@ -1,7 +1,7 @@
 // misc.hip -- the small HBM-bound kernels of the train step: activations, bias gradient, semantic mask
-// multiply-reduce (module.py:312-314), losses (model.py:149-166), Keras-form Adam (model.py:199-207), the
+// multiply-reduce (module.py:312-314), losses (model.py:149-166), the
 // colour->class-index map (segment_class.py:60-99), one-hot + resample of the mask (utils.py:158-165,197-199)
-// and the channel pad/unpad at the boundary.
+// and the channel pad/unpad at the boundary.  (The optimizer is adam.hip.)
 #include "common.h"
 
 // ---------------------------------------------------------------- activations / add
@@ -404,325 +404,6 @@ __global__ __launch_bounds__(256) void l1_final_kernel(const float* partial, int
     if (threadIdx.x == 0) { float l = (float)(red[0] * scale); *loss = accumulate ? *loss + l : l; }
 }
 
-// ---------------------------------------------------------------- Adam (Keras form), flat buffer
-// one element of the update (every Adam kernel below goes through it, so their results are the same bits)
-__device__ __forceinline__ void adam_apply(float* th, const float* g, float* m, float* v, int64_t i, float lr_t, float b1, float b2,
-                                           float eps, float gs) {
-    float gi = g[i] * gs;
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    th[i] = th[i] - lr_t * mi / (sqrtf(vi) + eps);
-}
-__global__ __launch_bounds__(256) void adam_kernel(float* th, const float* g, float* m, float* v, int64_t n, float lr_t,
-                                                   float b1, float b2, float eps, float gs) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        adam_apply(th, g, m, v, i, lr_t, b1, b2, eps, gs);
-    }
-}
-
-// The two pieces of the prep launches' arithmetic (below), shared by all of them so that they cannot drift apart: the
-// bias-corrected rate of step t, and the linear decay of the base rate.
-__device__ inline float adam_lr_t(float lr, int64_t t_, float b1, float b2) {
-    const double t = (double)t_;
-    return (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
-}
-__device__ inline float adam_sched_rate(int64_t it, const int64_t* sched, float lr) {
-    const int64_t spe = sched[0] < 1 ? 1 : sched[0], epoch_step = sched[1], epochs = sched[2];
-    const int64_t e = it / spe;
-    float lr_e = lr;
-    if (!(epochs <= epoch_step || e < epoch_step)) {
-        const int64_t left = epochs - e > 0 ? epochs - e : 0;
-        lr_e = (float)(((double)lr * (double)left) / (double)(epochs - epoch_step));
-    }
-    return lr_e;
-}
-
-// Same update with the step number read from a device-resident counter (Keras keeps `optimizer.iterations` as a variable
-// too).  `state` is int64[2]: [0] = iterations, [1] = scratch (the bits of lr_t for the step being applied).  A 1-thread
-// launch evaluates lr_t in double from t = iterations + 1 (same formula as the host path of sgg_adam) and bumps the
-// counter; the update kernel reads the float.  The host never touches t, so the pair of launches can sit inside a captured
-// HIP graph and be replayed.  (Evaluating pow() in every block of the update kernel cost +18 us per launch.)
-__global__ void adam_prep_kernel(int64_t* state, float lr, float b1, float b2) {
-    const float lr_t = adam_lr_t(lr, state[0] + 1, b1, b2);
-    state[0] += 1;
-    reinterpret_cast<float*>(state + 1)[0] = lr_t;
-}
-// The prep launch of sgg_adam_sched: the same, with the base rate first put through the reference's linear decay
-// (model.py:223, commented out there).  The epoch is iterations / steps_per_epoch, and `sched` = {steps_per_epoch,
-// epoch_step, epochs} is read from device memory at run time -- never a kernel argument -- so a captured launch follows a
-// descriptor that is written after the capture.  lr_e is rounded to f32 once (what a Keras learning_rate.assign would
-// hold); from there on the arithmetic is adam_prep_kernel's, so the pair is bit-identical to sgg_adam_iter given lr_e.
-__global__ void adam_sched_prep_kernel(int64_t* state, const int64_t* sched, float lr, float b1, float b2) {
-    const int64_t it = state[0];
-    const float lr_t = adam_lr_t(adam_sched_rate(it, sched, lr), it + 1, b1, b2);
-    state[0] = it + 1;
-    reinterpret_cast<float*>(state + 1)[0] = lr_t;
-}
-__global__ __launch_bounds__(256) void adam_iter_kernel(float* th, const float* g, float* m, float* v, int64_t n, const int64_t* state,
-                                                        float b1, float b2, float eps, float gs) {
-    const float lr_t = reinterpret_cast<const float*>(state + 1)[0];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        adam_apply(th, g, m, v, i, lr_t, b1, b2, eps, gs);
-    }
-}
-
-// ---------------------------------------------------------------- guarded Adam: global gradient norm, clip, non-finite skip
-// Three launches, nothing on the host, no atomics (two runs give the same bits):
-//   gradsq_partial_kernel   one pass over the gradient: per GSQ_CHUNK elements a sum of squares (double) and a non-finite flag
-//   adam_guard_prep_kernel  folds the chunk records in a fixed order; ONE thread then decides skip / clip / lr_t
-//   adam_guard_kernel       adam_iter_kernel's update with g * (grad_scale * clip); returns at once on skip
-// Workspace: a 16-byte decision header {u32 skip, f32 grad_scale * clip, 0, 0} followed by one 16-byte record per chunk.
-// The chunk is a constant and the grid is ceil(n / GSQ_CHUNK): neither depends on the device, so neither does the sum.
-#define GSQ_CHUNK 8192
-struct GsqPartial { double sumsq; uint32_t bad, pad; };
-static_assert(sizeof(GsqPartial) == 16, "one 16-byte record per chunk");
-static inline int64_t gsq_chunks(int64_t n) { return (n + GSQ_CHUNK - 1) / GSQ_CHUNK; }
-
-__device__ __forceinline__ void gsq_acc(const u32x4& c, double& s, uint32_t& bad) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        // NaN / +-Inf by the bit pattern (exponent all ones): a finite sum that overflows is not "non-finite"
-        bad |= (c[e] & 0x7f800000u) == 0x7f800000u;
-        const double x = (double)__uint_as_float(c[e]);
-        s += x * x;                                             // (an f32 squared is exact in double)
-    }
-}
-__global__ __launch_bounds__(256) void gradsq_partial_kernel(const float* g, int64_t n, GsqPartial* part) {
-    const int64_t e0 = (int64_t)blockIdx.x * GSQ_CHUNK;
-    const int64_t e1 = e0 + GSQ_CHUNK < n ? e0 + GSQ_CHUNK : n;
-    const int64_t v1 = e0 + ((e1 - e0) & ~(int64_t)3);          // end of the chunk's whole 16-byte groups (e0 is a multiple of 4)
-    double s = 0.0;
-    uint32_t bad = 0;
-    // thread t takes the 16-byte groups t, t + 256, ... of the chunk in that order.  A whole chunk (every block but the last)
-    // issues its 8 loads back to back -- 32 KiB in flight per block -- before the first is consumed; the last chunk walks
-    // what it has, then the n % 4 scalar tail.  Same order either way, so a chunk's sum does not depend on which path ran.
-    if (e1 - e0 == GSQ_CHUNK) {
-        u32x4 c[GSQ_CHUNK / 1024];
-#pragma unroll
-        for (int u = 0; u < GSQ_CHUNK / 1024; ++u) c[u] = ld16(g + e0 + 4 * (threadIdx.x + 256 * u));
-#pragma unroll
-        for (int u = 0; u < GSQ_CHUNK / 1024; ++u) gsq_acc(c[u], s, bad);
-    } else {
-        for (int64_t i = e0 + 4 * threadIdx.x; i + 4 <= v1; i += 1024) gsq_acc(ld16(g + i), s, bad);
-        if (v1 + threadIdx.x < e1) {
-            u32x4 c = zero16();                                 // (+0.0 squared adds nothing and sets no flag)
-            c[0] = __float_as_uint(g[v1 + threadIdx.x]);
-            gsq_acc(c, s, bad);
-        }
-    }
-    __shared__ double red[256];
-    __shared__ uint32_t flag[256];
-    red[threadIdx.x] = s; flag[threadIdx.x] = bad;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { red[threadIdx.x] += red[threadIdx.x + o]; flag[threadIdx.x] |= flag[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { GsqPartial r; r.sumsq = red[0]; r.bad = flag[0]; r.pad = 0; part[blockIdx.x] = r; }
-}
-
-// One block.  Its 256 threads fold the chunk records (thread k takes records k, k + 256, ... in order, then the same fixed
-// tree as above): a single thread walking the 1 400 - 2 700 records of a generator one dependent load after the other would
-// take longer than the pass that made them (cf. colsum_final_kernel).  Thread 0 alone then decides, in double:
-//   norm = sqrt(sumsq) * grad_scale;   skip = any flag;   clip = 1 if max_norm <= 0 or norm <= max_norm, else
-//   (float)(max_norm / norm);   lr_t as adam_prep_kernel / adam_sched_prep_kernel (sched == NULL: no decay).
-// On skip `iterations` stays, lr_t = 0 and clip = 1 are written, and the update kernel returns at once; bias correction and
-// the decay's epoch count therefore follow APPLIED updates.  guard = {last_norm, last_clip, skipped_total, applied_total}.
-__global__ __launch_bounds__(256) void adam_guard_prep_kernel(int64_t* state, const int64_t* sched, const GsqPartial* part, int chunks,
-                                                              uint32_t* head, double* guard, float lr, float b1, float b2, float gs,
-                                                              float max_norm) {
-    __shared__ double red[256];
-    __shared__ uint32_t flag[256];
-    double s = 0.0;
-    uint32_t bad = 0;
-    for (int k = threadIdx.x; k < chunks; k += 256) { const GsqPartial r = part[k]; s += r.sumsq; bad |= r.bad; }
-    red[threadIdx.x] = s; flag[threadIdx.x] = bad;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { red[threadIdx.x] += red[threadIdx.x + o]; flag[threadIdx.x] |= flag[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    const double norm = sqrt(red[0]) * (double)gs;
-    const bool skip = flag[0] != 0;
-    float clip = 1.f;
-    if (!skip && max_norm > 0.f && !(norm <= (double)max_norm)) clip = (float)((double)max_norm / norm);
-    float lr_t = 0.f;
-    if (!skip) {
-        const int64_t it = state[0];
-        lr_t = adam_lr_t(sched ? adam_sched_rate(it, sched, lr) : lr, it + 1, b1, b2);
-        state[0] = it + 1;
-    }
-    reinterpret_cast<float*>(state + 1)[0] = lr_t;
-    head[0] = skip ? 1u : 0u;
-    head[1] = __float_as_uint(gs * clip);                       // the update's gradient factor, formed once in f32
-    head[2] = 0u; head[3] = 0u;
-    guard[0] = norm; guard[1] = (double)clip;
-    guard[2] += skip ? 1.0 : 0.0; guard[3] += skip ? 0.0 : 1.0;
-}
-
-__global__ __launch_bounds__(256) void adam_guard_kernel(float* th, const float* g, float* m, float* v, int64_t n, const int64_t* state,
-                                                         const uint32_t* head, float b1, float b2, float eps) {
-    if (head[0]) return;                                        // skipped step: theta, m and v keep their bits
-    const float lr_t = reinterpret_cast<const float*>(state + 1)[0];
-    const float gs = __uint_as_float(head[1]);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        adam_apply(th, g, m, v, i, lr_t, b1, b2, eps, gs);
-}
-
-// ---------------------------------------------------------------- Adam + exponential moving average of theta (sgg_adam_ema)
-// The update of sgg_adam_iter / sgg_adam_sched / sgg_adam_guard with a fifth stream: ema = d_t ema + (1 - d_t) theta_new, the
-// average tf.train.ExponentialMovingAverage(decay, num_updates) keeps, d_t = min(decay, (1 + t) / (10 + t)) with t the number
-// of APPLIED updates (iterations after this one's increment).  d_t is formed by the launch that forms lr_t and handed over in
-// device memory (ema_state = {d_t, 1 - d_t}), so a captured launch follows the counter, a skipped step leaves the average
-// alone and a resumed run goes on along the ramp.
-//   adam_ema_prep_kernel   1 thread (plain) or 1 block (guarded: it folds the chunk records first, as adam_guard_prep_kernel)
-//   adam_ema_kernel        16 bytes per lane on all five streams, EMA_CHUNK elements per block, scalar tail for n % 4
-// adam_apply_reg is adam_apply on registers -- the same expression, and the build has -ffp-contract=off -- so theta, m and v
-// come out with the bits of the scalar kernels above (tests/test_gpu_ema.py compares them).
-#define EMA_CHUNK 2048
-static_assert(EMA_CHUNK % 1024 == 0, "a whole chunk is EMA_CHUNK / 1024 16-byte groups per thread");
-static inline int64_t ema_chunks(int64_t n) { return (n + EMA_CHUNK - 1) / EMA_CHUNK; }
-
-__device__ __forceinline__ void adam_apply_reg(float& th, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
-                                               float gs) {
-    float gi = g * gs;
-    float mi = b1 * m + (1.f - b1) * gi;
-    float vi = b2 * v + (1.f - b2) * gi * gi;
-    m = mi; v = vi;
-    th = th - lr_t * mi / (sqrtf(vi) + eps);
-}
-__device__ __forceinline__ void adam_ema_group(u32x4& th, const u32x4& g, u32x4& m, u32x4& v, u32x4& e, float lr_t, float b1, float b2,
-                                               float eps, float gs, float d, float omd) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float t = __uint_as_float(th[k]), mk = __uint_as_float(m[k]), vk = __uint_as_float(v[k]);
-        adam_apply_reg(t, __uint_as_float(g[k]), mk, vk, lr_t, b1, b2, eps, gs);
-        th[k] = __float_as_uint(t); m[k] = __float_as_uint(mk); v[k] = __float_as_uint(vk);
-        e[k] = __float_as_uint(d * __uint_as_float(e[k]) + omd * t);
-    }
-}
-
-// part == NULL: one thread, no guard (head and guard are not touched).  Otherwise one block of 256 threads: the fold and the
-// decision of adam_guard_prep_kernel, term for term, so guard[0..3], the header and lr_t are that kernel's bits.
-__global__ __launch_bounds__(256) void adam_ema_prep_kernel(int64_t* state, const int64_t* sched, const GsqPartial* part, int chunks,
-                                                            uint32_t* head, double* guard, float lr, float b1, float b2, float gs,
-                                                            float max_norm, float ema_decay, float* ema_state) {
-    __shared__ double red[256];
-    __shared__ uint32_t flag[256];
-    bool skip = false;
-    if (part) {
-        double s = 0.0;
-        uint32_t bad = 0;
-        for (int k = threadIdx.x; k < chunks; k += 256) { const GsqPartial r = part[k]; s += r.sumsq; bad |= r.bad; }
-        red[threadIdx.x] = s; flag[threadIdx.x] = bad;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) { red[threadIdx.x] += red[threadIdx.x + o]; flag[threadIdx.x] |= flag[threadIdx.x + o]; }
-            __syncthreads();
-        }
-        if (threadIdx.x != 0) return;
-        const double norm = sqrt(red[0]) * (double)gs;
-        skip = flag[0] != 0;
-        float clip = 1.f;
-        if (!skip && max_norm > 0.f && !(norm <= (double)max_norm)) clip = (float)((double)max_norm / norm);
-        head[0] = skip ? 1u : 0u;
-        head[1] = __float_as_uint(gs * clip);
-        head[2] = 0u; head[3] = 0u;
-        guard[0] = norm; guard[1] = (double)clip;
-        guard[2] += skip ? 1.0 : 0.0; guard[3] += skip ? 0.0 : 1.0;
-    } else if (threadIdx.x != 0) {
-        return;
-    }
-    float lr_t = 0.f;
-    if (!skip) {
-        const int64_t it = state[0];
-        lr_t = adam_lr_t(sched ? adam_sched_rate(it, sched, lr) : lr, it + 1, b1, b2);
-        state[0] = it + 1;
-        const double t = (double)(it + 1), ramp = (1.0 + t) / (10.0 + t);
-        const float d = (float)((double)ema_decay < ramp ? (double)ema_decay : ramp);
-        ema_state[0] = d;
-        ema_state[1] = 1.f - d;                                 // (a skipped step keeps both)
-    }
-    reinterpret_cast<float*>(state + 1)[0] = lr_t;
-}
-
-// Block b owns elements [b EMA_CHUNK, (b + 1) EMA_CHUNK).  A whole chunk issues its 2 x 5 16-byte loads back to back -- 40 KiB
-// in flight per block -- before the first is consumed; the last chunk walks the 16-byte groups it has, then the n % 4 tail
-// one element per thread.  head == NULL: the plain update with the launch's grad_scale; otherwise the guard's header decides
-// (skip: every stream keeps its bits) and carries grad_scale * clip.  No element is touched by two threads and nothing is
-// accumulated across threads: two runs give the same bits.
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* th, const float* g, float* m, float* v, float* ema, int64_t n,
-                                                       const int64_t* state, const uint32_t* head, const float* ema_state, float b1,
-                                                       float b2, float eps, float gs) {
-    if (head) {
-        if (head[0]) return;
-        gs = __uint_as_float(head[1]);
-    }
-    const float lr_t = reinterpret_cast<const float*>(state + 1)[0];
-    const float d = ema_state[0], omd = ema_state[1];
-    const int64_t e0 = (int64_t)blockIdx.x * EMA_CHUNK;
-    const int64_t e1 = e0 + EMA_CHUNK < n ? e0 + EMA_CHUNK : n;
-    if (e1 - e0 == EMA_CHUNK) {
-        constexpr int U = EMA_CHUNK / 1024;
-        u32x4 ct[U], cg[U], cm[U], cv[U], ce[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = e0 + 4 * (threadIdx.x + 256 * u);
-            ct[u] = ld16(th + i); cg[u] = ld16(g + i); cm[u] = ld16(m + i); cv[u] = ld16(v + i); ce[u] = ld16(ema + i);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = e0 + 4 * (threadIdx.x + 256 * u);
-            adam_ema_group(ct[u], cg[u], cm[u], cv[u], ce[u], lr_t, b1, b2, eps, gs, d, omd);
-            st16(th + i, ct[u]); st16(m + i, cm[u]); st16(v + i, cv[u]); st16(ema + i, ce[u]);
-        }
-    } else {
-        const int64_t v1 = e0 + ((e1 - e0) & ~(int64_t)3);      // end of the chunk's whole 16-byte groups (e0 is a multiple of 4)
-        for (int64_t i = e0 + 4 * threadIdx.x; i + 4 <= v1; i += 1024) {
-            u32x4 ct = ld16(th + i), cg = ld16(g + i), cm = ld16(m + i), cv = ld16(v + i), ce = ld16(ema + i);
-            adam_ema_group(ct, cg, cm, cv, ce, lr_t, b1, b2, eps, gs, d, omd);
-            st16(th + i, ct); st16(m + i, cm); st16(v + i, cv); st16(ema + i, ce);
-        }
-        const int64_t i = v1 + threadIdx.x;
-        if (i < e1) {
-            float t = th[i], mk = m[i], vk = v[i];
-            adam_apply_reg(t, g[i], mk, vk, lr_t, b1, b2, eps, gs);
-            th[i] = t; m[i] = mk; v[i] = vk;
-            ema[i] = d * ema[i] + omd * t;
-        }
-    }
-}
-
-// Bitwise exchange of two buffers, same chunk walk (the payload never passes through a float: NaN bits survive).
-__global__ __launch_bounds__(256) void swap_f32_kernel(uint32_t* a, uint32_t* b, int64_t n) {
-    const int64_t e0 = (int64_t)blockIdx.x * EMA_CHUNK;
-    const int64_t e1 = e0 + EMA_CHUNK < n ? e0 + EMA_CHUNK : n;
-    if (e1 - e0 == EMA_CHUNK) {
-        constexpr int U = EMA_CHUNK / 1024;
-        u32x4 ca[U], cb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = e0 + 4 * (threadIdx.x + 256 * u);
-            ca[u] = ld16(a + i); cb[u] = ld16(b + i);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = e0 + 4 * (threadIdx.x + 256 * u);
-            st16(a + i, cb[u]); st16(b + i, ca[u]);
-        }
-    } else {
-        const int64_t v1 = e0 + ((e1 - e0) & ~(int64_t)3);
-        for (int64_t i = e0 + 4 * threadIdx.x; i + 4 <= v1; i += 1024) {
-            const u32x4 ca = ld16(a + i), cb = ld16(b + i);
-            st16(a + i, cb); st16(b + i, ca);
-        }
-        const int64_t i = v1 + threadIdx.x;
-        if (i < e1) { const uint32_t x = a[i]; a[i] = b[i]; b[i] = x; }
-    }
-}
-
 // ---------------------------------------------------------------- colour -> class index (integer, bit exact)
 // segment_class.py:63-66: 21 colours -> {1..7}; default 0.  Keys are 24-bit (R<<16|G<<8|B).
 #define SGG_SEG_KEYS 0x804080, 0xF423E8, 0xFAAAA0, 0xE6968C, 0x464646, 0x66669C, 0xBE9999, 0xB4A5B4, 0x966464, 0x96785A, \
@@ -823,11 +504,6 @@ __global__ __launch_bounds__(256) void argmax_u8_kernel(const T* x, int32_t* out
         }
         out[i] = best;
     }
-}
-
-static inline int grid_for(int64_t n, int cap = 4096) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
 SggTimedLaunch& sgg_timed_launch() {
@@ -1021,98 +697,6 @@ int sgg_l1_loss(const void* a, const void* b, int64_t P, int Cr, int Cp, float w
     else if (dtype == SGG_F32) hipLaunchKernelGGL(l1_partial_kernel<float>, dim3(chunks), dim3(256), 0, s, (const char*)a, (const char*)b, (char*)db, (float*)ws, nvec, Cr, Cp, gval, (accumulate >> 1) & 1);
     else return SGG_EINVAL;
     hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, chunks, (double)weight / cnt, loss, accumulate & 1);
-    return sgg_check_launch();
-}
-
-int sgg_adam(float* theta, const float* g, float* m, float* v, int64_t n, int t, float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
-    if (!theta || !g || !m || !v || n < 0 || t < 1) return SGG_EINVAL;
-    if (n == 0) return SGG_OK;
-    double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n, (float)lr_t, beta1, beta2, eps, grad_scale);
-    return sgg_check_launch();
-}
-
-int sgg_adam_iter(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, float lr, float beta1, float beta2,
-                  float eps, float grad_scale, void* stream) {
-    if (!theta || !g || !m || !v || !state || n < 0) return SGG_EINVAL;
-    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2);
-    int rc = sgg_check_launch();
-    if (rc || n == 0) return rc;
-    hipLaunchKernelGGL(adam_iter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n, (const int64_t*)state,
-                       beta1, beta2, eps, grad_scale);
-    return sgg_check_launch();
-}
-
-int sgg_adam_sched(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched, float lr,
-                   float beta1, float beta2, float eps, float grad_scale, void* stream) {
-    if (!theta || !g || !m || !v || !state || !sched || n < 0) return SGG_EINVAL;
-    hipLaunchKernelGGL(adam_sched_prep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, sched, lr, beta1, beta2);
-    int rc = sgg_check_launch();
-    if (rc || n == 0) return rc;
-    hipLaunchKernelGGL(adam_iter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n, (const int64_t*)state,
-                       beta1, beta2, eps, grad_scale);
-    return sgg_check_launch();
-}
-
-size_t sgg_grad_guard_workspace(int64_t n) {
-    if (n <= 0) return 0;
-    return 16 + (size_t)gsq_chunks(n) * sizeof(GsqPartial);
-}
-static int grad_guard_args(const float* g, int64_t n, void* ws, size_t ws_bytes) {
-    if (!g || !ws || n <= 0 || ((uintptr_t)g & 15) || ((uintptr_t)ws & 15) || gsq_chunks(n) > 0x7fffffff) return SGG_EINVAL;
-    if (ws_bytes < sgg_grad_guard_workspace(n)) return SGG_EWORKSPACE;
-    return SGG_OK;
-}
-int sgg_grad_sumsq(const float* g, int64_t n, void* ws, size_t ws_bytes, void* stream) {
-    int rc = grad_guard_args(g, n, ws, ws_bytes);
-    if (rc) return rc;
-    hipLaunchKernelGGL(gradsq_partial_kernel, dim3((unsigned)gsq_chunks(n)), dim3(256), 0, (hipStream_t)stream, g, n,
-                       reinterpret_cast<GsqPartial*>((char*)ws + 16));
-    return sgg_check_launch();
-}
-int sgg_adam_guard(float* theta, const float* g, float* m, float* v, int64_t n, int64_t* state, const int64_t* sched, float lr,
-                   float beta1, float beta2, float eps, float grad_scale, float max_norm, double* guard, void* ws, size_t ws_bytes,
-                   void* stream) {
-    if (!theta || !m || !v || !state || !guard) return SGG_EINVAL;
-    int rc = sgg_grad_sumsq(g, n, ws, ws_bytes, stream);        // (validates g, n and the workspace before anything is launched)
-    if (rc) return rc;
-    hipLaunchKernelGGL(adam_guard_prep_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, sched,
-                       reinterpret_cast<const GsqPartial*>((char*)ws + 16), (int)gsq_chunks(n), (uint32_t*)ws, guard, lr, beta1, beta2,
-                       grad_scale, max_norm);
-    rc = sgg_check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(adam_guard_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v, n,
-                       (const int64_t*)state, (const uint32_t*)ws, beta1, beta2, eps);
-    return sgg_check_launch();
-}
-
-static inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
-int sgg_adam_ema(float* theta, const float* g, float* m, float* v, float* ema, int64_t n, int64_t* state, const int64_t* sched, float lr,
-                 float beta1, float beta2, float eps, float grad_scale, float ema_decay, float* ema_state, float max_norm, int guarded,
-                 double* guard, void* ws, size_t ws_bytes, void* stream) {
-    if (!theta || !g || !m || !v || !ema || !state || !ema_state || n <= 0 || ema_chunks(n) > 0x7fffffff) return SGG_EINVAL;
-    if (!(ema_decay > 0.f && ema_decay < 1.f)) return SGG_EINVAL;
-    if (misaligned16(theta) || misaligned16(g) || misaligned16(m) || misaligned16(v) || misaligned16(ema)) return SGG_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const GsqPartial* part = nullptr;
-    if (guarded) {
-        if (!guard) return SGG_EINVAL;
-        int rc = sgg_grad_sumsq(g, n, ws, ws_bytes, stream);    // (validates the workspace before anything is launched)
-        if (rc) return rc;
-        part = reinterpret_cast<const GsqPartial*>((char*)ws + 16);
-    }
-    hipLaunchKernelGGL(adam_ema_prep_kernel, dim3(1), dim3(guarded ? 256 : 1), 0, s, state, sched, part, (int)gsq_chunks(n),
-                       (uint32_t*)(guarded ? ws : nullptr), guard, lr, beta1, beta2, grad_scale, max_norm, ema_decay, ema_state);
-    int rc = sgg_check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(adam_ema_kernel, dim3((unsigned)ema_chunks(n)), dim3(256), 0, s, theta, g, m, v, ema, n, (const int64_t*)state,
-                       (const uint32_t*)(guarded ? ws : nullptr), (const float*)ema_state, beta1, beta2, eps, grad_scale);
-    return sgg_check_launch();
-}
-
-int sgg_swap_f32(float* a, float* b, int64_t n, void* stream) {
-    if (!a || !b || n <= 0 || ema_chunks(n) > 0x7fffffff || misaligned16(a) || misaligned16(b)) return SGG_EINVAL;
-    hipLaunchKernelGGL(swap_f32_kernel, dim3((unsigned)ema_chunks(n)), dim3(256), 0, (hipStream_t)stream, (uint32_t*)a, (uint32_t*)b, n);
     return sgg_check_launch();
 }
 

@@ -660,19 +660,26 @@ def adam(theta, g, m, v, t, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scal
     A.check(A.lib().sgg_adam(_p(theta), _p(g), _p(m), _p(v), theta.numel(), int(t), lr, beta1, beta2, eps, grad_scale, _s()), "adam")
 
 
-def adam_iter(theta, g, m, v, state, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0):
-    """Adam with the step number kept on the device (``state``: int64[2] = [iterations, scratch]; iterations is incremented)."""
+def _adam_args(theta, g, m, v, state, sched=None, guard=None):
+    """What the entry points with a device-side counter ask of their tensors (csrc/adam.hip): f32 buffers of one length,
+    ``state`` int64[2], ``sched`` int64[3] and ``guard`` float64[4] where given."""
     assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
     assert state.dtype == torch.int64 and state.numel() == 2
+    assert sched is None or (sched.dtype == torch.int64 and sched.numel() == 3)
+    assert guard is None or (guard.dtype == torch.float64 and guard.numel() == 4)
+
+
+def adam_iter(theta, g, m, v, state, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0):
+    """Adam with the step number kept on the device (``state``: int64[2] = [iterations, scratch]; iterations is incremented)."""
+    _adam_args(theta, g, m, v, state)
     A.check(A.lib().sgg_adam_iter(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(state), lr, beta1, beta2, eps, grad_scale, _s()), "adam_iter")
 
 
 def adam_sched(theta, g, m, v, state, sched, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0):
     """``adam_iter`` with the base rate ``lr`` put through the linear decay of model.py:223 on the device: ``sched`` is a device
     int64[3] = [steps_per_epoch, epoch_step, epochs], read when the launch runs (``scheduled_lr`` states the rule)."""
-    assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
-    assert state.dtype == torch.int64 and state.numel() == 2
-    assert sched.dtype == torch.int64 and sched.numel() == 3
+    assert sched is not None
+    _adam_args(theta, g, m, v, state, sched)
     A.check(A.lib().sgg_adam_sched(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(state), _p(sched), lr, beta1, beta2, eps, grad_scale, _s()),
             "adam_sched")
 
@@ -691,7 +698,7 @@ def scheduled_lr(lr, iterations, steps_per_epoch, epoch_step, epochs):
     return np.float32((float(lr) * float(max(epochs - e, 0))) / float(epochs - epoch_step))
 
 
-GRAD_GUARD_CHUNK = 8192          # elements per block of the sum-of-squares pass (GSQ_CHUNK, csrc/misc.hip)
+GRAD_GUARD_CHUNK = 8192          # elements per block of the sum-of-squares pass (GSQ_CHUNK, csrc/adam.hip)
 
 
 def grad_guard_workspace(n: int, device) -> torch.Tensor:
@@ -715,10 +722,8 @@ def grad_sumsq(g, ws=None):
 def adam_guard(theta, g, m, v, state, guard, ws, sched=None, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0, max_norm=0.0):
     """``adam_iter`` (``sched`` None) or ``adam_sched`` behind the device-side guard (``guarded_update`` states the rule):
     ``guard`` is a device float64[4] = [last_norm, last_clip, skipped_total, applied_total], ``ws`` a ``grad_guard_workspace``."""
-    assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel()
-    assert state.dtype == torch.int64 and state.numel() == 2
-    assert guard.dtype == torch.float64 and guard.numel() == 4
-    assert sched is None or (sched.dtype == torch.int64 and sched.numel() == 3)
+    assert guard is not None
+    _adam_args(theta, g, m, v, state, sched, guard)
     A.check(A.lib().sgg_adam_guard(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(state), _p(sched), lr, beta1, beta2, eps,
                                    grad_scale, float(max_norm), _p(guard), _p(ws), ws.numel(), _s()), "adam_guard")
 
@@ -755,7 +760,7 @@ def guarded_update(theta, g, m, v, iterations, lr=1e-3, beta1=0.5, beta2=0.999, 
     return theta - lr_t * m / (np.sqrt(v) + eps), m, v, t, info
 
 
-EMA_CHUNK = 2048                 # elements per block of the fused update and of swap_ (EMA_CHUNK, csrc/misc.hip)
+EMA_CHUNK = 2048                 # elements per block of the fused update and of swap_ (EMA_CHUNK, csrc/adam.hip)
 
 
 def adam_ema(theta, g, m, v, ema, state, ema_state, ema_decay, sched=None, lr=1e-3, beta1=0.5, beta2=0.999, eps=1e-7, grad_scale=1.0,
@@ -765,11 +770,9 @@ def adam_ema(theta, g, m, v, ema, state, ema_state, ema_decay, sched=None, lr=1e
     after the update (include/sggan.h).  ``ema_state`` is a device
     float32[2] = [d_t, 1 - d_t], written by the prep launch; theta, m, v, iterations and the guard record come out with the
     bits of the calls named above."""
-    assert theta.dtype == torch.float32 and theta.numel() == g.numel() == m.numel() == v.numel() == ema.numel()
-    assert state.dtype == torch.int64 and state.numel() == 2
-    assert ema.dtype == torch.float32 and ema_state.dtype == torch.float32 and ema_state.numel() == 2
-    assert sched is None or (sched.dtype == torch.int64 and sched.numel() == 3)
-    assert guard is None or (guard.dtype == torch.float64 and guard.numel() == 4 and ws is not None)
+    _adam_args(theta, g, m, v, state, sched, guard)
+    assert guard is None or ws is not None
+    assert ema.dtype == torch.float32 and ema.numel() == theta.numel() and ema_state.dtype == torch.float32 and ema_state.numel() == 2
     A.check(A.lib().sgg_adam_ema(_p(theta), _p(g), _p(m), _p(v), _p(ema), theta.numel(), _p(state), _p(sched), lr, beta1, beta2, eps,
                                  grad_scale, float(ema_decay), _p(ema_state), float(max_norm), int(guard is not None), _p(guard),
                                  _p(ws) if guard is not None else None, ws.numel() if guard is not None else 0, _s()), "adam_ema")

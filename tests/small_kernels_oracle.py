@@ -1,4 +1,4 @@
-"""NumPy float64 statements of the small kernels of csrc/misc.hip, written from include/sggan.h (not from the kernels):
+"""NumPy float64 statements of the small kernels of csrc/misc.hip (Adam: csrc/adam.hip), written from include/sggan.h (not from the kernels):
 column sum, L1 loss, BCE-with-logits, the LSGAN criterion, the Sobel gradient loss, the segmentation-edge indicator,
 channel pad / unpad, the argmax-u8 label rule, the confusion histogram, the activations and Keras-form Adam.
 

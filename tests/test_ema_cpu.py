@@ -4,9 +4,6 @@ checkpoint key handling of sggan.state_dict / load_state_dict on host-memory par
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +11,7 @@ import torch
 
 from sggan_amd import _abi as A
 from tests import ema_oracle as E
+from tests.kernel_resources import kernel_resource_usage, the_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR, B1, B2, EPS = 2e-4, 0.5, 0.999, 1e-7
@@ -76,7 +74,7 @@ def test_ema_entry_points_are_declared_exported_and_bound():
     assert L.sgg_adam_ema.argtypes == A.SIGNATURES["sgg_adam_ema"][1] and L.sgg_swap_f32.argtypes == A.SIGNATURES["sgg_swap_f32"][1]
     from sggan_amd import kernels as K
     assert callable(K.adam_ema) and callable(K.swap_) and K.EMA_CHUNK % 1024 == 0
-    assert re.search(r"#define EMA_CHUNK %d\b" % K.EMA_CHUNK, open(os.path.join(ROOT, "sg-gan-tf2_amd", "csrc", "misc.hip")).read())
+    assert re.search(r"#define EMA_CHUNK %d\b" % K.EMA_CHUNK, open(os.path.join(ROOT, "sg-gan-tf2_amd", "csrc", "adam.hip")).read())
 
 
 def test_ema_entry_points_validate_on_the_host():
@@ -116,37 +114,15 @@ def test_ema_entry_points_validate_on_the_host():
 
 # ----------------------------------------------------------------------------- build
 def test_ema_kernels_do_not_spill_and_use_no_scratch(tmp_path):
-    """csrc/misc.hip recompiled with -Rpass-analysis=kernel-resource-usage (the method of tests/test_build_resources.py): the
-    three new kernels are in the build, each once, with zero VGPR / SGPR spills and no scratch.  The update kernel keeps its
+    """csrc/adam.hip recompiled with -Rpass-analysis=kernel-resource-usage (tests/kernel_resources.py): the three kernels of
+    the average are in the build, each once, with zero VGPR / SGPR spills and no scratch.  The update kernel keeps its
     ten 16-byte loads (40 VGPRs) in flight and still runs several waves per SIMD; the swap needs no LDS."""
-    sys.path.insert(0, os.path.join(ROOT, "sg-gan-tf2_amd"))
-    import build as B
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("hipcc not available")
-    r = subprocess.run([hipcc, *B.FLAGS, "-c", os.path.join(B.CSRC, "misc.hip"), "-o", str(tmp_path / "misc.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    pats = (("vspill", r"VGPRs Spill: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-            ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("vgpr", r" VGPRs: (\d+)"))
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        for key, pat in pats:
-            m = re.search(pat, line)
-            if m and name:
-                usage[name][key] = int(m.group(1))
-    for frag, lds, min_occ in (("adam_ema_prep_kernel", 3072, 8), ("adam_ema_kernel", 0, 4), ("swap_f32_kernel", 0, 8)):
-        hits = [v for k, v in usage.items() if frag in k]
-        assert len(hits) == 1, f"kernel {frag}: {len(hits)} matches in the build"
-        u = hits[0]
+    usage = kernel_resource_usage("adam.hip", tmp_path)
+    for frag, lds, min_occ in (("adam_prep_kernel", 3072, 8), ("adam_ema_kernel", 0, 4), ("swap_f32_kernel", 0, 8)):
+        u = the_kernel(usage, frag)
         print(frag, u)
         assert (u["vspill"], u["sspill"], u["scratch"], u["lds"]) == (0, 0, 0, lds) and u["occ"] >= min_occ, (frag, u)
-    assert [v for k, v in usage.items() if "adam_ema_kernel" in k][0]["vgpr"] >= 40
+    assert the_kernel(usage, "adam_ema_kernel")["vgpr"] >= 40
 
 
 # ----------------------------------------------------------------------------- flag

@@ -1,5 +1,5 @@
 """The small kernels of csrc/misc.hip -- bias gradient, L1 / BCE / LSGAN / Sobel losses, activations, add, channel pad / unpad,
-argmax-u8 labels, confusion histogram, segmentation-edge indicator, Adam -- against tests/small_kernels_oracle.py (float64,
+argmax-u8 labels, confusion histogram, segmentation-edge indicator, and Adam (csrc/adam.hip) -- against tests/small_kernels_oracle.py (float64,
 written from include/sggan.h) at the shapes where their chunking, grid-stride loops and vector tails change path.
 
 Exact wherever it can be had: inputs k/8, weights in {0, 0.5, 1} and power-of-two scalar factors make every float32 partial

@@ -5,14 +5,12 @@ import ctypes as C
 import math
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from sggan_amd import _abi as A
+from tests.kernel_resources import kernel_resource_usage, the_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR, B1, B2, EPS = 2e-4, 0.5, 0.999, 1e-7
@@ -151,34 +149,13 @@ def test_guard_entry_points_are_exported_bound_and_validate_on_the_host():
 
 
 def test_guard_kernels_do_not_spill_and_use_no_scratch(tmp_path):
-    """csrc/misc.hip recompiled with -Rpass-analysis=kernel-resource-usage (the method of tests/test_build_resources.py): the
-    three new kernels are in the build with zero VGPR / SGPR spills and no scratch, at full occupancy (8 waves per SIMD: the
+    """csrc/adam.hip recompiled with -Rpass-analysis=kernel-resource-usage (tests/kernel_resources.py): the three kernels of a
+    guarded update are in the build with zero VGPR / SGPR spills and no scratch, at full occupancy (8 waves per SIMD: the
     sum-of-squares pass hides HBM latency with resident blocks), and the two reductions hold their 256 doubles + 256 flags of LDS."""
-    sys.path.insert(0, os.path.join(ROOT, "sg-gan-tf2_amd"))
-    import build as B
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("hipcc not available")
-    r = subprocess.run([hipcc, *B.FLAGS, "-c", os.path.join(B.CSRC, "misc.hip"), "-o", str(tmp_path / "misc.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    pats = (("vspill", r"VGPRs Spill: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-            ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        for key, pat in pats:
-            m = re.search(pat, line)
-            if m and name:
-                usage[name][key] = int(m.group(1))
-    for frag, lds in (("gradsq_partial_kernel", 3072), ("adam_guard_prep_kernel", 3072), ("adam_guard_kernel", 0)):
-        hits = [v for k, v in usage.items() if frag in k]
-        assert len(hits) == 1, f"kernel {frag}: {len(hits)} matches in the build"
-        assert hits[0] == {"vspill": 0, "sspill": 0, "scratch": 0, "occ": 8, "lds": lds}, (frag, hits[0])
+    usage = kernel_resource_usage("adam.hip", tmp_path)
+    for frag, lds in (("gradsq_partial_kernel", 3072), ("adam_prep_kernel", 3072), ("adam_kernel", 0)):
+        u = the_kernel(usage, frag)
+        assert {k: u[k] for k in ("vspill", "sspill", "scratch", "occ", "lds")} == {"vspill": 0, "sspill": 0, "scratch": 0, "occ": 8, "lds": lds}, (frag, u)
 
 
 def test_guard_flags_and_default_arguments():

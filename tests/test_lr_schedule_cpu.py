@@ -1,15 +1,13 @@
 """CPU-side checks of the linear learning-rate decay (--lr_decay): the host statement of the rule
-(kernels.scheduled_lr), the C ABI of sgg_adam_sched, the build resources of csrc/misc.hip and the flag."""
+(kernels.scheduled_lr), the C ABI of sgg_adam_sched, the build resources of csrc/adam.hip and csrc/misc.hip and the flag."""
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from sggan_amd import _abi as A
+from tests.kernel_resources import kernel_resource_usage, the_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -71,32 +69,15 @@ def test_sgg_adam_sched_is_exported_bound_and_validates_on_the_host():
 
 
 def test_misc_kernels_do_not_spill_and_use_no_scratch(tmp_path):
-    """csrc/misc.hip recompiled with -Rpass-analysis=kernel-resource-usage (the method of tests/test_build_resources.py): the new
-    prep kernel is in the build, and it and every other kernel of the file have zero VGPR / SGPR spills and no scratch."""
-    sys.path.insert(0, os.path.join(ROOT, "sg-gan-tf2_amd"))
-    import build as B
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("hipcc not available")
-    r = subprocess.run([hipcc, *B.FLAGS, "-c", os.path.join(B.CSRC, "misc.hip"), "-o", str(tmp_path / "misc.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        for key, pat in (("vspill", r"VGPRs Spill: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                usage[name][key] = int(m.group(1))
-    for frag in ("adam_sched_prep_kernel", "adam_prep_kernel", "adam_iter_kernel", "adam_kernel"):
-        assert any(frag in k for k in usage), f"kernel {frag} not found in the build"
-    assert len(usage) >= 40, sorted(usage)                  # every kernel of the file reported
-    for k, v in usage.items():
-        assert v == {"vspill": 0, "sspill": 0, "scratch": 0}, (k, v)
+    """csrc/adam.hip and csrc/misc.hip recompiled with -Rpass-analysis=kernel-resource-usage (tests/kernel_resources.py): the
+    prep kernel and the scalar update kernel are in the build, each once, and they and every other kernel of the two files have
+    zero VGPR / SGPR spills and no scratch."""
+    adam, misc = kernel_resource_usage("adam.hip", tmp_path), kernel_resource_usage("misc.hip", tmp_path)
+    for frag in ("adam_prep_kernel", "adam_kernel"):
+        the_kernel(adam, frag)
+    assert len(adam) == 5 and len(misc) >= 39, (sorted(adam), sorted(misc))      # every kernel of the files reported
+    for k, v in {**adam, **misc}.items():
+        assert (v["vspill"], v["sspill"], v["scratch"]) == (0, 0, 0), (k, v)
 
 
 # parse_args([]) before --lr_decay existed

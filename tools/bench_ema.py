@@ -1,4 +1,4 @@
-"""Cost of keeping the generator weight average (sgg_adam_ema, csrc/misc.hip) on one MI355X.
+"""Cost of keeping the generator weight average (sgg_adam_ema, csrc/adam.hip) on one MI355X.
 
     python tools/bench_ema.py [--warmup 5] [--runs 20] [--steps 10] [--repeats 5] [--no-step] [--out profiles/ema_bench.txt]
 

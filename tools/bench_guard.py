@@ -1,4 +1,4 @@
-"""Cost of the guarded Adam update (sgg_adam_guard, csrc/misc.hip) beside the plain one (sgg_adam_iter) on one MI355X.
+"""Cost of the guarded Adam update (sgg_adam_guard, csrc/adam.hip) beside the plain one (sgg_adam_iter) on one MI355X.
 
     python tools/bench_guard.py [--warmup 5] [--runs 20] [--out profiles/guard_bench.txt]
 

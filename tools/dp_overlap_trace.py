@@ -23,7 +23,7 @@ print(f"{len(ev)} kernels, {len(cc)} of them RCCL" + (f" / {MARK} stand-ins" if 
 if not cc:
     sys.exit(0)
 # steps: an Adam launch of the last network ends a step; take the LAST complete steps (graph replays) of the trace
-adam = [i for i, e in enumerate(comp) if "adam_iter_kernel" in e[2]]
+adam = [i for i, e in enumerate(comp) if "adam_kernel" in e[2]]
 steps = []
 for a, b in zip(adam[3::4], adam[7::4]):           # 4 networks per step: spans between every 4th Adam launch
     steps.append((comp[a][1], comp[b][1]))
