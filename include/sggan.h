@@ -645,6 +645,25 @@ int sgg_diffaug_fwd(const void* x, void* y, const float* params, int rows, int H
                     void* ws, size_t ws_bytes, void* stream);
 int sgg_diffaug_bwd(const void* dy, const float* params, const void* addend, void* dx, int rows, int H, int W, int C_real,
                     int Cpad, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* ---- training-mode dropout: one in-place launch, used forward (y = m * scale * x) and backward (dx = m * scale * dy,
+ * the same call on the gradient).  The mask is never stored: it is regenerated from counters.
+ * x: dtype (SGG_F32 | SGG_BF16) [n_samples][elems_per_sample], modified in place; elems_per_sample a multiple of 8, the base
+ *   16-byte aligned.  Element i of sample n belongs to vector e = i / 8 and lane j = i % 8:
+ *     r = Philox4x32-10 (the constants of sgg_diffaug_draw), counter (t_lo, t_hi, g, e), key (seed, 1 + stream_id), with
+ *         t = *iterations, int64 on the DEVICE and read when the launch RUNS (the call can be captured; a step counter that
+ *         advances between replays gives new masks), g = (uint32)(sample_offset + n);
+ *     d = (r[j >> 1] >> (16 * (j & 1))) & 0xFFFF;  the element is kept iff d >= threshold.
+ *   Key word 1 is never 0, so no stream coincides with sgg_diffaug_draw's key (seed, 0).  The draw depends on the element index
+ *   alone, never on dtype or launch shape: f32 and bf16 calls drop the same elements.
+ *   threshold = round(rate * 65536) in 0..65535 (the caller's): the drop probability is exactly threshold / 65536.  Kept elements
+ *   are multiplied by scale = 65536.f / (65536 - threshold) -- the product formed in f32 and rounded once to the storage type, to
+ *   nearest even; rate 0.5 gives scale exactly 2 -- dropped ones become +0.  threshold = 0 keeps every bit of x (nothing is launched).
+ *   One 16-byte load and one 16-byte store per vector, no LDS, no atomics, no workspace, no host sync: one launch.
+ * Before any launch -- SGG_EINVAL: NULL x or iterations, a negative count, elems_per_sample % 8 != 0, a misaligned base, threshold
+ *   outside 0..65535, stream_id outside 0..2^28-1, a negative sample_offset, an unknown dtype; SGG_EUNSUPPORTED: elems_per_sample
+ *   > 2^35 (the vector index is a 32-bit counter word) or n_samples > 65535 (the grid's y extent).  n_samples == 0: SGG_OK, no launch. */
+int sgg_dropout(void* x, int64_t n_samples, int64_t elems_per_sample, int threshold, const int64_t* iterations, uint32_t seed,
+                int64_t sample_offset, int stream_id, int dtype, void* stream);
 /* ---- sliced Wasserstein distance of Laplacian-pyramid patches (Karras et al. 2018, section 5; the semantics of
  * PGGAN's metrics/sliced_wasserstein.py [3P-recall]): an unpaired realism score of two image sets.  The sort between
  * sgg_swd_project and sgg_swd_distance is the caller's.

@@ -166,7 +166,8 @@ SIGNATURES = {
     "sgg_diffaug_draw": (_i, [_vp, _i, _vp, C.c_uint32, _i64, _i, _i, _i, _i, _f, _vp]),
     "sgg_diffaug_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_diffaug_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "sgg_swd_pyramid_elems": (_sz, [_i, _i, _i]),
+    "sgg_dropout": (_i, [_vp, _i64, _i64, _i, _vp, C.c_uint32, _i64, _i, _i, _vp]),
+    "sgg_swd_pyramid_elems":(_sz, [_i, _i, _i]),
     "sgg_swd_pyramid_workspace": (_sz, [_i, _i, _i, _i]),
     "sgg_swd_project_workspace": (_sz, [_i64]),
     "sgg_swd_pyramid": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

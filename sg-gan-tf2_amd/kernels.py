@@ -1076,8 +1076,32 @@ def diffaug_bwd(dy, params, C_real, addend=None, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- training-mode dropout (csrc/dropout.hip)
+DROPOUT_THREADS, DROPOUT_CHUNK, DROPOUT_GRID_BLOCKS = 256, 1024, 2048     # DO_THREADS, DO_CHUNK (vectors of 8), DO_GRID_BLOCKS
+
+
+def dropout_threshold(rate) -> int:
+    """round(rate * 65536) clamped to 0..65535: an element is dropped iff its 16-bit draw is below it, probability threshold / 65536."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"dropout rate must lie in [0, 1), got {rate!r}")
+    return min(max(int(round(rate * 65536.0)), 0), 65535)
+
+
+def dropout_(x, rate, iterations, seed, sample_offset, stream_id):
+    """sgg_dropout, in place on x (n_samples, ...): elements dropped with probability ``rate`` become +0, the others are scaled by
+    1 / (1 - rate).  The mask comes from (the step ``iterations``, a 1-element int64 DEVICE tensor, holds when the launch runs;
+    seed; stream_id; sample_offset + row; element index) and from nothing else: the same call on the gradient is the backward."""
+    assert iterations.dtype == torch.int64 and iterations.is_cuda
+    if x.numel():
+        n = x.shape[0]
+        A.check(A.lib().sgg_dropout(_p(x), n, x.numel() // n, dropout_threshold(rate), C.c_void_p(iterations.data_ptr()),
+                                    int(seed) & 0xffffffff, int(sample_offset), int(stream_id), dt(x), _s()), "dropout")
+    return x
+
+
 # ----------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
-SWD_K = 147                      # values of a descriptor: a 7x7 patch of three channels, (channel, y, x)
+SWD_K = 147                     # values of a descriptor: a 7x7 patch of three channels, (channel, y, x)
 SWD_CHUNK = 256                  # descriptor rows per partial sum of the statistics (SW_CHUNK, csrc/swd.hip)
 SWD_MAX_LEVELS = 5
 

@@ -109,6 +109,13 @@ def build_parser():
            "the per-layer vectors are saved with the checkpoint, so it works under --graph, with data parallelism (nothing to "
            "exchange), --use_pool, the guard flags and after --continue_train; with --diffaug the draws stay keyed by the "
            "discriminator's step counter, unchanged.  A checkpoint loads only into a model of the same --d_norm")
+    a("--dropout", dest="dropout", nargs="?", type=float, const=0.5, metavar="RATE", default=argparse.SUPPRESS,
+      help="--generator unet: train the generator(s) with the Dropout layers of generator_unet (d1..d3, between the transposed conv and the "
+           "instance norm) in training mode, at RATE in [0, 1) (bare flag: 0.5, the reference's constant; default: off -- the "
+           "reference's own calls run the generator in inference mode).  The masks are regenerated on the device from the "
+           "generator's step counter, the layer and the global sample index, never stored, so it works under --graph, with data "
+           "parallelism and after --continue_train; the test passes stay in inference mode.  Refused with --generator resnet: that "
+           "network has no dropout layers")
     a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
       help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "
            "class map) pairs and score it against the class map: 'Class Overall Accuracy' ... 'Class Mean IoU' scalars, "

@@ -35,7 +35,8 @@ def default_args(**over):
              fuse_in_stats=True, fuse_in_bwd=False, g_buckets=3, keep_tapes=False, group2=True, d_quad=True,
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
              crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
-             diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0, d_norm="instance")
+             diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0, d_norm="instance",
+             dropout=None)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -66,6 +67,20 @@ class sggan(object):
         # model.py:55-62: --use_resnet picks generator_resnet(), otherwise generator_unet() (the reference's flag-less default)
         self.arch = "resnet" if g("use_resnet", True) else "unet"
         self.cycle = bool(g("cycle", False))
+        # dropout (off by default -- the reference's own calls run the generator in inference mode): the rate of
+        # generator_unet's three Dropout layers (d1..d3, module.py:170-180).  Given, the train step runs the generators in training
+        # mode: each site masks its conv output in place, forward and backward, with a mask regenerated from the generator's own
+        # seed and device step counter, the application (0: the pass over a real batch, 1: the pass over the other generator's
+        # fakes), the layer and the global sample index -- no new state, so graph replay, checkpoints and data parallelism see the
+        # masks of the plain single-device run.  Every other caller (the test passes, generator(x)) stays in inference mode.
+        drop = g("dropout", None)
+        self.dropout = None if drop is None else float(drop)
+        if self.dropout is not None:
+            if not 0.0 <= self.dropout < 1.0:
+                raise ValueError(f"dropout must lie in [0, 1), got {drop!r}")
+            if self.arch == "resnet":
+                raise ValueError("--dropout: generator_resnet has no dropout layers (the reference's are in generator_unet: "
+                                 "--generator unet / use_resnet=False)")
         # d_norm ("instance" is the reference's network): "spectral" builds the discriminators without instance
         # norms and runs every one of their convs on W / sigma(W) -- one power iteration per discriminator per training step
         # (Discriminator.spectral_step, first thing in the step bodies), the gradient transform directly before their Adam
@@ -83,7 +98,9 @@ class sggan(object):
                                            dtype=self.dtype, device=self.device, seed=seed + 1, norm=self.d_norm)   # model.py:54
         def make_generator(in_c, out_c, seed):                  # :56 generator_resnet / :58 generator_unet
             kw = dict(gf_dim=g("ngf", 64), in_c=in_c, out_c=out_c, dtype=self.dtype, device=self.device, seed=seed)
-            return Generator(n_blocks=g("n_blocks", 9), **kw) if self.arch == "resnet" else GeneratorUNet(**kw)
+            if self.arch == "resnet":
+                return Generator(n_blocks=g("n_blocks", 9), **kw)
+            return GeneratorUNet(**kw) if self.dropout is None else GeneratorUNet(dropout=self.dropout, **kw)
         self.generator = make_generator(self.input_c_dim, self.output_c_dim, seed)
         self.beta1 = g("beta1", 0.5)
         self.lr = self.LR
@@ -394,6 +411,14 @@ class sggan(object):
             buf = bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.device)
         return buf
 
+    def _drop(self, application, n):
+        """The keywords that put a U-Net generator's forward into training mode for this application (0: over a real batch, 1:
+        over the other generator's fakes) of a batch of n per rank -- its samples are the global samples rank * n .., exactly
+        as _diffaug_table counts them.  Without the option: none, the forward's launches are the inference ones."""
+        if self.dropout is None:
+            return {}
+        return {"dropout": application, "sample_offset": (self._dp.rank if self._dp is not None else 0) * n}
+
     def _diffaug_table(self, n, H, W, streams):
         """The step's parameter table, n rows per entry of ``streams`` = ((discriminator, which_D, role), ...) in the row order of
         the batch it augments; role 0: reals, 1: fakes.  One draw launch per entry: each reads ITS discriminator's device step
@@ -451,7 +476,7 @@ class sggan(object):
         G.P.zero_grad()
         D.P.zero_grad()
 
-        fake, tG = G.forward(real, out=d_in[N:] if stack else None)         # :175-179 (D2)
+        fake, tG = G.forward(real, out=d_in[N:] if stack else None, **self._drop(0, N))   # :175-179 (D2)
         aug = bool(self.diffaug)
         d_seg, d_fake = seg, fake
         if aug:         # D judges augmented copies; ``seg`` and ``fake`` themselves stay as the L1 term reads them
@@ -601,10 +626,11 @@ class sggan(object):
         Da.spectral_step(); Db.spectral_step()      # (d_norm="spectral": this step's sigma, before their first use)
         C = self.output_c_dim
 
-        fake_B, t1 = Gab.forward(rA)
-        cyc_A, t4 = Gba.forward(fake_B)
-        fake_A, t3 = Gba.forward(rB)
-        cyc_B, t2 = Gab.forward(fake_A)
+        nA = rA.shape[0]
+        fake_B, t1 = Gab.forward(rA, **self._drop(0, nA))
+        cyc_A, t4 = Gba.forward(fake_B, **self._drop(1, nA))
+        fake_A, t3 = Gba.forward(rB, **self._drop(0, nA))
+        cyc_B, t2 = Gab.forward(fake_A, **self._drop(1, nA))
         aug = bool(self.diffaug)
         aBf, aAf, aAr, aBr = fake_B, fake_A, rA, rB                      # what the discriminators judge
         if aug:         # (never with the pool: refused by the constructor)
@@ -737,8 +763,8 @@ class sggan(object):
             net.P.zero_grad()
         Da.spectral_step(); Db.spectral_step()      # (d_norm="spectral": this step's sigma, before their first use)
         C = self.output_c_dim
-        f1, t1 = Gp1.forward(x1, out=dq[n:3 * n] if quad else None)   # [fake_B; fake_A]
-        c2, t2 = Gp2.forward(f1)                              # [cyc_A; cyc_B]
+        f1, t1 = Gp1.forward(x1, out=dq[n:3 * n] if quad else None, **self._drop(0, n))   # [fake_B; fake_A]
+        c2, t2 = Gp2.forward(f1, **self._drop(1, n))          # [cyc_A; cyc_B]
         aug = bool(self.diffaug)
         if aug:         # the discriminators judge augmented copies, rows in the stacked pass's order [real_B; fake_B | fake_A; real_A]
             par = self._diffaug_table(n, shp[1], shp[2], ((Db, 1, 0), (Db, 1, 1), (Da, 0, 1), (Da, 0, 0)))

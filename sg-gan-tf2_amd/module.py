@@ -324,6 +324,7 @@ class _ConvUnit:
     they hold."""
 
     skip_grad = False           # backward returns dx (True: (dx, dskip), the gradient of the skip path as well)
+    drop_layer = None           # a dropout site's layer index (generator_unet d1..d3: 0..2): the mask sits between conv and norm
 
     def __init__(self, net, name, kind, stride=1, padding="VALID", reflect=0, norm=True, act=A.ACT_NONE, leak=0.0):
         self.net, self.name, self.kind = net, name, kind            # kind: "conv" | "deconv"
@@ -369,14 +370,15 @@ class _ConvUnit:
                 self._packed = (key, wf, wd)
         return self._packed[1], self._packed[2]
 
-    def _conv(self, x, out=None):
+    def _conv(self, x, out=None, fuse=True):
         """The convolution alone: (g, xc, part).  part: the per-chunk (sum, sumsq) rows of xc where the launch's epilogue
-        delivers them for the norm behind it (that norm then skips its own statistics pass over the tensor), else None."""
+        delivers them for the norm behind it (that norm then skips its own statistics pass over the tensor), else None.
+        fuse=False (a dropout site in training mode): never -- the epilogue would sum the tensor in front of the mask."""
         P, n = self.net.P, self.name
         assert out is None or not self.norm
         g = self.geom(x)
         wf, wd = self.packed(x.dtype)
-        stats = self.norm and g.stats_chunks and self.net.fuse_in_stats
+        stats = fuse and self.norm and g.stats_chunks and self.net.fuse_in_stats
         if self.kind == "conv" and stats and (self.R != 7 or self.net.fuse_in_stats_stem):
             return (g,) + K.conv_fwd_stats(g, x, wf, P.p(n + "_b"))
         if self.kind == "deconv" and stats and self.net.fuse_in_stats_deconv:
@@ -387,12 +389,25 @@ class _ConvUnit:
             return g, K.conv_fwd(g, x, wf, P.p(n + "_b"), fused_act, self.leak, out=out), None
         return g, K.deconv_fwd(g, x, wd, P.p(n + "_b"), fused_act, self.leak, out=out), None
 
-    def forward(self, x, residual=None, record_only=False, out=None):
+    def dropout_(self, t, drop):
+        """The dropout launch of this site, in place on t (the conv output, or the gradient with respect to the masked tensor):
+        drop = (stream id, sample offset), the mask keyed by this unit's network -- its seed and its device step counter."""
+        K.dropout_(t, self.net.dropout, self.net.P.iterations, self.net.seed, drop[1], drop[0])
+
+    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
         """out: the caller's buffer for the layer output (layers without a norm only: the generator's last layer writes the
         fakes straight into the discriminators' stacked input).
         record_only: the caller only wants the forward record (activation checkpointing re-runs a residual block's second
         conv for its backward pass: the block's output is not needed again) -- where the conv's epilogue delivers the norm's
-        sums, the norm's apply pass is skipped (same statistics, bit for bit) and y is None."""
+        sums, the norm's apply pass is skipped (same statistics, bit for bit) and y is None.
+        drop: (stream id, sample offset) at a dropout site in training mode -- the conv output is masked in place before the
+        norm reads it, and the record grows by ``drop``, which the backward needs to repeat the launch; None: today's launches."""
+        if drop is not None:
+            assert self.norm and not record_only
+            g, xc, _ = self._conv(x, fuse=False)
+            self.dropout_(xc, drop)
+            y, stats = K.instnorm_fwd(xc, *self.affine(), residual, self.net.eps, self.act, self.leak)
+            return y, (g, x, xc, stats, drop)
         g, xc, part = self._conv(x, out)
         if not self.norm:
             return xc, (g, x, xc, None)
@@ -431,7 +446,7 @@ class _ConvUnit:
         produced dy.  next_norm = (unit, rec) of the layer that will consume the returned dx: if its norm's first pass can
         be done in this unit's data-gradient epilogue the call returns (dx, partial) instead of dx."""
         P, n = self.net.P, self.name
-        g, x, xc, stats = rec
+        g, x, xc, stats, *drop = rec
         wf, wd = self.packed(x.dtype)
         if self.norm:
             if param_grads:
@@ -439,10 +454,18 @@ class _ConvUnit:
             else:   # gradients w.r.t. gamma/beta not wanted: send them to scratch
                 dg = db = self.net.scratch_vec(K.cpad(self.cout))
             if dy_partial is not None:
+                assert not drop                     # (a dropout site takes no fused-statistics route)
                 dxc = K.instnorm_bwd_partial(dy, xc, dy_partial, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
             else:
                 dxc = K.instnorm_bwd(dy, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
-            # the conv bias feeds an InstanceNorm: its gradient is identically 0 -> left at 0
+            # the conv bias feeds an InstanceNorm: its gradient is identically 0 -> left at 0 ...
+            if drop:
+                # ... unless a mask sits between them: the norm no longer cancels the bias.  dxc becomes the gradient with respect
+                # to the conv output -- the forward's launch again -- and bias, weight and data gradient are taken from that
+                assert next_norm is None
+                self.dropout_(dxc, drop[0])
+                if param_grads:
+                    K.bias_grad(dxc, P.g(n + "_b", buf=gbuf), accumulate=True)
         else:
             if dy.dtype != xc.dtype:
                 dy = dy.to(xc.dtype)
@@ -477,22 +500,28 @@ class _SkipActUnit(_ConvUnit):
 
     skip_grad = True
 
-    def forward(self, x, residual=None, record_only=False, out=None):
+    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
         assert residual is not None and out is None and not record_only and self.norm
-        g, xc, part = self._conv(x)
+        g, xc, part = self._conv(x, fuse=drop is None)
+        if drop is not None:
+            self.dropout_(xc, drop)
         y, stats = K.instnorm_fwd_skip(xc, *self.affine(), residual, self.net.eps, self.act, self.leak, partial=part)
-        return y, (g, x, xc, stats, y)
+        return y, (g, x, xc, stats, y) + (() if drop is None else (drop,))
 
     def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
         assert addend is None and dy_partial is None and next_norm is None
         P, n = self.net.P, self.name
-        g, x, xc, stats, y = rec
+        g, x, xc, stats, y, *drop = rec
         wf, wd = self.packed(x.dtype)
         if param_grads:
             dg, db = P.g(n + "_g", buf=gbuf), P.g(n + "_beta", buf=gbuf)
         else:
             dg = db = self.net.scratch_vec(K.cpad(self.cout))
         dxc, dskip = K.instnorm_bwd_skip(dy, y, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
+        if drop:                                    # (_ConvUnit.backward: the mask again, then the bias gradient it uncovers)
+            self.dropout_(dxc, drop[0])
+            if param_grads:
+                K.bias_grad(dxc, P.g(n + "_b", buf=gbuf), accumulate=True)
         if param_grads:
             self.weight_grad(g, x, dxc, gbuf)
         if not want_dx:
@@ -509,6 +538,8 @@ class _Net:
         A.lib()                                      # fail loudly if the extension is missing
         self.eps = eps
         self.P = ParamStore(specs, self.device)
+        self.seed = 0 if seed is None else int(seed)     # keys the network's own random draws (dropout masks)
+        self.dropout = 0.0                               # the rate of the network's dropout sites (GeneratorUNet)
         if seed is not None:
             self.P.init_keras(seed)
         self._scratch = None
@@ -696,11 +727,12 @@ class Generator(_ResNetWalk, _Net):
         self.out = U("out", "conv", reflect=3, norm=False, act=A.ACT_TANH)         # :262-265
         self.head, self.tail = [self.c1, self.c2, self.c3], [self.d1, self.d2, self.out]
 
-    def __call__(self, x):
-        """Drop-in for ``self.generator(self.real_A)`` (model.py:175): NHWC float32 in, NHWC float32 out."""
-        return _apply_net(self, x)
+    def __call__(self, x, training=False):
+        """Drop-in for ``self.generator(self.real_A)`` (model.py:175): NHWC float32 in, NHWC float32 out.  training: Keras's
+        keyword -- the U-Net's dropout layers mask (application 0, sample offset 0); a network without dropout layers ignores it."""
+        return _apply_net(self, x, *((True,) if training else ()))
 
-    def _run(self, x):
+    def _run(self, x, training=False):
         y, tape = self.forward(self.to_internal(x))
         return K.unpad_channels(y, self.out_c), tape
 
@@ -717,9 +749,13 @@ class _UNetWalk:
     def conv_units(self):
         return self.enc + self.dec + [self.d8]
 
-    def forward(self, x, out=None):
+    def forward(self, x, out=None, dropout=None, sample_offset=0):
         """x: internal (N,H,W,8).  Returns (fake internal (N,H,W,8), tape); out: buffer for the result.  tape = the layers'
-        forward records in layer order."""
+        forward records in layer order.
+        dropout: None -- inference, the dropout layers are the identity -- or the index of this application of the network within
+        the step (training mode): dropout site l then masks its conv output with draw stream 4 * application + l, sample i of
+        the batch being global sample ``sample_offset`` + i.  Forward and backward of one application must run at the same value
+        of the network's step counter."""
         tape, skips = [], []
         h = x
         for u in self.enc:
@@ -728,7 +764,10 @@ class _UNetWalk:
             skips.append(h)
         skips.pop()                                            # (the innermost output feeds the decoder: no skip)
         for u in self.dec:                                     # d(j) + e(8-j): the skips are consumed innermost first
-            h, r = u.forward(h, residual=skips.pop())
+            if dropout is not None and u.drop_layer is not None:
+                h, r = u.forward(h, residual=skips.pop(), drop=(4 * int(dropout) + u.drop_layer, int(sample_offset)))
+            else:
+                h, r = u.forward(h, residual=skips.pop())
             tape.append(r)
         h, r = self.d8.forward(h, out=out)
         tape.append(r)
@@ -761,22 +800,36 @@ class _UNetWalk:
 class GeneratorUNet(_UNetWalk, _Net):
     """generator_unet (module.py:125-206), the reference's default generator (--use_resnet False): eight 3x3 stride-1 SAME
     Conv2D + IN + LeakyReLU (e8: ReLU), seven 3x3 stride-1 SAME Conv2DTranspose + IN + additive skip from the mirrored
-    encoder layer (d3 / d7: ReLU after the add), and a Conv2DTranspose to the output channels + tanh.  Dropout (d1-d3) is the
-    identity: the reference calls the generator without ``training=`` (model.py:173-178, 347, 561), so Keras runs it in inference mode."""
+    encoder layer (d3 / d7: ReLU after the add), and a Conv2DTranspose to the output channels + tanh.
+
+    Dropout(``dropout``) sits between the Conv2DTranspose and the instance norm of d1, d2 and d3 (module.py:170, 175, 180; the
+    reference's constant, :131, is the default).  In inference mode -- ``generator(x)``, ``forward(x)``: what the reference's own
+    calls run, since it calls the generator without ``training=`` (model.py:173-178, 347, 561) -- the three layers are the
+    identity and nothing is launched for them.  In training mode -- ``generator(x, training=True)``, ``forward(x, dropout=
+    application)`` -- each masks its conv output in place (K.dropout_): the mask is regenerated from (seed, the
+    network's device step counter, application, layer, global sample index, element index) in forward and backward, never
+    stored, and the biases d1_b, d2_b, d3_b get the gradient the norm would otherwise cancel."""
 
     LEAK = 0.3           # tf.keras.layers.LeakyReLU() default alpha
 
-    def __init__(self, gf_dim=64, in_c=3, out_c=3, dtype=torch.bfloat16, device="cuda", eps=1e-3, seed=19):
+    def __init__(self, gf_dim=64, in_c=3, out_c=3, dtype=torch.bfloat16, device="cuda", eps=1e-3, seed=19, dropout=0.5):
         super().__init__(unet_param_specs(gf_dim, in_c, out_c), dtype, device, eps, seed)
         self.in_c, self.out_c = in_c, out_c
+        K.dropout_threshold(dropout)                    # (0 <= rate < 1, else ValueError)
+        self.dropout = float(dropout)
         U = lambda *a, **k: _ConvUnit(self, *a, padding="SAME", **k)
         self.enc = [U(f"e{i}", "conv", act=A.ACT_LRELU, leak=self.LEAK) for i in range(1, 8)] + [U("e8", "conv", act=A.ACT_RELU)]
         self.dec = [(_SkipActUnit(self, f"d{i}", "deconv", stride=1, act=A.ACT_RELU) if i in (3, 7) else
                      U(f"d{i}", "deconv", stride=1, act=A.ACT_NONE)) for i in range(1, 8)]
         self.d8 = U("d8", "deconv", stride=1, norm=False, act=A.ACT_TANH)
+        for layer, u in enumerate(self.dec[:3]):        # d1, d2, d3: the dropout sites (:170, :175, :180)
+            u.drop_layer = layer
+
+    def _run(self, x, training=False):
+        y, tape = self.forward(self.to_internal(x), dropout=0 if training else None)
+        return K.unpad_channels(y, self.out_c), tape
 
     __call__ = Generator.__call__
-    _run = Generator._run
     _run_backward = Generator._run_backward
 
 
@@ -965,10 +1018,31 @@ class _PairUnit:
 
     skip_grad = False
 
-    def _conv(self, x, out=None):
+    @property
+    def drop_layer(self):
+        return self.ua.drop_layer
+
+    def dropout_(self, t, drop):
+        """_ConvUnit.dropout_ per half of the stacked tensor t: each network masks its own images with its own seed and step
+        counter (two launches), exactly the launches of the one-network-at-a-time step."""
+        n = t.shape[0] // 2
+        self.ua.dropout_(t[:n], drop)
+        self.ub.dropout_(t[n:], drop)
+
+    def _bias_grads(self, dxc):
+        """The bias gradients a dropout site's mask uncovers, as the units without a norm take theirs (bit-identical per half)."""
+        ua, ub = self.ua, self.ub
+        n = dxc.shape[0] // 2
+        if ua.net.group2:
+            K.bias_grad_group2(dxc, ua.net.P.g(ua.name + "_b"), ub.net.P.g(ub.name + "_b"), accumulate=True)
+        else:
+            for u, sl in ((ua, slice(0, n)), (ub, slice(n, 2 * n))):
+                K.bias_grad(dxc[sl], u.net.P.g(u.name + "_b"), accumulate=True)
+
+    def _conv(self, x, out=None, fuse=True):
         """The convolution of both halves into one stacked output: (g, xc, part, one_launch).  part: the per-chunk (sum, sumsq)
         rows of xc where the launch's epilogue delivers them for the norm behind it, else None; one_launch: they came from the
-        stacked launch of the two networks' 3x3 halo kernel."""
+        stacked launch of the two networks' 3x3 halo kernel.  fuse=False (a dropout site in training mode): part is None."""
         ua, ub = self.ua, self.ub
         assert out is None or not ua.norm
         n = x.shape[0] // 2
@@ -978,21 +1052,22 @@ class _PairUnit:
         PA, PB = ua.net.P, ub.net.P
         fused_act = A.ACT_NONE if ua.norm else ua.act
         g2 = ua.geom(x) if ua.kind == "conv" else None     # geometry of the stacked batch
-        if ua.kind == "conv" and ua.norm and g.stats_chunks and ua.net.fuse_in_stats and g2.pair_ok:
+        fuse = fuse and ua.net.fuse_in_stats
+        if ua.kind == "conv" and ua.norm and g.stats_chunks and fuse and g2.pair_ok:
             # one launch for both networks (per-image weights): 512 blocks, the second round's halo loads run under the
             # first round's stores
             wfa, _ = ua.packed(x.dtype)
             wfb, _ = ub.packed(x.dtype)
             xc, part = K.conv_fwd_stats_pair(g2, x, wfa, PA.p(na + "_b"), wfb, PB.p(nb + "_b"), n)
             return g, xc, part, True
-        if ua.kind == "conv" and ua.norm and g.stats_chunks and ua.net.fuse_in_stats and (ua.R != 7 or ua.net.fuse_in_stats_stem):
+        if ua.kind == "conv" and ua.norm and g.stats_chunks and fuse and (ua.R != 7 or ua.net.fuse_in_stats_stem):
             xc = torch.empty((2 * n,) + tuple(g.y_shape[1:]), dtype=x.dtype, device=x.device)
             part = torch.empty((2 * n, g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x.device)
             for u, sl in halves:
                 wf, _ = u.packed(x.dtype)
                 K.conv_fwd_stats(g, x[sl], wf, u.net.P.p(u.name + "_b"), out=xc[sl], out_partial=part[sl])
             return g, xc, part, False
-        if ua.kind == "deconv" and ua.norm and ua.net.fuse_in_stats and ua.net.fuse_in_stats_deconv and ua.net.group2:
+        if ua.kind == "deconv" and ua.norm and fuse and ua.net.fuse_in_stats_deconv and ua.net.group2:
             gs = ua.geom(x)                                    # the stacked batch: per-image weights in the stride-2 halo kernel
             if gs.stats_chunks:
                 _, wda = ua.packed(x.dtype)
@@ -1016,9 +1091,15 @@ class _PairUnit:
             xc = K.deconv_fwd_group2(g, x, wda, PA.p(na + "_b"), wdb, PB.p(nb + "_b"), fused_act, ua.leak, out=out)
         return g, xc, None, False
 
-    def forward(self, x, residual=None, record_only=False, out=None):
+    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
         ua, ub = self.ua, self.ub
         n = x.shape[0] // 2
+        if drop is not None:                        # (_ConvUnit.forward: mask the conv output in place, then the plain norm)
+            assert ua.norm and not record_only
+            g, xc, _, _ = self._conv(x, fuse=False)
+            self.dropout_(xc, drop)
+            y, stats = K.instnorm_fwd_pair(xc, *self.affine(), n, residual, ua.net.eps, ua.act, ua.leak)
+            return y, (g, x, xc, stats, drop)
         g, xc, part, one_launch = self._conv(x, out)
         if not ua.norm:
             return xc, (g, x, xc, None)
@@ -1050,13 +1131,19 @@ class _PairUnit:
         sums (fuse_in_bwd has no paired form: partial is None), and mixed mode runs one network at a time."""
         ua, ub = self.ua, self.ub
         assert gbuf is None and dy_partial is None and not (ua.net.mixed or ub.net.mixed)
-        g, x, xc, stats = rec
+        g, x, xc, stats, *drop = rec
         n = x.shape[0] // 2
         na, nb = ua.name, ub.name
         PA, PB = ua.net.P, ub.net.P
         if ua.norm:
             dxc = K.instnorm_bwd_pair(dy, xc, *self.affine(), n, stats, *self._norm_grads(param_grads), param_grads, ua.act, ua.leak)
-            # (the conv bias in front of an instance norm has an identically zero gradient: left at 0)
+            # (the conv bias in front of an instance norm has an identically zero gradient: left at 0 -- unless a mask sits
+            # between them, _ConvUnit.backward)
+            if drop:
+                assert next_norm is None
+                self.dropout_(dxc, drop[0])
+                if param_grads:
+                    self._bias_grads(dxc)
         else:
             dxc = K.act_bwd(dy, xc, ua.act, ua.leak) if ua.act != A.ACT_NONE else dy
             if param_grads and ua.net.group2:
@@ -1116,19 +1203,25 @@ class _PairSkipActUnit(_PairUnit):
 
     skip_grad = True
 
-    def forward(self, x, residual=None, record_only=False, out=None):
+    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
         assert residual is not None and out is None and not record_only and self.ua.norm
         ua = self.ua
-        g, xc, part, _ = self._conv(x)
+        g, xc, part, _ = self._conv(x, fuse=drop is None)
+        if drop is not None:
+            self.dropout_(xc, drop)
         y, stats = K.instnorm_fwd_skip_pair(xc, *self.affine(), x.shape[0] // 2, residual, ua.net.eps, ua.act, ua.leak, partial=part)
-        return y, (g, x, xc, stats, y)
+        return y, (g, x, xc, stats, y) + (() if drop is None else (drop,))
 
     def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
         assert gbuf is None and addend is None and dy_partial is None and next_norm is None
         ua = self.ua
-        g, x, xc, stats, y = rec
+        g, x, xc, stats, y, *drop = rec
         dxc, dskip = K.instnorm_bwd_skip_pair(dy, y, xc, *self.affine(), x.shape[0] // 2, stats, *self._norm_grads(param_grads),
                                               param_grads, ua.act, ua.leak)
+        if drop:
+            self.dropout_(dxc, drop[0])
+            if param_grads:
+                self._bias_grads(dxc)
         return self._conv_backward(g, x, dxc, want_dx, param_grads, None), dskip
 
 
@@ -1181,8 +1274,9 @@ class _NetFn(torch.autograd.Function):
     callers like model.py:170-197).  The training loop of ``sggan`` does not go through this."""
 
     @staticmethod
-    def forward(ctx, net, mask, x, *params):
-        y, tape = net._run(x) if mask is None else net._run(x, mask)
+    def forward(ctx, net, run_args, x, *params):
+        """run_args: what the network's ``_run`` takes beside x -- (mask,) for a discriminator, () or (training,) for a generator."""
+        y, tape = net._run(x, *run_args)
         ctx.net, ctx.tape = net, tape
         return y
 
@@ -1196,14 +1290,14 @@ class _NetFn(torch.autograd.Function):
         return (None, None, dx) + grads
 
 
-def _apply_net(net, x, mask=None):
+def _apply_net(net, x, *run_args):
     x = torch.as_tensor(x)
     if x.device != net.device:
         x = x.to(net.device)
     params = net.trainable_variables
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        return _NetFn.apply(net, mask, x, *params)
-    y, _ = net._run(x) if mask is None else net._run(x, mask)
+        return _NetFn.apply(net, run_args, x, *params)
+    y, _ = net._run(x, *run_args)
     return y
 
 
