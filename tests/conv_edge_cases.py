@@ -137,7 +137,43 @@ ROWS = [
     # transposed conv
     # outside s2halo: odd sizes, channel tails
     ("deconv_ragged", "deconv", 3, 2, "SAME", 24, 40, 2, 5, 7, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 34560), "f32": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 34560)}),
+    # stride-1 transposed conv (the U-Net's d1-d8): the forward is the halo GEMM in its data-gradient direction WITH a bias and an
+    # activation, the data gradient the forward GEMM, the weight gradient the conv's with x in the conv-output role
+    ("tconv1_halo3_min", "deconv", 3, 1, "SAME", 64, 64, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "WGRAD_128x64", 294912)}),
+    # odd batch, two column tiles, destination tail of 8 forward
+    ("tconv1_halo3_n3_dtail", "deconv", 3, 1, "SAME", 64, 264, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64+SPLITK", "WGRAD_128x64", 10948608)}),
+    # the tail on the data-gradient side
+    ("tconv1_halo3_src264", "deconv", 3, 1, "SAME", 264, 64, 1, 4, 128, {"bf16": ("GLDS_128x64+SPLITK", "HALO3", "WGRAD_V2_ROWFAST", 2433024)}),
+    # HALO3 both ways with Cin != Cout: two source chunks, destination tail of 64 in the second 256 tile
+    ("tconv1_halo3_pair_n3", "deconv", 3, 1, "SAME", 128, 320, 3, 4, 256, {"bf16": ("HALO3", "HALO3", "W9", 35389440)}),
+    # the U-Net's widest layer: eight source chunks
+    ("tconv1_halo3_c512", "deconv", 3, 1, "SAME", 512, 512, 1, 4, 128, {"bf16": ("HALO3", "HALO3", "W9", 37748736)}),
+    # d8: 3 (8) destination channels forward
+    ("tconv1_head_c3", "deconv", 3, 1, "SAME", 64, 3, 3, 6, 256, {"bf16": ("HALO3", "GLDS_128x64", "WGRAD_128x64", 331776), "f32": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x64", 331776)}),
+    # d8 off the halo kernel
+    ("tconv1_head_ragged", "deconv", 3, 1, "SAME", 64, 3, 2, 9, 65, {"bf16": ("GLDS_256x16", "GLDS_128x64", "WGRAD_128x64", 92160), "f32": ("GLDS_256x16+SPLITK", "GLDS_128x64", "WGRAD_128x64", 92160)}),
+    ("tconv1_out_h5", "deconv", 3, 1, "SAME", 64, 64, 1, 5, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 442368)}),   # outside: odd H
+    ("tconv1_out_w120", "deconv", 3, 1, "SAME", 64, 64, 1, 4, 120, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 294912)}),   # outside: W one granule short of the tile
+    ("tconv1_out_c72", "deconv", 3, 1, "SAME", 72, 72, 1, 4, 128, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 373248)}),   # outside: 72 source channels in both directions
+    # split-K both ways with a bias behind the reduce
+    ("tconv1_splitk", "deconv", 3, 1, "SAME", 152, 264, 2, 5, 13, {"bf16": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128", 1444608), "f32": ("GLDS_128x128+SPLITK", "GLDS_128x128+SPLITK", "WGRAD_128x128", 1444608)}),
+    ("tconv1_ragged", "deconv", 3, 1, "SAME", 24, 40, 2, 5, 7, {"bf16": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 34560), "f32": ("GLDS_128x64", "GLDS_128x64", "WGRAD_128x64", 34560)}),
+    # W9 with the operand roles swapped (x plays the conv-output side): one split with H = 2's mirrored rows; two slabs, so the grouped
+    # call shares a launch; 35 slabs
+    ("tconv1_w9_min", "deconv", 3, 1, "SAME", 128, 64, 1, 2, 64, {"bf16": ("GLDS_128x64+SPLITK", "GLDS_128x128", "W9", 294912)}),
+    ("tconv1_w9_two_splits", "deconv", 3, 1, "SAME", 128, 64, 1, 4, 64, {"bf16": ("GLDS_128x64+SPLITK", "GLDS_128x128", "W9", 589824)}),
+    ("tconv1_w9_odd_splits", "deconv", 3, 1, "SAME", 128, 64, 5, 4, 448, {"bf16": ("GLDS_128x64+SPLITK", "GLDS_128x128", "W9", 10321920)}),
 ]
+# The routes of the U-Net generator's own layer shapes in bf16 (3x3, stride 1, SAME; conv e1-e8, transposed conv d1-d8; e5-e8 and d1-d4
+# share one shape, 512 -> 512), at N8 128x128 and at N8 256x512 alike: a predicate narrowed for an edge row cannot move one unnoticed.
+UNET_SIZES = [(8, 128, 128), (8, 256, 512)]
+UNET_ROUTES = {
+    "e1": ("conv", 3, 64, ("HALO_NARROW_IN", "HALO_DGRAD_NARROW", "WGRAD_128x64")), "e2": ("conv", 64, 128, ("HALO3", "HALO3", "W9")),
+    "e3": ("conv", 128, 256, ("HALO3", "HALO3", "W9")), "e4": ("conv", 256, 512, ("HALO3", "HALO3", "W9")),
+    "e5": ("conv", 512, 512, ("HALO3", "HALO3", "W9")), "d1": ("deconv", 512, 512, ("HALO3", "HALO3", "W9")),
+    "d5": ("deconv", 512, 256, ("HALO3", "HALO3", "W9")), "d6": ("deconv", 256, 128, ("HALO3", "HALO3", "W9")),
+    "d7": ("deconv", 128, 64, ("HALO3", "HALO3", "W9")), "d8": ("deconv", 64, 3, ("HALO3", "GLDS_128x64", "WGRAD_128x64")),
+}
 # The weight-gradient workspace of the bench workload's layers (tests/test_gpu_exact.LAYERS, bf16), recorded like the rows' from the
 # library before its launch layer was given one plan: a planner edit cannot move a production layer's slab count unnoticed.
 BENCH_WS_WGRAD = {
@@ -169,6 +205,10 @@ WS_FWD_DGRAD = {
     "w9_odd_splits": {"bf16": (0, 19543040)}, "w9_out_odd_h": {"bf16": (0, 1474560)}, "rowfast_valid": {"bf16": (0, 1824768)},
     "rowfast_7x7": {"bf16": (0, 10196992)}, "rowfast_f32_wo32": {"bf16": (0, 368640), "f32": (0, 655360)}, "wgrad_v2_wo63": {"bf16": (0, 580608)},
     "wgrad_v2_wo65": {"bf16": (0, 599040)}, "wgrad_128x128_cr3": {"bf16": (0, 15840), "f32": (0, 28512)},
+    # (a transposed conv's forward is the data-gradient GEMM: tconv1_splitk holds splitk_dgrad_dc264's two values the other way round)
+    "tconv1_halo3_n3_dtail": {"bf16": (0, 9437184)}, "tconv1_halo3_src264": {"bf16": (1179648, 0)}, "tconv1_head_c3": {"f32": (589824, 0)},
+    "tconv1_head_ragged": {"f32": (149760, 0)}, "tconv1_splitk": {"bf16": (686400, 711360), "f32": (1372800, 1264640)},
+    "tconv1_w9_min": {"bf16": (131072, 0)}, "tconv1_w9_two_splits": {"bf16": (262144, 0)}, "tconv1_w9_odd_splits": {"bf16": (9175040, 0)},
     # the bench layers
     "G.res_3x3_256": {"bf16": (0, 14008320)}, "G.c1_7x7_3_64": {"bf16": (0, 17371648)}, "G.out_7x7_64_3": {"bf16": (0, 28675584)},
     "D.h31_s2v_512": {"bf16": (22855680, 0)}, "D.h32_s2v_512": {"bf16": (17203200, 15237120)}, "D.h33_s1v_512": {"bf16": (13844480, 17203200)},
@@ -191,6 +231,7 @@ DX_ROUNDS_ONCE = {"rowfast_7x7"}
 #   normload_ok: halo3_normload_out_c576 (C = 576 > H3_NORM_MAXC) keeps stats_chunks = 4 and loses normload_ok; the SAME rows have none
 #   pair_ok:     halo3_min_* (N = 1); halo3_n3_dtail_* and halo3_dgrad_dtail_* (HALO3 in one direction only, the other splits K)
 #   deconv stats_chunks: 0 in f32 (s2halo_min_deconv's f32 geometry, test_conv_edges_cpu.py) and outside s2halo_ok (deconv_ragged)
+#   a stride-1 transposed conv (every tconv1_* row) has no statistics epilogue and no paired form, on HALO3 or off it: NO_FUSED
 NO_FUSED = (0, 0, False, False, False)
 ELIGIBLE = {
     "halo3_min_reflect": (4, 4, False, True, True), "halo3_min_same": (4, 4, False, False, True),
@@ -314,7 +355,9 @@ FRAC = {"bf16": 7, "f32": 12}
 # above misses a discrimination floor of test_conv_edges_cpu.py -- s2n_wo130: 23.7 % of y change under store (floor 25 %);
 # wgrad_128x16_kr3: 21.8 % of dx (floor 25 %).  Their draw has no zeros in x and dy and no weight below 1/2: |w| < 1/2 is moved to
 # |w| + 1/2.  (The other 3-channel rows keep the common draw: wgrad_128x128_cr3 25.1 % of y, wgrad_128x64_cr3 10.4 % from truncation.)
-ROUND_THIN = {"s2n_wo130", "wgrad_128x16_kr3"}
+# The same on d8's shape as a transposed conv (3 real OUTPUT channels: 27 terms per element of dx) -- tconv1_head_c3: 21.0 % of dx,
+# tconv1_head_ragged: 21.7 %.
+ROUND_THIN = {"s2n_wo130", "wgrad_128x16_kr3", "tconv1_head_c3", "tconv1_head_ragged"}
 # REFLECT rows whose bf16 data gradient is a narrow halo kernel on zero padding plus conv_border_fold_kernel, which rounds a second time
 FOLD_TWICE = ["narrow5_in16_reflect", "head7_16x32"]
 
@@ -484,7 +527,11 @@ GROUP2 = ["glds_256x256_fwd_ragged", "glds_256x128_3stage", "glds_128x128_long_k
           "halo3_min_same", "halo3_n3_dtail_same", "halo3_n3_dtail_reflect", "halo3_dgrad_dtail_reflect",
           "s2halo_min", "s2halo_min_deconv", "s2halo_deconv_n3", "s2n_wo5", "s2n_wo130",
           "head7_ragged", "head7_16x32", "stem7_16x32", "stem7_17x33", "narrow5_16x32", "narrow5_in16_16x32", "narrow5_in16_reflect",
-          "deconv_ragged", "wgrad_128x64_cr3"]
+          "deconv_ragged", "wgrad_128x64_cr3",
+          # stride-1 transposed convs: the stacked HALO3 launch in the data-gradient direction WITH a bias per image (forward) and in the
+          # forward direction without one (data gradient), the generic GEMM's one launch on the other side of each, d8's 8 channels
+          "tconv1_halo3_pair_n3", "tconv1_halo3_c512", "tconv1_halo3_n3_dtail", "tconv1_halo3_src264", "tconv1_head_c3", "tconv1_splitk",
+          "tconv1_ragged"]
 GROUP2_CASES = [(BY_NAME[n], dt) for n in GROUP2 for dt in BY_NAME[n][10]]
 TWO_NETWORK = sorted({n for n, _ in PAIRED + DECONV_STATS} | set(GROUP2) | {"halo3_pair_n3_reflect"})
 

@@ -28,6 +28,11 @@ def test_every_route_is_pinned_by_a_row():
     assert split and not any(r.startswith(("HALO", "S2", "N7", "W")) for r in split)     # only the generic GEMM tiles split K
 
 
+# the slab count of the W9 rows that are there for it (a transposed conv's weight gradient is the conv's with x and dy swapped: the
+# same tiles, the same splits)
+W9_SPLITS = {"w9_two_splits": 2, "w9_odd_splits": 35, "tconv1_w9_min": 1, "tconv1_w9_two_splits": 2, "tconv1_w9_odd_splits": 35}
+
+
 @pytest.mark.parametrize("row", E.ROWS, ids=E.ROW_IDS)
 def test_row_keeps_its_weight_gradient_plan(row):
     """The planner's answer for the row -- the workspace the table records, i.e. its slab count -- and the precondition of the
@@ -40,10 +45,20 @@ def test_row_keeps_its_weight_gradient_plan(row):
             slab = 9 * g.desc.C * g.desc.K * 4                   # one f32 slab of dW per split: the workspace is the split count
             sp, tiles = g.ws_wgrad // slab, g.desc.N * (g.desc.H // 2) * (g.desc.W // 64)
             assert g.ws_wgrad == sp * slab and 1 <= sp <= tiles, (row[0], sp, tiles)
-            if row[0] in ("w9_two_splits", "w9_odd_splits"):
-                assert sp == (2 if row[0] == "w9_two_splits" else 35)
+            if row[0] in W9_SPLITS:
+                assert sp == W9_SPLITS[row[0]]
         assert 2 * g.desc.N * g.desc.Ho * g.desc.Wo <= 2 ** 24
     assert E.BY_NAME["w9s_two_splits"][10]["bf16"][3] == 2 * E.BY_NAME["w9s_min"][10]["bf16"][3]      # two slabs against one
+
+
+def test_transposed_rows_that_share_a_grouped_weight_gradient_launch():
+    """The slab count of each transposed row of the two-network weight-gradient test and whether its two networks run in one launch
+    (W9: an even count; the LDS-DMA kernel: two slabs or more), from the workspace -- host only, so asserted here as well."""
+    from tests import test_gpu_conv_edges as GE          # (module level: lists only, nothing touches a device)
+    assert set(GE.TCONV1_SLABS) == {n for n in GE.GROUPED if n.startswith("tconv1_")}
+    for name, exp in GE.TCONV1_SLABS.items():
+        assert GE.shares_the_launch(E.geom(E.BY_NAME[name], "bf16")) == exp, name
+    assert {s for s, _ in GE.TCONV1_SLABS.values()} >= {1, 2, 35}
 
 
 def test_bench_layers_keep_their_weight_gradient_plan():
@@ -104,24 +119,40 @@ def test_bench_layers_keep_their_routes():
         assert E.routes(E.geom(l + ({},), "bf16")) == exp[l[0]], l[0]
 
 
+def test_unet_layers_keep_their_routes():
+    """The same for the U-Net generator's own layers in bf16 (conv_edge_cases.UNET_ROUTES), at both sizes: e1 on the narrow-input
+    kernels, e2-e8 and d1-d7 on HALO3 / HALO3 / W9, d8's forward on HALO3 with 8 destination channels.  No transposed layer has a
+    fused form."""
+    assert set(E.UNET_ROUTES) == {"e1", "e2", "e3", "e4", "e5", "d1", "d5", "d6", "d7", "d8"} and E.UNET_SIZES == [(8, 128, 128), (8, 256, 512)]
+    for n, h, w in E.UNET_SIZES:
+        for name, (kind, ci, co, exp) in E.UNET_ROUTES.items():
+            g = E.geom((name, kind, 3, 1, "SAME", ci, co, n, h, w, {}), "bf16")
+            assert E.routes(g) == exp, (name, n, h, w, E.routes(g))
+            assert kind == "conv" or E.eligible(g) == E.NO_FUSED, (name, E.eligible(g))
+
+
 def _ktiles(g, mode):
-    """K-tile count and split factor of a zero-padded conv's forward (0) / data-gradient (1) GEMM: plan_conv's arithmetic, and
-    its workspace (one f32 slab of the result per split, nothing else)."""
+    """K-tile count and split factor of a zero-padded layer's forward (0) / data-gradient (1) GEMM: plan_conv's arithmetic, and
+    its workspace (one f32 slab of the result per split, nothing else).  A transposed conv's forward is the data-gradient GEMM of its
+    descriptor (the equivalent conv) and its data gradient the forward GEMM."""
     d, vec = g.desc, 8 if g.dtype == torch.bfloat16 else 4
-    assert not g.is_deconv and d.pad_mode == A.PAD_ZERO and d.stride == 1
-    if mode == 0:
-        return (d.R * d.S * (d.C // vec) + 7) // 8, g.ws_fwd // (d.N * d.Ho * d.Wo * d.K * 4)
-    return (d.R * d.S * (d.K // vec) + 7) // 8, g.ws_dgrad // (d.N * d.H * d.W * d.C * 4)
+    assert d.pad_mode == A.PAD_ZERO and d.stride == 1
+    ws = g.ws_fwd if mode == 0 else g.ws_dgrad
+    if (mode == 0) != g.is_deconv:
+        return (d.R * d.S * (d.C // vec) + 7) // 8, ws // (d.N * d.Ho * d.Wo * d.K * 4), d.K
+    return (d.R * d.S * (d.K // vec) + 7) // 8, ws // (d.N * d.H * d.W * d.C * 4), d.C
 
 
-@pytest.mark.parametrize("name,mode", [("splitk_fwd_dc40", 0), ("splitk_dgrad_dc40", 1), ("splitk_fwd_dc264", 0), ("splitk_dgrad_dc264", 1)])
+@pytest.mark.parametrize("name,mode", [("splitk_fwd_dc40", 0), ("splitk_dgrad_dc40", 1), ("splitk_fwd_dc264", 0), ("splitk_dgrad_dc264", 1),
+                                       ("tconv1_splitk", 0), ("tconv1_splitk", 1)])
 def test_split_k_rows_leave_a_remainder(name, mode):
     """The split-K rows' K-tile count is not divisible by the split factor, so the last split is shorter than the others."""
     row = E.BY_NAME[name]
     for dtype in row[10]:
         g = E.geom(row, dtype)
-        assert (g.desc.C if mode else g.desc.K) == (40 if "dc40" in name else 264)
-        ktot, ks = _ktiles(g, mode)
+        assert E.row_routes(row, dtype)[mode].endswith("+SPLITK")
+        ktot, ks, DC = _ktiles(g, mode)
+        assert DC == ({0: 264, 1: 152}[mode] if name == "tconv1_splitk" else 40 if "dc40" in name else 264)
         assert ks >= 2 and ktot % ks != 0, (name, dtype, ktot, ks)
 
 
@@ -137,8 +168,16 @@ def test_row_is_exact_and_not_trivial(row):
         assert np.abs(e.dx).max() <= 256
     assert np.abs(e.dw).max() < 2 ** 24 and np.abs(e.db).max() < 2 ** 24
     assert np.abs(e.y).max() >= 8 and np.abs(e.dw).max() >= 8
+    if row[0].startswith("tconv1_"):                     # (measured: |y| <= 206 and |dx| <= 197, both on tconv1_halo3_c512)
+        assert np.abs(e.dw).max() >= 20
     for a in (e.y, e.dx, e.dw, e.db):
         assert np.array_equal(a, np.round(a))
+
+
+def test_rows_whose_data_gradient_rounds_once():
+    """The rows compared after one rounding of dx instead of as exact integers: rowfast_7x7 alone, no stride-1 transposed conv."""
+    assert E.DX_ROUNDS_ONCE == {"rowfast_7x7"} and E.DX_ROUNDS_ONCE <= set(E.BY_NAME)
+    assert sum(r[0].startswith("tconv1_") for r in E.ROWS) == 15
 
 
 def _perturbed(row, e, how):
@@ -176,6 +215,41 @@ def test_exact_comparison_sees_what_the_bf16_tolerance_misses(name, how):
         close(E.store(p.y, torch.bfloat16), E.store(e.y, torch.bfloat16), torch.bfloat16, "y with an input channel missing")   # passes
 
 
+@pytest.mark.parametrize("how", ["channel", "tap", "other_bias"])
+def test_exact_comparison_sees_a_transposed_conv_fault(how):
+    """The same in the transposed direction, on tconv1_halo3_pair_n3 (128 -> 320, N3): the oracle with one input channel zeroed, with
+    one tap zeroed, and with image 3 given network B's bias -- what a lockstep forward with a wrong per-image bias pick computes.
+    The exact comparison reports each: in y, and in dw (channel) or dx (tap).  Measured against close() of test_gpu_ops.py (2e-2 of the
+    tensor's maximum, max |y| = 111): at this width it reports all three as well -- the missing channel moves y by up to 9 (8.1 %),
+    the tap by up to 36 (32 %), the bias by up to 4 (3.6 %) -- so what it cannot see here is the smaller share of each: one tap of one
+    channel (at most 1), and the other network's bias wherever the two differ by 2 or less, 239 of the 320 channels of this draw
+    (1.8 % of the maximum): a swap confined to those channels, or a pair of networks whose biases are that close, passes it."""
+    from tests.test_gpu_ops import close
+    name = "tconv1_halo3_pair_n3"
+    row = E.BY_NAME[name]
+    e, eb = E.expected(name), E.expected_b(name)
+    bf = torch.bfloat16
+    assert row[1] == "deconv" and row[7] == 3 and np.abs(e.y).max() == 111
+    if how == "other_bias":
+        y = e.y.copy()
+        y[2] += eb.b - e.b
+        step = np.abs(eb.b - e.b)
+        assert step.max() == 4 and int((step / 111 < 2e-2).sum()) == 239 and int((step > 0).sum()) > 256
+        assert not np.array_equal(y[2], e.y[2]) and np.array_equal(y[:2], e.y[:2])
+    else:
+        p = _perturbed(row, e, how)
+        y = p.y
+        assert E.mismatch(*((p.dx, e.dx) if how == "tap" else (p.dw, e.dw))) is not None
+    assert E.mismatch(E.store(y, bf), E.store(e.y, bf)) is not None
+    assert np.abs(y - e.y).max() == {"channel": 9, "tap": 36, "other_bias": 4}[how]
+    with pytest.raises(AssertionError):                  # the tolerance reports it too, at the tensor's maximum
+        close(E.store(y, bf), E.store(e.y, bf), bf, f"y with {how}")
+    if how == "other_bias":                              # ... and not where the two biases differ by 2 or less
+        small = step <= 2
+        close(E.store(y, bf)[..., small], E.store(e.y, bf)[..., small], bf, "y with the other bias, close channels", scale=111.0)
+        assert E.mismatch(E.store(y, bf)[..., small], E.store(e.y, bf)[..., small]) is not None
+
+
 # ------------------------------------------------------------------------------------------------------------ fused forms
 @pytest.mark.parametrize("row", E.ROWS, ids=E.ROW_IDS)
 def test_row_keeps_its_fused_forms(row):
@@ -204,6 +278,15 @@ def test_first_shape_outside_each_fused_predicate():
     # transposed conv statistics: bf16 inside s2halo_ok only
     assert el("s2halo_min_deconv")[0] == 1 and el("s2halo_deconv_n3")[0] == 4
     assert el("s2halo_min_deconv", "f32")[0] == 0 and el("deconv_ragged")[0] == 0
+    # ... and never at stride 1, on the halo kernel or off it, nor a paired form: the same shape as a conv has both
+    for row in E.ROWS:
+        if row[0].startswith("tconv1_"):
+            assert row[1] == "deconv" and row[3] == 1 and E.row_eligible(row, "bf16") == E.NO_FUSED
+            for dtype in ("bf16", "f32"):
+                g = E.geom(row, dtype)
+                assert g.stats_chunks == 0 and not g.pair_ok, (row[0], dtype)
+    assert E.row_routes(E.BY_NAME["tconv1_halo3_pair_n3"], "bf16")[:2] == ("HALO3", "HALO3")
+    assert el("halo3_pair_n3_same")[0] > 0 and el("halo3_pair_n3_same")[2]
     # the fused rows' lists hold what the issue names
     assert set(E.STATS_FWD) >= {"halo3_n3_dtail_reflect", "halo3_n3_dtail_same", "stem7_16x32", "stem7_32x64_n2"}
     assert set(E.STATS_BWD) >= {"halo3_dgrad_dtail_reflect", "halo3_dgrad_dtail_same"}
@@ -351,6 +434,7 @@ def _draws():
     d = [(r[0], dt, "") for r, dt in RD.CASES_AB]
     d += [(n, "bf16", "") for n in E.STATS_FWD + E.STATS_BWD + [n for n, _ in E.DECONV_STATS]]
     d += [(n, "bf16", "/B") for n, k in E.DECONV_STATS if k]
+    d += [(n, "bf16", "/B") for n in RD.GROUPED_FWD]     # network B of the grouped transposed forward
     return list(dict.fromkeys(d))
 
 

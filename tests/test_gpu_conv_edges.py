@@ -64,7 +64,11 @@ FUSED = ["glds_256x256_fwd_ragged", "glds_256x256_dgrad", "glds_256x128_3stage",
          "s2halo_min", "s2halo_min_deconv", "s2n_wo130", "head7_ragged", "stem7_16x32", "stem7_17x33", "narrow5_16x32",
          "narrow5_in16_16x32", "w9_min_reflect", "w9_odd_splits", "w9s_min", "rowfast_valid", "rowfast_f32_wo32", "wgrad_v2_wo65",
          "wgrad_128x128_cr3", "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged",
-         "halo3_pair_n3_same", "s2halo_deconv_n3", "stem7_32x64_n2"]     # two source chunks forward; S2HALO past one tile; the stem past one tile
+         "halo3_pair_n3_same", "s2halo_deconv_n3", "stem7_32x64_n2",     # two source chunks forward; S2HALO past one tile; the stem past one tile
+         # stride-1 transposed convs: the halo GEMM's data-gradient direction with a bias and an activation (its epilogue off the plain
+         # path, at 8 to 512 destination channels), the same behind a split-K reduce and on a ragged tile, W9 with x on the conv-output side
+         "tconv1_halo3_min", "tconv1_halo3_n3_dtail", "tconv1_halo3_pair_n3", "tconv1_halo3_c512", "tconv1_head_c3", "tconv1_head_ragged",
+         "tconv1_splitk", "tconv1_ragged", "tconv1_w9_two_splits"]
 FUSED_CASES = [(E.BY_NAME[n], dt) for n in FUSED for dt in E.BY_NAME[n][10]]
 
 
@@ -117,8 +121,23 @@ def test_edge_row_fused_forms_in_guard_cells(sg, row, dtype):
 # odd split count, W9S with one split).
 GROUPED = ["narrow5_16x32", "head7_16x32", "head7_ragged", "stem7_17x33", "w9_min_reflect", "w9_odd_splits", "w9_two_splits", "w9s_min",
            "w9s_lead_pad", "w9s_two_splits", "s2n_wo130", "rowfast_valid", "rowfast_f32_wo32", "wgrad_v2_wo65", "wgrad_128x128_cr3",
-           "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged", "s2halo_deconv_n3"]       # (W9S as a transposed conv)
+           "wgrad_128x64_cr3", "wgrad_128x16_kr3", "deconv_ragged", "s2halo_deconv_n3",       # (W9S as a transposed conv)
+           # stride-1 transposed convs (sgg_deconv2d_bwd_weight_group2: x on the conv-output side): W9 with one, two and 35 slabs and
+           # with 24 at Cin != Cout, the LDS-DMA kernel, a generic tile
+           "tconv1_w9_min", "tconv1_w9_two_splits", "tconv1_w9_odd_splits", "tconv1_halo3_pair_n3", "tconv1_halo3_src264", "tconv1_ragged"]
 GROUPED_CASES = [(E.BY_NAME[n], dt) for n in GROUPED for dt in E.BY_NAME[n][10]]
+# Which of the transposed rows' two networks share ONE launch, from the slab count (the workspace over one f32 slab of dW): W9 with
+# an even count (half the slabs each), the LDS-DMA kernel from two slabs on; every other form launches once per network.
+TCONV1_SLABS = {"tconv1_w9_min": (1, False), "tconv1_w9_two_splits": (2, True), "tconv1_w9_odd_splits": (35, False),
+                "tconv1_halo3_pair_n3": (24, True), "tconv1_halo3_src264": (4, True), "tconv1_ragged": (1, False)}
+
+
+def shares_the_launch(g):
+    """(slab count, whether a grouped weight gradient of this shape runs both networks in one launch): run_wgrad's rule."""
+    route = E.routes(g)[2]
+    slabs, rest = divmod(g.ws_wgrad, 9 * g.desc.C * g.desc.K * 4)
+    assert rest == 0
+    return slabs, (route == "W9" and slabs % 2 == 0) or (route in ("WGRAD_V2", "WGRAD_V2_ROWFAST") and slabs >= 2)
 
 
 @pytest.mark.parametrize("row,dtype", GROUPED_CASES, ids=[f"{r[0]}-{dt}" for r, dt in GROUPED_CASES])
@@ -133,6 +152,8 @@ def test_edge_row_two_network_weight_gradients_bit_exact(sg, row, dtype):
     g, x, dy, _, _, _ = operands(sg, row, dtype, e)
     assert E.routes(g)[2] == E.row_routes(row, dtype)[2]
     tag = f"{name}[{dtype}] {E.row_routes(row, dtype)[2]}"
+    if name in TCONV1_SLABS and dtype == "bf16":
+        assert g.is_deconv and shares_the_launch(g) == TCONV1_SLABS[name], (name, shares_the_launch(g))
     xs, dys = torch.cat([x, 2 * x]), torch.cat([dy, -dy])
     wshape = tuple(e.w.shape)
     for accumulate in (False, True):
@@ -142,7 +163,8 @@ def test_edge_row_two_network_weight_gradients_bit_exact(sg, row, dtype):
         E.same(dwb.t, -2 * e.dw + (-3.0 if accumulate else 0.0), f"{tag} group2 dwB accumulate={accumulate}")
         dwa.check(f"{tag} group2 dwA accumulate={accumulate}")
         dwb.check(f"{tag} group2 dwB accumulate={accumulate}")
-    if E.row_routes(row, dtype)[2] != "W9":
+    if E.row_routes(row, dtype)[2] != "W9" or g.is_deconv:   # (a transposed conv has no conv_wgrad_pair: g.wgrad_pair is False)
+        assert not (g.is_deconv and g.wgrad_pair)
         return
     # two applications of one layer summed into one dw: dw(x, dy) + dw(2x, -dy) = -dw
     assert g.wgrad_pair

@@ -265,7 +265,23 @@ REACHES = {
     "stem7_17x33": (1, "N7", ("bf16",)), "narrow5_16x32": (0, "HALO_FWD", ("bf16", "f32")),
     "narrow5_in16_16x32": (1, "HALO_DGRAD_NARROW", ("bf16", "f32")), "narrow5_in16_reflect": (1, "HALO_DGRAD_NARROW", ("bf16", "f32")),
     "deconv_ragged": (0, "GLDS_128x64", ("bf16", "f32")), "wgrad_128x64_cr3": (0, "GLDS_128x64", ("bf16", "f32")),
+    # stride-1 transposed convs: deconv_fwd_group2 is the stacked halo launch in the data-gradient direction with bias / bias2 picked per
+    # image (no conv-side form passes a bias there), deconv_dgrad_group2 the stacked forward direction without one
+    "tconv1_halo3_pair_n3": (0, "HALO3", ("bf16",)), "tconv1_halo3_c512": (0, "HALO3", ("bf16",)), "tconv1_halo3_n3_dtail": (0, "HALO3", ("bf16",)),
+    "tconv1_halo3_src264": (1, "HALO3", ("bf16",)), "tconv1_head_c3": (0, "HALO3", ("bf16",)),
+    "tconv1_splitk": (0, "GLDS_128x128+SPLITK", ("bf16", "f32")), "tconv1_ragged": (0, "GLDS_128x64", ("bf16", "f32")),
 }
+# How the grouped forward / data gradient of the transposed rows run in bf16 (plan_conv's `group`, from the route): the halo kernel
+# picks weights and bias per image, so its grouped call is the single launch on 2N images split at N; the generic GEMM doubles its grid.
+TCONV1_GROUP = {
+    "tconv1_halo3_pair_n3": ("stacked", "stacked"), "tconv1_halo3_c512": ("stacked", "stacked"), "tconv1_halo3_n3_dtail": ("stacked", "one launch"),
+    "tconv1_halo3_src264": ("one launch", "stacked"), "tconv1_head_c3": ("stacked", "one launch"), "tconv1_splitk": ("one launch", "one launch"),
+    "tconv1_ragged": ("one launch", "one launch"),
+}
+
+
+def group_path(route):
+    return "stacked" if route in ("HALO3", "S2HALO") else "one launch" if route.startswith("GLDS_") else "two calls"
 
 
 def group2_operands(sg, row, dtype):
@@ -285,6 +301,8 @@ def test_grouped_two_network_calls_bit_exact(sg, row, dtype):
     K, ea, eb, g, x, dy, (wfa, wda, ba), (wfb, wdb, bb) = group2_operands(sg, row, dtype)
     if dtype in dts:
         assert E.routes(g)[op] == route, (name, dtype, E.routes(g))
+    if name in TCONV1_GROUP and dtype == "bf16":
+        assert g.is_deconv and tuple(group_path(r) for r in E.routes(g)[:2]) == TCONV1_GROUP[name], (name, E.routes(g))
     for r, ws in zip(E.routes(g)[:2], (g.ws_fwd, g.ws_dgrad)):
         assert not r.endswith("+SPLITK") or ws > 0       # split K: the grouped call needs, and the launcher passes, twice this
     tag = f"{name}[{dtype}] {E.routes(g)[:2]}"
@@ -320,6 +338,44 @@ def test_grouped_two_network_calls_bit_exact(sg, row, dtype):
         E.same(dbb.t, eb.db + (-3.0 if accumulate else 0.0), f"{tag} group2 dbB accumulate={accumulate}")
         dba.check(f"{tag} group2 dbA")
         dbb.check(f"{tag} group2 dbB")
+
+
+def test_lockstep_head_writes_into_a_batch_slice_of_a_larger_tensor(sg):
+    """tconv1_head_c3 (d8: 64 -> 3, 8 stored channels), stacked forward through out=: the 2N = 6 images go into images 2..7 of a guarded
+    tensor of 10 -- what the lockstep U-Net's d8 does with the discriminators' stacked input.  The images before and after the slice
+    keep their sentinel bytes, like the cells around the tensor."""
+    row = E.BY_NAME["tconv1_head_c3"]
+    pinned(row, "bf16")
+    K, ea, eb, g, x, _, (_, wda, ba), (_, wdb, bb) = group2_operands(sg, row, "bf16")
+    assert g.is_deconv and E.routes(g)[0] == "HALO3" and g.y_shape == (3, 6, 256, 8)
+    ye = np.concatenate([padc(ea.y, 8), padc(eb.y, 8)])
+    for act, leak, an in acts():
+        f = {"none": lambda v: v, "relu": lambda v: np.maximum(v, 0.0), "lrelu": lambda v: np.where(v > 0, v, 0.5 * v)}[an]
+        big = Guarded((10,) + tuple(g.y_shape[1:]), BF)
+        out = K.deconv_fwd_group2(g, x, wda, ba, wdb, bb, act, leak, out=big.t[2:8])
+        assert out.data_ptr() == big.t[2].data_ptr()
+        E.same(big.t[2:8], E.store(f(ye), BF), f"tconv1_head_c3 group2 y into a slice, act {an}")
+        big.check(f"tconv1_head_c3 group2 y into a slice, act {an}")
+        for lo, hi in ((0, 2), (8, 10)):
+            assert bool((big.t[lo:hi].contiguous().view(torch.uint8) == 0xA5).all()), f"act {an}: images {lo}..{hi - 1} beside the slice were written"
+
+
+def test_stride1_transposed_conv_has_no_statistics_epilogue(sg):
+    """tconv1_halo3_pair_n3 runs HALO3 in both directions, and still sgg_deconv2d_fwd_stats has no form for it, single or stacked
+    (the statistics epilogue of a transposed conv is the stride-2 kernel's): unsupported, before anything is launched."""
+    from sggan_amd import _abi as A
+    row = E.BY_NAME["tconv1_halo3_pair_n3"]
+    pinned(row, "bf16")
+    K, _, _, g, x, _, (_, wda, ba), (_, wdb, bb) = group2_operands(sg, row, "bf16")
+    assert g.is_deconv and g.stats_chunks == 0 and not g.pair_ok and E.routes(g)[:2] == ("HALO3", "HALO3")
+    p = K._p
+    xa = x[:g.x_shape[0]].contiguous()
+    for w2, b2, nsplit in ((None, None, 0), (wdb, bb, 1)):
+        y, part = Guarded(g.y_shape, BF), Guarded((g.y_shape[0], 4, g.y_shape[3], 2), F32)
+        rc = A.lib().sgg_deconv2d_fwd_stats(C.byref(g.desc), p(xa), p(wda), p(ba), p(w2), p(b2), nsplit, p(y.t), p(part.t), None, 0, K._s())
+        assert rc == A.EUNSUPPORTED
+        y.untouched(f"{row[0]} y, nsplit {nsplit}")
+        part.untouched(f"{row[0]} partial, nsplit {nsplit}")
 
 
 def test_grouped_split_k_call_refuses_the_single_workspace(sg):

@@ -33,7 +33,10 @@ ROWS_AB = FUSED + ["glds_128x128_long_k"] + E.FOLD_TWICE
 CASES_AB = [(E.BY_NAME[n], dt) for n in ROWS_AB for dt in E.BY_NAME[n][10]]
 IDS_AB = [f"{r[0]}-{dt}" for r, dt in CASES_AB]
 TANH_ROUTES = ("N7", "HALO_FWD")
-TANH_ROWS = ("glds_128x128_long_k", "splitk_fwd_dc40", "s2halo_min_deconv")
+TANH_ROWS = ("glds_128x128_long_k", "splitk_fwd_dc40", "s2halo_min_deconv",
+             "tconv1_head_c3", "tconv1_halo3_min")       # d8's own activation: HALO3 at 8 destination channels (f32: behind the split-K reduce), and at 64
+# the stacked forward of two networks (deconv_fwd_group2), each with a fractional draw of its own
+GROUPED_FWD = ["tconv1_halo3_pair_n3"]
 # d: the f32 rows of FUSED; left out: rows whose weight-gradient draw holds fewer than 9 fraction bits inside the exactness bound.
 # None: the two rows with 2 x 101 x 103 = 20806 pixels per element of dw hold 11, every other row 12 (test_conv_edges_cpu.py asserts
 # that the list is exactly the rows below 9).
@@ -140,6 +143,28 @@ def test_data_gradient_epilogue_rounds_once(sg, case):
     K.conv_dgrad(g, dy, wd, dev(add, dt), out=dx.t)      # (an addend takes the narrow halo routes' shapes to the generic GEMM: one rounding)
     E.same(dx.t, E.store(dxp + add, dt), tag + " dx + addend")
     dx.check(tag + " dx + addend")
+
+
+@pytest.mark.parametrize("name", GROUPED_FWD)
+def test_grouped_transposed_forward_rounds_once_per_network(sg, name):
+    """deconv_fwd_group2 on the stacked HALO3 launch: network A's images with A's fractional weights and bias, B's with B's, each
+    y = store(act(exact)) of its own network -- the bias is added and the activation applied before the one rounding, per image."""
+    from sggan_amd import _abi as A
+    K = sg.kernels
+    row = E.BY_NAME[name]
+    pinned(row, "bf16")
+    ea, eb = E.rounding(name, "bf16"), E.rounding(name, "bf16", "/B")
+    g, xa, _, _, wda, ba = E.operands(sg, row, "bf16", ea)
+    _, xb, _, _, wdb, bb = E.operands(sg, row, "bf16", eb)
+    assert g.is_deconv and E.routes(g)[0] == "HALO3"
+    yc = g.y_shape[3]
+    pre = np.concatenate([padc(ea.y, yc), padc(eb.y, yc)])
+    x = torch.cat([xa, xb])
+    for act, leak, exp in ((A.ACT_NONE, 0.0, pre), (A.ACT_RELU, 0.0, np.maximum(pre, 0.0)), (A.ACT_LRELU, LEAK, E.lrelu_f32(pre, LEAK))):
+        y = Guarded((2 * g.y_shape[0],) + tuple(g.y_shape[1:]), BF)
+        K.deconv_fwd_group2(g, x, wda, ba, wdb, bb, act, leak, out=y.t)
+        E.same(y.t, E.store(exp, BF), f"{name} group2 y act {act}")
+        y.check(f"{name} group2 y act {act}")
 
 
 # ---------------------------------------------------------------------------------------------------- c. fused forms, bf16
