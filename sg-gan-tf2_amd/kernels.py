@@ -436,15 +436,17 @@ def bias_grad_group2(dy, db, db2, accumulate=False):
 
 
 # ----------------------------------------------------------------------------- instance norm / activations
-# The public instnorm_* functions below are thin calls into _instnorm_fwd / _instnorm_bwd, which check, allocate, size the
-# workspace, open the profiler span and assemble the argument list of the sgg_instnorm_* symbol the arguments select.
+# instnorm_forward / instnorm_backward check, allocate, size the workspace, open the profiler span and assemble the argument list
+# of the sgg_instnorm_* symbol their arguments select; the layer units of module.py call them, and the named instnorm_* functions
+# below are thin calls into them.
 #   addend   the tensor added to the output: the residual (after the activation; may be None), or with skip=True the skip
 #            (before the activation: y = act(gamma*xhat + beta + skip), generator_unet d3 / d7)
 #   partial  the (sum, sumsq) / (sum g, sum g*xhat) rows of the producing conv: the norm skips its statistics pass
 #   pair     two networks of the same shape on one stacked batch (images 0..nsplit-1: first network; the rest: second):
 #            (gamma2, beta2, nsplit) forward, (gamma2, beta2, nsplit, dgamma2, dbeta2) backward
-#   span     (name, key) of the profiler span, or None for none
-def _instnorm_fwd(span, x, gamma, beta, addend, eps, act, leak, skip=False, partial=None, pair=None):
+# The profiler span follows from the same arguments.  Forward: the named function's name (the skip forms': without "_partial") and
+# the key (shape, has residual), the skip forms' (shape, has partial); backward: the skip forms only, keyed by the shape.
+def instnorm_forward(x, gamma, beta, addend, eps, act, leak, skip=False, partial=None, pair=None):
     N, H, W, Cp = x.shape
     assert gamma.numel() == Cp and beta.numel() == Cp, "gamma/beta must be channel-padded"
     if skip:
@@ -466,14 +468,15 @@ def _instnorm_fwd(span, x, gamma, beta, addend, eps, act, leak, skip=False, part
     if partial is None:
         ws = workspace(int(A.lib().sgg_instnorm_workspace(N, H * W, Cp)), x.device)
         args += [_p(ws), ws.numel()]
-    pr = _prof(*span) if span else None
+    span = "instnorm_fwd" + ("_skip" if skip else "_partial" if partial is not None else "") + ("_pair" if pair is not None else "")
+    pr = _prof(span, (tuple(x.shape), (partial if skip else addend) is not None))
     if pr: pr.start()
     A.check(getattr(A.lib(), "sgg_" + name)(*args, _s()), name)
     if pr: pr.stop()
     return y, stats
 
 
-def _instnorm_bwd(span, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=None, partial=None, pair=None):
+def instnorm_backward(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=None, partial=None, pair=None):
     """y: the stored output of the skip form, whose backward returns (dx, dskip), dskip = dy * act'(y); otherwise dx alone."""
     N, H, W, Cp = x.shape
     skip = y is not None
@@ -500,7 +503,7 @@ def _instnorm_bwd(span, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, ac
     if partial is not None:
         args += [_p(partial), partial.shape[1]]
     args += [N, H * W, Cp, dgamma.numel(), int(accumulate), act, leak] + ([] if mixed else [dt(x)])
-    pr = _prof(*span) if span else None
+    pr = _prof(name, tuple(x.shape)) if skip else None
     if pr: pr.start()
     A.check(getattr(A.lib(), "sgg_" + name)(*args, _p(ws), ws.numel(), _s()), name)
     if pr: pr.stop()
@@ -508,62 +511,56 @@ def _instnorm_bwd(span, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, ac
 
 
 def instnorm_fwd(x, gamma, beta, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
-    return _instnorm_fwd(("instnorm_fwd", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak)
+    return instnorm_forward(x, gamma, beta, residual, eps, act, leak)
 
 
 def instnorm_fwd_partial(x, partial, gamma, beta, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
     """instance norm whose statistics pass was done by the producing conv (conv_fwd_stats): finalize + apply only."""
-    return _instnorm_fwd(("instnorm_fwd_partial", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak,
-                         partial=partial)
+    return instnorm_forward(x, gamma, beta, residual, eps, act, leak, partial=partial)
 
 
 def instnorm_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
     """sgg_instnorm_bwd, or sgg_instnorm_bwd_mixed when dy is f32 and x is bf16."""
-    return _instnorm_bwd(None, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak)
+    return instnorm_backward(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak)
 
 
 def instnorm_bwd_partial(dy, x, partial, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
     """instance-norm backward whose statistics pass was done by the conv data gradient that produced dy."""
-    return _instnorm_bwd(None, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, partial=partial)
+    return instnorm_backward(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, partial=partial)
 
 
 def instnorm_fwd_skip(x, gamma, beta, skip, eps=1e-3, act=A.ACT_NONE, leak=0.0, partial=None):
     """partial: the producing conv's (sum, sumsq) rows (conv_fwd_stats / deconv_fwd_stats) -- the norm skips its statistics pass."""
-    return _instnorm_fwd(("instnorm_fwd_skip", (tuple(x.shape), partial is not None)), x, gamma, beta, skip, eps, act, leak,
-                         skip=True, partial=partial)
+    return instnorm_forward(x, gamma, beta, skip, eps, act, leak, skip=True, partial=partial)
 
 
 def instnorm_bwd_skip(dy, y, x, gamma, beta, stats, dgamma, dbeta, accumulate=False, act=A.ACT_NONE, leak=0.0):
     """Backward of instnorm_fwd_skip from its stored output y: returns (dx, dskip), dskip = dy * act'(y)."""
-    return _instnorm_bwd(("instnorm_bwd_skip", tuple(x.shape)), dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=y)
+    return instnorm_backward(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=y)
 
 
 def instnorm_fwd_pair(x, gamma, beta, gamma2, beta2, nsplit, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
-    return _instnorm_fwd(("instnorm_fwd_pair", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak,
-                         pair=(gamma2, beta2, nsplit))
+    return instnorm_forward(x, gamma, beta, residual, eps, act, leak, pair=(gamma2, beta2, nsplit))
 
 
 def instnorm_fwd_partial_pair(x, partial, gamma, beta, gamma2, beta2, nsplit, residual=None, eps=1e-3, act=A.ACT_NONE, leak=0.0):
-    return _instnorm_fwd(("instnorm_fwd_partial_pair", (tuple(x.shape), residual is not None)), x, gamma, beta, residual, eps, act, leak,
-                         partial=partial, pair=(gamma2, beta2, nsplit))
+    return instnorm_forward(x, gamma, beta, residual, eps, act, leak, partial=partial, pair=(gamma2, beta2, nsplit))
 
 
 def instnorm_bwd_pair(dy, x, gamma, beta, gamma2, beta2, nsplit, stats, dgamma, dbeta, dgamma2, dbeta2, accumulate=False,
                       act=A.ACT_NONE, leak=0.0):
-    return _instnorm_bwd(None, dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, pair=(gamma2, beta2, nsplit, dgamma2, dbeta2))
+    return instnorm_backward(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, pair=(gamma2, beta2, nsplit, dgamma2, dbeta2))
 
 
 def instnorm_fwd_skip_pair(x, gamma, beta, gamma2, beta2, nsplit, skip, eps=1e-3, act=A.ACT_NONE, leak=0.0, partial=None):
     """instnorm_fwd_skip of two networks on one stacked batch: y = act(IN(x) + skip) with the affine set picked by image index."""
-    return _instnorm_fwd(("instnorm_fwd_skip_pair", (tuple(x.shape), partial is not None)), x, gamma, beta, skip, eps, act, leak,
-                         skip=True, partial=partial, pair=(gamma2, beta2, nsplit))
+    return instnorm_forward(x, gamma, beta, skip, eps, act, leak, skip=True, partial=partial, pair=(gamma2, beta2, nsplit))
 
 
 def instnorm_bwd_skip_pair(dy, y, x, gamma, beta, gamma2, beta2, nsplit, stats, dgamma, dbeta, dgamma2, dbeta2, accumulate=False,
                            act=A.ACT_NONE, leak=0.0):
     """Backward of instnorm_fwd_skip_pair from its stored output y: (dx, dskip), both stacked like x."""
-    return _instnorm_bwd(("instnorm_bwd_skip_pair", tuple(x.shape)), dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak,
-                         y=y, pair=(gamma2, beta2, nsplit, dgamma2, dbeta2))
+    return instnorm_backward(dy, x, gamma, beta, stats, dgamma, dbeta, accumulate, act, leak, y=y, pair=(gamma2, beta2, nsplit, dgamma2, dbeta2))
 
 
 def act_fwd(x, act, leak=0.0):

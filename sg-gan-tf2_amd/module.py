@@ -314,22 +314,105 @@ FUSE_DECONV_IN_STATS = False
 FUSE_STEM_IN_STATS = False
 
 
-class _ConvUnit:
-    """One Conv2D / Conv2DTranspose call site, optionally followed by InstanceNorm (+act, +residual),
-    or by a fused activation when there is no norm.  Stateless w.r.t. activations: forward returns a
-    record that backward consumes, so one network can be applied several times per step.
+class _Unit:
+    """One Conv2D / Conv2DTranspose call site, optionally followed by InstanceNorm (+act, +residual), or by a fused activation
+    when there is no norm -- of one network (_ConvUnit) or of two networks of one shape in lockstep on a stacked batch
+    (_PairUnit).  Stateless w.r.t. activations: forward returns a record that backward consumes, so one network can be applied
+    several times per step.
 
-    The unit protocol -- ``name``, ``skip_grad``, ``geom(x)``, ``forward(...)``, ``backward(...)`` -- is answered alike by
-    _SkipActUnit and by the lockstep units (_PairUnit, _PairSkipActUnit): the networks' layer walks never ask which kind
-    they hold."""
+    This class owns the sequence -- conv -> (mask) -> norm -> record, and norm backward -> (mask) -> bias, weight and data
+    gradient -- with its options, record layouts and return conventions; the two kinds supply the launches: ``_conv``,
+    ``_norm``, ``_norm_backward``, ``_bias_grad``, ``weight_grad``, ``_data_grad`` (and ``geom``, ``affine``, ``dropout_``).
+    The layer's description (``name``, ``kind``, ``norm``, ``act``, ``leak``, ``R``, ``cout``, ...) and ``skip_grad`` are fixed
+    at construction; the switches of ``net`` are read at every call (model.py sets them after the units are built).  The
+    networks' layer walks see ``name``, ``skip_grad``, ``drop_layer``, ``geom``, ``forward`` and ``backward`` and never ask
+    which kind they hold.
 
-    skip_grad = False           # backward returns dx (True: (dx, dskip), the gradient of the skip path as well)
+    skip_grad: the skip tensor is added BEFORE the activation, y = act(IN(conv(x)) + skip) (generator_unet d3 / d7,
+    module.py:181-184,199-202).  The record then keeps y as well -- the norm backward derives act' from it -- and backward
+    returns (dx, dskip), dskip being the skip path's gradient."""
+
+    LAYER = ("name", "kind", "stride", "padding", "reflect", "norm", "act", "leak", "R", "S", "cin", "cout", "skip_grad")
     drop_layer = None           # a dropout site's layer index (generator_unet d1..d3: 0..2): the mask sits between conv and norm
 
-    def __init__(self, net, name, kind, stride=1, padding="VALID", reflect=0, norm=True, act=A.ACT_NONE, leak=0.0):
+    def _epilogue_stats(self, g, fuse):
+        """Does this conv's epilogue deliver the (sum, sumsq) rows of its output for the norm behind it (which then skips its
+        own statistics pass over the tensor)?  fuse=False -- a dropout site in training mode -- never: the epilogue would sum
+        the tensor in front of the mask.  The stem's and the transposed layers' epilogues are opt-ins of their own."""
+        net = self.net
+        if not (fuse and self.norm and g.stats_chunks and net.fuse_in_stats):
+            return False
+        return net.fuse_in_stats_deconv if self.kind == "deconv" else self.R != 7 or net.fuse_in_stats_stem
+
+    def _limits(self, gbuf, dy_partial):
+        """What this kind's backward has no form for is refused here, before anything is launched."""
+
+    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
+        """Returns (y, record); record = (g, x, xc, stats) [+ (y,) with skip_grad] [+ (drop,) at a dropout site], stats None for
+        a layer without a norm.
+        out: the caller's buffer for the layer output (layers without a norm only: the generator's last layer writes the
+        fakes straight into the discriminators' stacked input).
+        record_only: the caller only wants the forward record (activation checkpointing re-runs a residual block's second
+        conv for its backward pass: the block's output is not needed again) -- where one launch's epilogue delivered the
+        norm's sums for the whole batch, the norm's apply pass is skipped (same statistics, bit for bit) and y is None.
+        drop: (stream id, sample offset) at a dropout site in training mode -- the conv output is masked in place before the
+        norm reads it, and the record grows by ``drop``, which the backward needs to repeat the launch; None: no launch."""
+        assert out is None or not self.norm
+        assert drop is None or (self.norm and not record_only)
+        assert not self.skip_grad or (self.norm and residual is not None and not record_only)
+        g, xc, part, whole = self._conv(x, out, fuse=drop is None)
+        if not self.norm:
+            return xc, (g, x, xc, None)
+        if drop is not None:
+            self.dropout_(xc, drop)
+        if record_only and part is not None and whole:
+            return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], self.net.eps))
+        y, stats = self._norm(xc, residual, part)
+        return y, (g, x, xc, stats) + ((y,) if self.skip_grad else ()) + (() if drop is None else (drop,))
+
+    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
+        """Returns dx (None without want_dx); (dx, partial) when next_norm is given; with skip_grad (dx, dskip).
+        gbuf: a gradient buffer to use instead of the network's own.  addend: added to dx (in the data gradient's store where
+        the kernel has one).  dy_partial: the norm-backward partial sums of THIS unit's norm, already computed by the data
+        gradient that produced dy.  next_norm = (unit, rec) of the layer that will consume the returned dx: ``partial`` is
+        the first pass of its norm backward where this unit's data-gradient epilogue can make it, else None."""
+        self._limits(gbuf, dy_partial)
+        g, x, xc, stats, *rest = rec
+        y = rest.pop(0) if self.skip_grad else None
+        drop = rest[0] if rest else None
+        assert not self.skip_grad or addend is None
+        assert (not self.skip_grad and drop is None) or (dy_partial is None and next_norm is None)     # (neither takes a fused-statistics route)
+        dskip = None
+        if self.norm:
+            dxc = self._norm_backward(dy, xc, stats, y, dy_partial, param_grads, gbuf)
+            if self.skip_grad:
+                dxc, dskip = dxc
+            if drop is not None:            # dxc becomes the gradient with respect to the conv output: the forward's launch again
+                self.dropout_(dxc, drop)
+        else:
+            if dy.dtype != xc.dtype:
+                dy = dy.to(xc.dtype)
+            dxc = K.act_bwd(dy, xc, self.act, self.leak) if self.act != A.ACT_NONE else dy
+        if param_grads:
+            # a conv bias that feeds an InstanceNorm has an identically zero gradient (SURVEY.md 3.3) and is left at 0 -- unless
+            # a mask sits between them: the norm no longer cancels the bias
+            if drop is not None or not self.norm:
+                self._bias_grad(dxc, gbuf)
+            self.weight_grad(g, x, dxc, gbuf)
+        dx = None
+        if want_dx:
+            dx = self._data_grad(g, x, dxc, addend, next_norm)
+            dx = dx if next_norm is not None else dx[0]
+        return (dx, dskip) if self.skip_grad else dx
+
+
+class _ConvUnit(_Unit):
+    """The unit of one network: every launch is the plain per-network entry."""
+
+    def __init__(self, net, name, kind, stride=1, padding="VALID", reflect=0, norm=True, act=A.ACT_NONE, leak=0.0, skip_grad=False):
         self.net, self.name, self.kind = net, name, kind            # kind: "conv" | "deconv"
         self.stride, self.padding, self.reflect = stride, padding, reflect
-        self.norm, self.act, self.leak = norm, act, leak
+        self.norm, self.act, self.leak, self.skip_grad = norm, act, leak, skip_grad
         shape = net.P.index[name + "_w"][2]
         self.R, self.S = shape[0], shape[1]
         if kind == "conv":
@@ -370,58 +453,41 @@ class _ConvUnit:
                 self._packed = (key, wf, wd)
         return self._packed[1], self._packed[2]
 
-    def _conv(self, x, out=None, fuse=True):
-        """The convolution alone: (g, xc, part).  part: the per-chunk (sum, sumsq) rows of xc where the launch's epilogue
-        delivers them for the norm behind it (that norm then skips its own statistics pass over the tensor), else None.
-        fuse=False (a dropout site in training mode): never -- the epilogue would sum the tensor in front of the mask."""
-        P, n = self.net.P, self.name
-        assert out is None or not self.norm
-        g = self.geom(x)
-        wf, wd = self.packed(x.dtype)
-        stats = fuse and self.norm and g.stats_chunks and self.net.fuse_in_stats
-        if self.kind == "conv" and stats and (self.R != 7 or self.net.fuse_in_stats_stem):
-            return (g,) + K.conv_fwd_stats(g, x, wf, P.p(n + "_b"))
-        if self.kind == "deconv" and stats and self.net.fuse_in_stats_deconv:
-            # Conv2DTranspose + InstanceNormalization (module.py:254-260): the stride-2 halo kernel's epilogue emits the norm's sums too
-            return (g,) + K.deconv_fwd_stats(g, x, wd, P.p(n + "_b"))
-        fused_act = A.ACT_NONE if self.norm else self.act
-        if self.kind == "conv":
-            return g, K.conv_fwd(g, x, wf, P.p(n + "_b"), fused_act, self.leak, out=out), None
-        return g, K.deconv_fwd(g, x, wd, P.p(n + "_b"), fused_act, self.leak, out=out), None
+    def affine(self):
+        """(gamma, beta) of this unit's norm."""
+        return self.net.P.p(self.name + "_g"), self.net.P.p(self.name + "_beta")
 
     def dropout_(self, t, drop):
         """The dropout launch of this site, in place on t (the conv output, or the gradient with respect to the masked tensor):
         drop = (stream id, sample offset), the mask keyed by this unit's network -- its seed and its device step counter."""
         K.dropout_(t, self.net.dropout, self.net.P.iterations, self.net.seed, drop[1], drop[0])
 
-    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
-        """out: the caller's buffer for the layer output (layers without a norm only: the generator's last layer writes the
-        fakes straight into the discriminators' stacked input).
-        record_only: the caller only wants the forward record (activation checkpointing re-runs a residual block's second
-        conv for its backward pass: the block's output is not needed again) -- where the conv's epilogue delivers the norm's
-        sums, the norm's apply pass is skipped (same statistics, bit for bit) and y is None.
-        drop: (stream id, sample offset) at a dropout site in training mode -- the conv output is masked in place before the
-        norm reads it, and the record grows by ``drop``, which the backward needs to repeat the launch; None: today's launches."""
-        if drop is not None:
-            assert self.norm and not record_only
-            g, xc, _ = self._conv(x, fuse=False)
-            self.dropout_(xc, drop)
-            y, stats = K.instnorm_fwd(xc, *self.affine(), residual, self.net.eps, self.act, self.leak)
-            return y, (g, x, xc, stats, drop)
-        g, xc, part = self._conv(x, out)
-        if not self.norm:
-            return xc, (g, x, xc, None)
-        if part is None:
-            y, stats = K.instnorm_fwd(xc, *self.affine(), residual, self.net.eps, self.act, self.leak)
-        elif record_only:
-            return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], self.net.eps))
-        else:
-            y, stats = K.instnorm_fwd_partial(xc, part, *self.affine(), residual, self.net.eps, self.act, self.leak)
-        return y, (g, x, xc, stats)
+    def _conv(self, x, out, fuse):
+        """The convolution alone: (g, xc, part, whole).  part: the statistics rows of xc where _epilogue_stats says the launch
+        delivers them, else None; whole: they cover the batch from one launch (here: always)."""
+        g = self.geom(x)
+        wf, wd = self.packed(x.dtype)
+        conv, bias = self.kind == "conv", self.net.P.p(self.name + "_b")
+        if self._epilogue_stats(g, fuse):
+            # (a Conv2DTranspose, module.py:254-260: the stride-2 halo kernel's epilogue emits the norm's sums too)
+            return (g,) + (K.conv_fwd_stats(g, x, wf, bias) if conv else K.deconv_fwd_stats(g, x, wd, bias)) + (True,)
+        fused_act = A.ACT_NONE if self.norm else self.act
+        xc = K.conv_fwd(g, x, wf, bias, fused_act, self.leak, out=out) if conv else K.deconv_fwd(g, x, wd, bias, fused_act, self.leak, out=out)
+        return g, xc, None, False
 
-    def affine(self):
-        """(gamma, beta) of this unit's norm."""
-        return self.net.P.p(self.name + "_g"), self.net.P.p(self.name + "_beta")
+    def _norm(self, xc, addend, part):
+        return K.instnorm_forward(xc, *self.affine(), addend, self.net.eps, self.act, self.leak, skip=self.skip_grad, partial=part)
+
+    def _norm_backward(self, dy, xc, stats, y, part, param_grads, gbuf):
+        P, n = self.net.P, self.name
+        if param_grads:
+            dg, db = P.g(n + "_g", buf=gbuf), P.g(n + "_beta", buf=gbuf)
+        else:   # gradients w.r.t. gamma/beta not wanted: send them to scratch
+            dg = db = self.net.scratch_vec(K.cpad(self.cout))
+        return K.instnorm_backward(dy, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak, y=y, partial=part)
+
+    def _bias_grad(self, dxc, gbuf):
+        K.bias_grad(dxc, self.net.P.g(self.name + "_b", buf=gbuf), accumulate=True)
 
     def weight_grad(self, g, x, dxc, gbuf=None):
         """dW += wgrad(x, dxc).  When the net is applied twice this step (pair_wgrads) the first application's operands are
@@ -441,92 +507,22 @@ class _ConvUnit:
         else:
             (K.conv_wgrad if self.kind == "conv" else K.deconv_wgrad)(g, x, dxc, P.g(n + "_w", buf=gbuf), accumulate=True)
 
-    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
-        """dy_partial: the norm-backward partial sums of THIS unit's norm, already computed by the data gradient that
-        produced dy.  next_norm = (unit, rec) of the layer that will consume the returned dx: if its norm's first pass can
-        be done in this unit's data-gradient epilogue the call returns (dx, partial) instead of dx."""
-        P, n = self.net.P, self.name
-        g, x, xc, stats, *drop = rec
+    def _data_grad(self, g, x, dxc, addend, next_norm):
+        """(dx + addend, the next norm's backward sums or None)."""
+        net = self.net
         wf, wd = self.packed(x.dtype)
-        if self.norm:
-            if param_grads:
-                dg, db = P.g(n + "_g", buf=gbuf), P.g(n + "_beta", buf=gbuf)
-            else:   # gradients w.r.t. gamma/beta not wanted: send them to scratch
-                dg = db = self.net.scratch_vec(K.cpad(self.cout))
-            if dy_partial is not None:
-                assert not drop                     # (a dropout site takes no fused-statistics route)
-                dxc = K.instnorm_bwd_partial(dy, xc, dy_partial, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
-            else:
-                dxc = K.instnorm_bwd(dy, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
-            # the conv bias feeds an InstanceNorm: its gradient is identically 0 (SURVEY.md 3.3) -> left at 0 ...
-            if drop:
-                # ... unless a mask sits between them: the norm no longer cancels the bias.  dxc becomes the gradient with respect
-                # to the conv output -- the forward's launch again -- and bias, weight and data gradient are taken from that
-                assert next_norm is None
-                self.dropout_(dxc, drop[0])
-                if param_grads:
-                    K.bias_grad(dxc, P.g(n + "_b", buf=gbuf), accumulate=True)
-        else:
-            if dy.dtype != xc.dtype:
-                dy = dy.to(xc.dtype)
-            dxc = K.act_bwd(dy, xc, self.act, self.leak) if self.act != A.ACT_NONE else dy
-            if param_grads:
-                K.bias_grad(dxc, P.g(n + "_b", buf=gbuf), accumulate=True)
-        if param_grads:
-            self.weight_grad(g, x, dxc, gbuf)
-        if not want_dx:
-            return None
-        if self.kind == "conv":
-            # mixed mode: the gradient handed to the NEXT norm backward stays f32 (bf16 operands in the GEMM, f32 result)
-            out_f32 = bool(self.net.mixed and next_norm is not None and next_norm[0].norm and g.dgrad_mixed and dxc.dtype == torch.bfloat16)
-            if addend is not None and addend.dtype != dxc.dtype and not out_f32:
-                addend = addend.to(dxc.dtype)
-            if next_norm is not None:
-                nu, nrec = next_norm
-                if (not out_f32 and self.net.fuse_in_stats and self.net.fuse_in_bwd and g.bwd_stats_chunks and nu.norm
-                        and tuple(nrec[2].shape) == g.x_shape):
-                    return K.conv_dgrad_stats(g, dxc, wd, addend, nrec[2], nrec[3], *nu.affine(), nu.act, nu.leak)
-                return K.conv_dgrad(g, dxc, wd, addend, out_f32=out_f32), None
-            return K.conv_dgrad(g, dxc, wd, addend)
-        dx = K.deconv_dgrad(g, dxc, wf)
-        dx = dx if addend is None else K.add(dx, addend.to(dx.dtype))
-        return (dx, None) if next_norm is not None else dx
-
-
-class _SkipActUnit(_ConvUnit):
-    """A Conv2D / Conv2DTranspose + InstanceNorm whose skip tensor is added BEFORE the activation: y = act(IN(conv(x)) + skip)
-    (generator_unet d3 / d7, module.py:181-184,199-202).  The forward record keeps y as well: the backward derives act'
-    from it (sgg_instnorm_bwd_skip) and returns (dx, dskip), dskip being the skip path's gradient."""
-
-    skip_grad = True
-
-    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
-        assert residual is not None and out is None and not record_only and self.norm
-        g, xc, part = self._conv(x, fuse=drop is None)
-        if drop is not None:
-            self.dropout_(xc, drop)
-        y, stats = K.instnorm_fwd_skip(xc, *self.affine(), residual, self.net.eps, self.act, self.leak, partial=part)
-        return y, (g, x, xc, stats, y) + (() if drop is None else (drop,))
-
-    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
-        assert addend is None and dy_partial is None and next_norm is None
-        P, n = self.net.P, self.name
-        g, x, xc, stats, y, *drop = rec
-        wf, wd = self.packed(x.dtype)
-        if param_grads:
-            dg, db = P.g(n + "_g", buf=gbuf), P.g(n + "_beta", buf=gbuf)
-        else:
-            dg = db = self.net.scratch_vec(K.cpad(self.cout))
-        dxc, dskip = K.instnorm_bwd_skip(dy, y, xc, *self.affine(), stats, dg, db, param_grads, self.act, self.leak)
-        if drop:                                    # (_ConvUnit.backward: the mask again, then the bias gradient it uncovers)
-            self.dropout_(dxc, drop[0])
-            if param_grads:
-                K.bias_grad(dxc, P.g(n + "_b", buf=gbuf), accumulate=True)
-        if param_grads:
-            self.weight_grad(g, x, dxc, gbuf)
-        if not want_dx:
-            return None, dskip
-        return (K.conv_dgrad(g, dxc, wd) if self.kind == "conv" else K.deconv_dgrad(g, dxc, wf)), dskip
+        if self.kind == "deconv":
+            dx = K.deconv_dgrad(g, dxc, wf)
+            return (dx if addend is None else K.add(dx, addend.to(dx.dtype))), None
+        nu, nrec = next_norm if next_norm is not None else (None, None)
+        # mixed mode: the gradient handed to the NEXT norm backward stays f32 (bf16 operands in the GEMM, f32 result)
+        out_f32 = bool(net.mixed and nu is not None and nu.norm and g.dgrad_mixed and dxc.dtype == torch.bfloat16)
+        if addend is not None and addend.dtype != dxc.dtype and not out_f32:
+            addend = addend.to(dxc.dtype)
+        if (nu is not None and not out_f32 and net.fuse_in_stats and net.fuse_in_bwd and g.bwd_stats_chunks and nu.norm
+                and tuple(nrec[2].shape) == g.x_shape):
+            return K.conv_dgrad_stats(g, dxc, wd, addend, nrec[2], nrec[3], *nu.affine(), nu.act, nu.leak)
+        return K.conv_dgrad(g, dxc, wd, addend, out_f32=out_f32), None
 
 
 class _Net:
@@ -545,7 +541,7 @@ class _Net:
         self._scratch = None
         self._tv = None
         # set by a step that applies this net exactly twice (the cycle step): weight gradients of layers that support
-        # it are deferred at the first backward and run with the second as one launch (_ConvUnit.backward)
+        # it are deferred at the first backward and run with the second as one launch (_ConvUnit.weight_grad)
         self.pair_wgrads = False
         # mixed precision (bf16 networks only): data gradients that feed an instance-norm backward are kept in f32 where the
         # kernel supports it (the residual chain) -- see sgg_conv2d_bwd_data_mixed in include/sggan.h
@@ -635,9 +631,10 @@ class _BlockInput:
         self.x = x
 
 
-# One walk per topology, written against the unit protocol (_ConvUnit): the network classes and their lockstep pair classes
-# (GeneratorPair, GeneratorUNetPair, DiscriminatorPair) differ only in the units they hand it, so a network and its pair visit
-# the layers -- and report them to on_unit_done -- in the same order by construction.
+# One walk per topology, written against the unit protocol (_Unit): a network class hands it _ConvUnits, its lockstep pair class
+# (GeneratorPair, GeneratorUNetPair, DiscriminatorPair) the _PairUnits over two networks' units -- nothing else differs, and the
+# units share one forward and one backward, so a network and its pair visit the layers, report them to on_unit_done and order
+# each layer's launches alike by construction.
 class _ResNetWalk:
     """generator_resnet (module.py:219-269) over ``head`` (three stem units), ``blocks`` ((a, b) unit pairs of the residual
     blocks) and ``tail`` (two transposed units + the output unit); ``checkpoint_blocks`` selects activation checkpointing."""
@@ -819,7 +816,7 @@ class GeneratorUNet(_UNetWalk, _Net):
         self.dropout = float(dropout)
         U = lambda *a, **k: _ConvUnit(self, *a, padding="SAME", **k)
         self.enc = [U(f"e{i}", "conv", act=A.ACT_LRELU, leak=self.LEAK) for i in range(1, 8)] + [U("e8", "conv", act=A.ACT_RELU)]
-        self.dec = [(_SkipActUnit(self, f"d{i}", "deconv", stride=1, act=A.ACT_RELU) if i in (3, 7) else
+        self.dec = [(U(f"d{i}", "deconv", stride=1, act=A.ACT_RELU, skip_grad=True) if i in (3, 7) else     # (ReLU after the add)
                      U(f"d{i}", "deconv", stride=1, act=A.ACT_NONE)) for i in range(1, 8)]
         self.d8 = U("d8", "deconv", stride=1, norm=False, act=A.ACT_TANH)
         for layer, u in enumerate(self.dec[:3]):        # d1, d2, d3: the dropout sites (:170, :175, :180)
@@ -1000,234 +997,155 @@ class Discriminator(_DiscriminatorWalk, _Net):
 
 
 # ----------------------------------------------------------------------------- two networks in lockstep
-class _PairUnit:
+class _PairUnit(_Unit):
     """The same call site of TWO networks of one shape (G_A->B / G_B->A, D_A / D_B), applied to a batch that stacks their
-    activations: images [:n] belong to ``ua``'s network, [n:] to ``ub``'s.  The convolutions run per half with each network's
-    weights (into slices of one stacked output); the instance norm -- per image -- runs ONCE over the stacked tensor with the
-    affine parameters picked by image index (sgg_instnorm_*_pair): twice the bytes per launch (a 67 MB pass reaches 5-5.5 TB/s,
-    a 33 MB one 4.1-4.5), half the launches, and per image exactly the arithmetic of two separate calls."""
+    activations: images [:n] belong to ``ua``'s network, [n:] to ``ub``'s.  The convolutions run with each network's weights --
+    one stacked or grouped launch where the kernel has such a form, else per half into slices of one stacked output; the
+    instance norm -- per image -- runs ONCE over the stacked tensor with the affine parameters picked by image index
+    (sgg_instnorm_*_pair): twice the bytes per launch (a 67 MB pass reaches 5-5.5 TB/s, a 33 MB one 4.1-4.5), half the
+    launches, and per image exactly the arithmetic of two separate calls.  The first network's switches govern the pair."""
 
     def __init__(self, ua, ub):
-        assert (ua.name, ua.kind, ua.stride, ua.padding, ua.reflect, ua.norm, ua.act, ua.leak, ua.R, ua.cin, ua.cout) == \
-               (ub.name, ub.kind, ub.stride, ub.padding, ub.reflect, ub.norm, ub.act, ub.leak, ub.R, ub.cin, ub.cout)
-        self.ua, self.ub, self.name = ua, ub, ua.name
+        assert [getattr(ua, f) for f in self.LAYER] == [getattr(ub, f) for f in self.LAYER]
+        self.ua, self.ub = ua, ub
+        for f in self.LAYER:
+            setattr(self, f, getattr(ua, f))
+
+    net = property(lambda self: self.ua.net)
+    drop_layer = property(lambda self: self.ua.drop_layer)
+
+    def _limits(self, gbuf, dy_partial):
+        """The lockstep path's limits: gradients go to the networks' own buffers, the data-gradient epilogue never makes a
+        norm's backward sums (fuse_in_bwd has no paired form, so none can arrive and ``partial`` is None on the way out), and
+        mixed mode runs one network at a time."""
+        assert gbuf is None and dy_partial is None and not (self.ua.net.mixed or self.ub.net.mixed)
+
+    def _halves(self, t):
+        """((unit, the slice of its network's images in the stacked tensor t), ...)."""
+        n = t.shape[0] // 2
+        return (self.ua, slice(0, n)), (self.ub, slice(n, 2 * n))
 
     def geom(self, x):
         """The per-network geometry of a stacked batch: each network convolves its half."""
         return self.ua.geom(x[:x.shape[0] // 2])
 
-    skip_grad = False
-
-    @property
-    def drop_layer(self):
-        return self.ua.drop_layer
-
-    def dropout_(self, t, drop):
-        """_ConvUnit.dropout_ per half of the stacked tensor t: each network masks its own images with its own seed and step
-        counter (two launches), exactly the launches of the one-network-at-a-time step."""
-        n = t.shape[0] // 2
-        self.ua.dropout_(t[:n], drop)
-        self.ub.dropout_(t[n:], drop)
-
-    def _bias_grads(self, dxc):
-        """The bias gradients a dropout site's mask uncovers, as the units without a norm take theirs (bit-identical per half)."""
-        ua, ub = self.ua, self.ub
-        n = dxc.shape[0] // 2
-        if ua.net.group2:
-            K.bias_grad_group2(dxc, ua.net.P.g(ua.name + "_b"), ub.net.P.g(ub.name + "_b"), accumulate=True)
-        else:
-            for u, sl in ((ua, slice(0, n)), (ub, slice(n, 2 * n))):
-                K.bias_grad(dxc[sl], u.net.P.g(u.name + "_b"), accumulate=True)
-
-    def _conv(self, x, out=None, fuse=True):
-        """The convolution of both halves into one stacked output: (g, xc, part, one_launch).  part: the per-chunk (sum, sumsq)
-        rows of xc where the launch's epilogue delivers them for the norm behind it, else None; one_launch: they came from the
-        stacked launch of the two networks' 3x3 halo kernel.  fuse=False (a dropout site in training mode): part is None."""
-        ua, ub = self.ua, self.ub
-        assert out is None or not ua.norm
-        n = x.shape[0] // 2
-        halves = ((ua, slice(0, n)), (ub, slice(n, 2 * n)))
-        g = self.geom(x)
-        na, nb = ua.name, ub.name
-        PA, PB = ua.net.P, ub.net.P
-        fused_act = A.ACT_NONE if ua.norm else ua.act
-        g2 = ua.geom(x) if ua.kind == "conv" else None     # geometry of the stacked batch
-        fuse = fuse and ua.net.fuse_in_stats
-        if ua.kind == "conv" and ua.norm and g.stats_chunks and fuse and g2.pair_ok:
-            # one launch for both networks (per-image weights): 512 blocks, the second round's halo loads run under the
-            # first round's stores
-            wfa, _ = ua.packed(x.dtype)
-            wfb, _ = ub.packed(x.dtype)
-            xc, part = K.conv_fwd_stats_pair(g2, x, wfa, PA.p(na + "_b"), wfb, PB.p(nb + "_b"), n)
-            return g, xc, part, True
-        if ua.kind == "conv" and ua.norm and g.stats_chunks and fuse and (ua.R != 7 or ua.net.fuse_in_stats_stem):
-            xc = torch.empty((2 * n,) + tuple(g.y_shape[1:]), dtype=x.dtype, device=x.device)
-            part = torch.empty((2 * n, g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x.device)
-            for u, sl in halves:
-                wf, _ = u.packed(x.dtype)
-                K.conv_fwd_stats(g, x[sl], wf, u.net.P.p(u.name + "_b"), out=xc[sl], out_partial=part[sl])
-            return g, xc, part, False
-        if ua.kind == "deconv" and ua.norm and fuse and ua.net.fuse_in_stats_deconv and ua.net.group2:
-            gs = ua.geom(x)                                    # the stacked batch: per-image weights in the stride-2 halo kernel
-            if gs.stats_chunks:
-                _, wda = ua.packed(x.dtype)
-                _, wdb = ub.packed(x.dtype)
-                xc, part = K.deconv_fwd_stats(gs, x, wda, PA.p(na + "_b"), pair=(wdb, PB.p(nb + "_b"), n))
-                return g, xc, part, False
-        # every other convolution: ONE grouped launch for both networks (sgg_*_group2: each network's call as its own group of
-        # blocks -- bit-identical to two calls; the discriminators' small maps are latency bound, two half-size launches cost twice)
-        wfa, wda = ua.packed(x.dtype)
-        wfb, wdb = ub.packed(x.dtype)
-        if not ua.net.group2:                                 # A/B switch: one launch per network into slices of the stacked output
-            xc = K._out(out, (2 * n,) + tuple(g.y_shape[1:]), x.dtype, x.device)
-            for u, sl, wf, wd in ((ua, halves[0][1], wfa, wda), (ub, halves[1][1], wfb, wdb)):
-                if u.kind == "conv":
-                    K.conv_fwd(g, x[sl], wf, u.net.P.p(u.name + "_b"), fused_act, u.leak, out=xc[sl])
-                else:
-                    K.deconv_fwd(g, x[sl], wd, u.net.P.p(u.name + "_b"), fused_act, u.leak, out=xc[sl])
-        elif ua.kind == "conv":
-            xc = K.conv_fwd_group2(g, x, wfa, PA.p(na + "_b"), wfb, PB.p(nb + "_b"), fused_act, ua.leak, out=out)
-        else:
-            xc = K.deconv_fwd_group2(g, x, wda, PA.p(na + "_b"), wdb, PB.p(nb + "_b"), fused_act, ua.leak, out=out)
-        return g, xc, None, False
-
-    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
-        ua, ub = self.ua, self.ub
-        n = x.shape[0] // 2
-        if drop is not None:                        # (_ConvUnit.forward: mask the conv output in place, then the plain norm)
-            assert ua.norm and not record_only
-            g, xc, _, _ = self._conv(x, fuse=False)
-            self.dropout_(xc, drop)
-            y, stats = K.instnorm_fwd_pair(xc, *self.affine(), n, residual, ua.net.eps, ua.act, ua.leak)
-            return y, (g, x, xc, stats, drop)
-        g, xc, part, one_launch = self._conv(x, out)
-        if not ua.norm:
-            return xc, (g, x, xc, None)
-        if part is not None:
-            if record_only and one_launch:          # (_ConvUnit.forward: the statistics without the apply pass)
-                return None, (g, x, xc, K.instnorm_finalize(part, xc.shape[1] * xc.shape[2], ua.net.eps))
-            y, stats = K.instnorm_fwd_partial_pair(xc, part, *self.affine(), n, residual, ua.net.eps, ua.act, ua.leak)
-            return y, (g, x, xc, stats)
-        y, stats = K.instnorm_fwd_pair(xc, *self.affine(), n, residual, ua.net.eps, ua.act, ua.leak)
-        return y, (g, x, xc, stats)
-
     def affine(self):
         """(gamma, beta) of the first network's norm, then the second's."""
-        ua, ub = self.ua, self.ub
-        return (ua.net.P.p(ua.name + "_g"), ua.net.P.p(ua.name + "_beta"), ub.net.P.p(ub.name + "_g"), ub.net.P.p(ub.name + "_beta"))
+        return self.ua.affine() + self.ub.affine()
 
-    def _norm_grads(self, param_grads):
-        """Where the norm backward puts (dgamma, dbeta) of the two networks."""
-        ua, ub = self.ua, self.ub
-        if param_grads:
-            return (ua.net.P.g(ua.name + "_g"), ua.net.P.g(ua.name + "_beta"), ub.net.P.g(ub.name + "_g"), ub.net.P.g(ub.name + "_beta"))
-        # gradients w.r.t. gamma / beta not wanted: send them to scratch
-        sa, sb = ua.net.scratch_vec(K.cpad(ua.cout)), ub.net.scratch_vec(K.cpad(ub.cout))
-        return (sa, sa, sb, sb)
+    def dropout_(self, t, drop):
+        """Each network masks its own images with its own seed and step counter (two launches): exactly the launches of the
+        one-network-at-a-time step."""
+        for u, sl in self._halves(t):
+            u.dropout_(t[sl], drop)
 
-    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
-        """_ConvUnit.backward's signature and return convention ((dx, partial) when next_norm is given), with the lockstep
-        path's limits: gradients go to the networks' own buffers, the data-gradient epilogue never makes the next norm's
-        sums (fuse_in_bwd has no paired form: partial is None), and mixed mode runs one network at a time."""
+    def _conv(self, x, out, fuse):
+        """The convolution of both halves into one stacked output: (g, xc, part, whole).  part: the statistics rows of xc
+        where _epilogue_stats says the launches deliver them, else None; whole: they came from ONE launch over the stacked
+        batch (the two networks' 3x3 halo kernel), not from one launch per half."""
         ua, ub = self.ua, self.ub
-        assert gbuf is None and dy_partial is None and not (ua.net.mixed or ub.net.mixed)
-        g, x, xc, stats, *drop = rec
         n = x.shape[0] // 2
-        na, nb = ua.name, ub.name
-        PA, PB = ua.net.P, ub.net.P
-        if ua.norm:
-            dxc = K.instnorm_bwd_pair(dy, xc, *self.affine(), n, stats, *self._norm_grads(param_grads), param_grads, ua.act, ua.leak)
-            # (the conv bias in front of an instance norm has an identically zero gradient: left at 0 -- unless a mask sits
-            # between them, _ConvUnit.backward)
-            if drop:
-                assert next_norm is None
-                self.dropout_(dxc, drop[0])
-                if param_grads:
-                    self._bias_grads(dxc)
+        g = self.geom(x)
+        conv = self.kind == "conv"
+        stats = self._epilogue_stats(g, fuse)
+        gs = ua.geom(x) if stats else None                     # the stacked batch: one launch with per-image weights
+        if stats and conv and not gs.pair_ok:                  # no such form: one launch per network
+            xc = torch.empty((2 * n,) + tuple(g.y_shape[1:]), dtype=x.dtype, device=x.device)
+            part = torch.empty((2 * n, g.stats_chunks, g.y_shape[3], 2), dtype=torch.float32, device=x.device)
+            for u, sl in self._halves(x):
+                K.conv_fwd_stats(g, x[sl], u.packed(x.dtype)[0], u.net.P.p(self.name + "_b"), out=xc[sl], out_partial=part[sl])
+            return g, xc, part, False
+        (wfa, wda), (wfb, wdb) = ua.packed(x.dtype), ub.packed(x.dtype)
+        ba, bb = ua.net.P.p(self.name + "_b"), ub.net.P.p(self.name + "_b")
+        if stats and conv:
+            # the 3x3 halo kernel: 512 blocks, the second round's halo loads run under the first round's stores
+            return (g,) + K.conv_fwd_stats_pair(gs, x, wfa, ba, wfb, bb, n) + (True,)
+        if stats and self.net.group2:                          # (the transposed layers' stride-2 halo kernel)
+            return (g,) + K.deconv_fwd_stats(gs, x, wda, ba, pair=(wdb, bb, n)) + (False,)
+        # every other convolution: ONE grouped launch for both networks (sgg_*_group2: each network's call as its own group of
+        # blocks -- bit-identical to two calls; the discriminators' small maps are latency bound, two half-size launches cost twice)
+        fused_act = A.ACT_NONE if self.norm else self.act
+        if not self.net.group2:                               # A/B switch: one launch per network into slices of the stacked output
+            xc = K._out(out, (2 * n,) + tuple(g.y_shape[1:]), x.dtype, x.device)
+            for (u, sl), w, bias in zip(self._halves(x), (wfa if conv else wda, wfb if conv else wdb), (ba, bb)):
+                (K.conv_fwd if conv else K.deconv_fwd)(g, x[sl], w, bias, fused_act, self.leak, out=xc[sl])
+        elif conv:
+            xc = K.conv_fwd_group2(g, x, wfa, ba, wfb, bb, fused_act, self.leak, out=out)
         else:
-            dxc = K.act_bwd(dy, xc, ua.act, ua.leak) if ua.act != A.ACT_NONE else dy
-            if param_grads and ua.net.group2:
-                K.bias_grad_group2(dxc, PA.g(na + "_b"), PB.g(nb + "_b"), accumulate=True)
-            elif param_grads:
-                for u, sl in ((ua, slice(0, n)), (ub, slice(n, 2 * n))):
-                    K.bias_grad(dxc[sl], u.net.P.g(u.name + "_b"), accumulate=True)
-        dx = self._conv_backward(g, x, dxc, want_dx, param_grads, addend)
-        return (dx, None) if next_norm is not None else dx
+            xc = K.deconv_fwd_group2(g, x, wda, ba, wdb, bb, fused_act, self.leak, out=out)
+        return g, xc, None, False
 
-    def _conv_backward(self, g, x, dxc, want_dx, param_grads, addend):
-        """Weight gradients of both networks, then the stacked data gradient (+ addend)."""
+    def _norm(self, xc, addend, part):
+        ga, ba, gb, bb = self.affine()
+        return K.instnorm_forward(xc, ga, ba, addend, self.net.eps, self.act, self.leak, skip=self.skip_grad, partial=part,
+                                  pair=(gb, bb, xc.shape[0] // 2))
+
+    def _norm_backward(self, dy, xc, stats, y, part, param_grads, gbuf):
         ua, ub = self.ua, self.ub
-        n = x.shape[0] // 2
-        halves = ((ua, slice(0, n)), (ub, slice(n, 2 * n)))
-        na, nb = ua.name, ub.name
-        PA, PB = ua.net.P, ub.net.P
+        ga, ba, gb, bb = self.affine()
         if param_grads:
-            # both networks have this layer's first application waiting (pair_wgrads): all four weight gradients in ONE launch
-            pa, pb = ua._pending, ub._pending
-            quad = (ua.kind == "conv" and g.wgrad_pair and ua.net.pair_wgrads and ub.net.pair_wgrads and pa is not None and pb is not None
-                    and pa[0].x_shape == g.x_shape and pb[0].x_shape == g.x_shape)
-            defer = ua.kind == "conv" and g.wgrad_pair and (ua.net.pair_wgrads or ub.net.pair_wgrads)   # the 3x3 layers' two-application form
-            if quad and K.conv_wgrad_pair2(g, (pa[1], pa[2], x[halves[0][1]], dxc[halves[0][1]], PA.g(na + "_w")),
-                                           (pb[1], pb[2], x[halves[1][1]], dxc[halves[1][1]], PB.g(nb + "_w")), accumulate=True):
-                ua._pending = ub._pending = None
-            elif ua.net.group2 and not defer and pa is None and pb is None:
-                # both networks' weight gradients as one grouped call: two main kernels, one slab reduce (bit-identical to two calls)
-                K.conv_wgrad_group2(g, x, dxc, PA.g(na + "_w"), PB.g(nb + "_w"), accumulate=True)
-            else:
-                for u, sl in halves:
-                    u.weight_grad(g, x[sl], dxc[sl])
-        if not want_dx:
-            return None
-        if ua.kind == "conv" and ua.geom(x).pair_ok:
-            return K.conv_dgrad_pair(ua.geom(x), dxc, ua.packed(x.dtype)[1], ub.packed(x.dtype)[1], n, addend)
-        wfa, wda = ua.packed(x.dtype)
-        wfb, wdb = ub.packed(x.dtype)
-        if not ua.net.group2:
-            dx = torch.empty((2 * n,) + tuple(g.x_shape[1:]), dtype=dxc.dtype, device=dxc.device)
-            for u, sl, wf, wd in ((ua, halves[0][1], wfa, wda), (ub, halves[1][1], wfb, wdb)):
-                if u.kind == "conv":
-                    K.conv_dgrad(g, dxc[sl], wd, None if addend is None else addend[sl], out=dx[sl])
-                else:
-                    K.deconv_dgrad(g, dxc[sl], wf, out=dx[sl])
-            return dx if (ua.kind == "conv" or addend is None) else K.add(dx, addend)
-        if ua.kind == "conv":
-            return K.conv_dgrad_group2(g, dxc, wda, wdb, addend)
-        dx = K.deconv_dgrad_group2(g, dxc, wfa, wfb)
-        return dx if addend is None else K.add(dx, addend)
+            dga, dba, dgb, dbb = (u.net.P.g(self.name + k) for u in (ua, ub) for k in ("_g", "_beta"))
+        else:   # gradients w.r.t. gamma / beta not wanted: send them to scratch
+            dga = dba = ua.net.scratch_vec(K.cpad(self.cout))
+            dgb = dbb = ub.net.scratch_vec(K.cpad(self.cout))
+        return K.instnorm_backward(dy, xc, ga, ba, stats, dga, dba, param_grads, self.act, self.leak, y=y,
+                                   pair=(gb, bb, xc.shape[0] // 2, dgb, dbb))
 
+    def _bias_grad(self, dxc, gbuf):
+        """As the one-network units take theirs (bit-identical per half)."""
+        if self.net.group2:
+            K.bias_grad_group2(dxc, self.ua.net.P.g(self.name + "_b"), self.ub.net.P.g(self.name + "_b"), accumulate=True)
+        else:
+            for u, sl in self._halves(dxc):
+                K.bias_grad(dxc[sl], u.net.P.g(self.name + "_b"), accumulate=True)
 
-class _PairSkipActUnit(_PairUnit):
-    """_SkipActUnit of two networks in lockstep: y = act(IN(conv(x)) + skip) on the stacked batch (the U-Net generators' d3 / d7
-    in the cycle step).  The convolution takes _PairUnit's paths; the norm is sgg_instnorm_*_skip_pair.  The forward record
-    carries y, and backward returns (dx, dskip), both stacked."""
+    def weight_grad(self, g, x, dxc, gbuf=None):
+        """The weight gradients of both networks."""
+        ua, ub = self.ua, self.ub
+        (_, a), (_, b) = self._halves(x)
+        xa, xb, da, db = x[a], x[b], dxc[a], dxc[b]
+        dwa, dwb = ua.net.P.g(self.name + "_w"), ub.net.P.g(self.name + "_w")
+        # both networks have this layer's first application waiting (pair_wgrads): all four weight gradients in ONE launch
+        pa, pb = ua._pending, ub._pending
+        pairable = self.kind == "conv" and g.wgrad_pair                      # the 3x3 layers' two-application form
+        quad = (pairable and ua.net.pair_wgrads and ub.net.pair_wgrads and pa is not None and pb is not None
+                and pa[0].x_shape == g.x_shape and pb[0].x_shape == g.x_shape)
+        defer = pairable and (ua.net.pair_wgrads or ub.net.pair_wgrads)
+        if quad and K.conv_wgrad_pair2(g, (pa[1], pa[2], xa, da, dwa), (pb[1], pb[2], xb, db, dwb), accumulate=True):
+            ua._pending = ub._pending = None
+        elif self.net.group2 and not defer and pa is None and pb is None:
+            # both networks' weight gradients as one grouped call: two main kernels, one slab reduce (bit-identical to two calls)
+            K.conv_wgrad_group2(g, x, dxc, dwa, dwb, accumulate=True)
+        else:
+            ua.weight_grad(g, xa, da)
+            ub.weight_grad(g, xb, db)
 
-    skip_grad = True
-
-    def forward(self, x, residual=None, record_only=False, out=None, drop=None):
-        assert residual is not None and out is None and not record_only and self.ua.norm
-        ua = self.ua
-        g, xc, part, _ = self._conv(x, fuse=drop is None)
-        if drop is not None:
-            self.dropout_(xc, drop)
-        y, stats = K.instnorm_fwd_skip_pair(xc, *self.affine(), x.shape[0] // 2, residual, ua.net.eps, ua.act, ua.leak, partial=part)
-        return y, (g, x, xc, stats, y) + (() if drop is None else (drop,))
-
-    def backward(self, rec, dy, want_dx=True, param_grads=True, gbuf=None, addend=None, dy_partial=None, next_norm=None):
-        assert gbuf is None and addend is None and dy_partial is None and next_norm is None
-        ua = self.ua
-        g, x, xc, stats, y, *drop = rec
-        dxc, dskip = K.instnorm_bwd_skip_pair(dy, y, xc, *self.affine(), x.shape[0] // 2, stats, *self._norm_grads(param_grads),
-                                              param_grads, ua.act, ua.leak)
-        if drop:
-            self.dropout_(dxc, drop[0])
-            if param_grads:
-                self._bias_grads(dxc)
-        return self._conv_backward(g, x, dxc, want_dx, param_grads, None), dskip
+    def _data_grad(self, g, x, dxc, addend, next_norm):
+        """(the stacked data gradient + addend, None)."""
+        ua, ub = self.ua, self.ub
+        conv = self.kind == "conv"
+        (wfa, wda), (wfb, wdb) = ua.packed(x.dtype), ub.packed(x.dtype)
+        if conv and ua.geom(x).pair_ok:
+            return K.conv_dgrad_pair(ua.geom(x), dxc, wda, wdb, x.shape[0] // 2, addend), None
+        if conv and self.net.group2:
+            return K.conv_dgrad_group2(g, dxc, wda, wdb, addend), None
+        if conv:
+            dx = torch.empty(tuple(x.shape), dtype=dxc.dtype, device=dxc.device)
+            for (u, sl), wd in zip(self._halves(x), (wda, wdb)):
+                K.conv_dgrad(g, dxc[sl], wd, None if addend is None else addend[sl], out=dx[sl])
+            return dx, None
+        if self.net.group2:
+            dx = K.deconv_dgrad_group2(g, dxc, wfa, wfb)
+        else:
+            dx = torch.empty(tuple(x.shape), dtype=dxc.dtype, device=dxc.device)
+            for (u, sl), wf in zip(self._halves(x), (wfa, wfb)):
+                K.deconv_dgrad(g, dxc[sl], wf, out=dx[sl])
+        return (dx if addend is None else K.add(dx, addend.to(dx.dtype))), None
 
 
 def _pair_units(xs, ys):
-    """The lockstep units of two networks' unit lists (a skip-gradient unit pairs into its own lockstep kind)."""
-    return [(_PairSkipActUnit if ua.skip_grad else _PairUnit)(ua, ub) for ua, ub in zip(xs, ys)]
+    """The lockstep units of two networks' unit lists."""
+    return [_PairUnit(ua, ub) for ua, ub in zip(xs, ys)]
 
 
 class GeneratorPair(_ResNetWalk):

@@ -165,7 +165,7 @@ def _close(got, exp, what, bar=2e-4, entry=1e-3):
 
 @pytest.mark.parametrize("name", ["d1", "d3"])
 def test_dropout_unit_forward_backward_against_float64(sg, name):
-    """A d1-type unit (deconv -> mask -> IN -> + skip) and the d3-type _SkipActUnit (... -> ReLU), f32, N 2, 16x16, 64 -> 64
+    """A d1-type unit (deconv -> mask -> IN -> + skip) and the d3-type unit with skip_grad (... -> ReLU), f32, N 2, 16x16, 64 -> 64
     channels, forward and backward with dropout against float64: y, dx, dW, db (non-zero), dgamma, dbeta and the skip gradient.
     The ReLU of the d3 form takes its decisions from the kernel's own output.  Bars of tests/test_gpu_unet.py: image 1e-4,
     gradients relative L2 2e-4, single entries 1e-3 of the tensor's largest."""

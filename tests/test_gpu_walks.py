@@ -50,7 +50,7 @@ def test_layers_complete_in_reverse_layer_order_single_and_pair(M, arch, ckpt):
 
 
 def test_pair_unit_backward_keeps_the_unit_protocol_within_its_limits(M):
-    """A lockstep unit takes _ConvUnit.backward's arguments but has no form for a caller's gradient buffer or for
+    """A lockstep unit runs the one backward of the units (_Unit.backward) but has no form for a caller's gradient buffer or for
     norm-backward sums made by the previous data gradient: both are refused (AssertionError, before anything is launched).
     With ``next_norm`` it returns (dx, None) -- its data-gradient epilogue never makes the next norm's sums -- and dx is the
     same bits as without.  One stride-1 SAME 3x3 conv + instance norm pair unit, 8 -> 8 channels, 2x16x16, f32 (the first
