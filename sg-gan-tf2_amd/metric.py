@@ -63,27 +63,11 @@ def _fast_hist(label_true, label_pred, n_class):
 
 
 def scores(label_trues, label_preds, n_class):
-    """metric.py:27-47 -- the FCN score set (same keys).  The confusion matrix of ALL pairs is accumulated on the device
-    in one int64 buffer (exact, order independent) and read back once; the five scores are then ratios of its
-    per-class true-positive / ground-truth / prediction counts."""
+    """metric.py:27-47 -- the FCN score set: ONE int64 confusion matrix of ALL pairs on the device (exact), read back by ``scores_from_hist``."""
     hist = torch.zeros(n_class * n_class, dtype=torch.int64, device="cuda")
     for lt, lp in zip(label_trues, label_preds):
         _accumulate_hist(hist, lt, lp, n_class)
-    h = hist.view(n_class, n_class).cpu().numpy()
-    tp = np.diagonal(h).astype(np.float64)            # correctly labelled pixels per class
-    n_true = h.sum(axis=1).astype(np.float64)         # pixels whose ground truth is the class
-    n_pred = h.sum(axis=0).astype(np.float64)         # pixels predicted as the class
-    total = float(h.sum())
-    with np.errstate(divide="ignore", invalid="ignore"):
-        iou = tp / (n_true + n_pred - tp)
-        seen = n_true > 0
-        share = n_true / total
-        out = {"Overall Acc": tp.sum() / total,
-               "Mean Acc": np.nanmean(tp / n_true),
-               "FreqW Acc": (share[share > 0] * iou[share > 0]).sum(),
-               "Mean IoU": np.nanmean(iou[seen]),
-               "Class IoU": {c: iou[c] for c in range(n_class)}}
-    return out
+    return scores_from_hist(hist)
 
 
 def argmax_u8_labels(img, c_real=None):
@@ -194,13 +178,13 @@ def palette_probs(img, n_class, palette=None, sigma=32.0, other_class=0, max_dis
 
 
 def scores_from_hist(hist):
-    """The FCN score set of ``scores`` (same five keys) from a confusion matrix (n_class, n_class) or its flat form."""
+    """metric.py:27-47 -- the FCN score set (five keys) from a confusion matrix (n_class, n_class) or its flat form, tensor (ONE read-back) or array."""
     h = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
     n_class = int(round(np.sqrt(h.size)))
     h = h.reshape(n_class, n_class)
-    tp = np.diagonal(h).astype(np.float64)
-    n_true = h.sum(axis=1).astype(np.float64)
-    n_pred = h.sum(axis=0).astype(np.float64)
+    tp = np.diagonal(h).astype(np.float64)            # correctly labelled pixels per class
+    n_true = h.sum(axis=1).astype(np.float64)         # pixels whose ground truth is the class
+    n_pred = h.sum(axis=0).astype(np.float64)         # pixels predicted as the class
     total = float(h.sum())
     with np.errstate(divide="ignore", invalid="ignore"):
         iou = tp / (n_true + n_pred - tp)
@@ -390,8 +374,3 @@ def sliced_wasserstein(fakes, reals, batch=16, **kw):
         for i in range(0, n, batch):
             s._add(which, imgs[i:i + batch])
     return s.result()
-
-
-def swd_scalars(res):
-    """[(scalar name, value) ...] of an ``SWD.result()`` in the order the test pass logs them: the levels finest first, the mean."""
-    return [("SWD %dx%d" % (h, w), v) for h, w, v in res["levels"]] + [("SWD Mean", res["mean"])]

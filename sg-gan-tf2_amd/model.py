@@ -10,16 +10,18 @@ from __future__ import annotations
 
 import contextlib
 import math
+import os
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _abi as A
+from . import evaluate as E
 from . import kernels as K
 from .graph import StepProgram
 from .module import Adam, check_d_norm, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet, GeneratorUNetPair
-from .utils import ImagePool, StaticImagePool
+from .utils import ImagePool, save_images, StaticImagePool
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32,
            "float32": torch.float32, torch.bfloat16: torch.bfloat16, torch.float32: torch.float32}
@@ -52,6 +54,7 @@ class sggan(object):
     # model.py:205 ``lr = 0.001`` (hard-coded; --lr is ignored) -- SURVEY.md 5 "Config / flags".
     LAMBDA = 100.0
     LR = 0.001
+    _swd_add_reals = staticmethod(E.swd_add_reals)      # (the name the SWD tests call it by)
 
     def __init__(self, args=None, **kw):
         args = args if args is not None else default_args(**kw)
@@ -899,7 +902,6 @@ class sggan(object):
 
     def _ckpt_paths(self, checkpoint_dir, ep=None):
         """model.py:454-456: <checkpoint_dir>/<dataset_dir>/{gen,disc}/cp-{epoch:04d}.ckpt"""
-        import os
         base = os.path.join(checkpoint_dir, self.dataset_dir)
         f = (lambda sub: os.path.join(base, sub, "cp-%04d.ckpt" % ep)) if ep is not None else (lambda sub: os.path.join(base, sub))
         return f("gen"), f("disc")
@@ -907,7 +909,6 @@ class sggan(object):
     def save(self, checkpoint_dir, ep):
         """model.py:450-468 (weights per network under gen/ and disc/), plus what the reference omits: the Adam
         slots and step counts, so training resumes exactly (SURVEY.md 5 "Checkpoint / resume")."""
-        import os
         gpath, dpath = self._ckpt_paths(checkpoint_dir, ep)
         sd = self.state_dict()
         for path, keys in ((gpath, ("G", "G_BA")), (dpath, ("D", "D_B"))):
@@ -941,205 +942,45 @@ class sggan(object):
         return as_np(test_label).transpose(0, 3, 2, 1), as_np(pred_img).transpose(0, 3, 2, 1)
 
     def test_during_train(self, epoch, args, samples, sink=None, swd_reals=None):
-        """model.py:307-448 (the live part; of the CRF variants, commented out there, scores_mask_sample_crf runs with --crf): every
-        test sample -- ``samples`` yields (name, sample_image (H,W,3) in [0,1], seg_image (H,W,3) in [0,1]); reading and
-        resizing the files (utils.load_test_data) stays on the caller's side -- is rescaled like the reference does
-        (tf.image.convert_image_dtype -> uint8 -> float32), translated by the generator, optionally saved under
-        ``args.test_dir``, and labelled against its segmentation image (metric.scores_seg_fake); the FCN scores of all labels
-        go to ``sink`` under the reference's scalar names.  Returns (the stacked fake images as model.py:440-448 does, scores).
-        With ``args.crf`` the samples carry a fourth element, load_test_data's full-resolution one-hot class mask (H,W,C), each
-        is also scored by metric.scores_mask_sample_crf (model.py:314-315 keeps the lists for it), and the four FCN scores of
-        those labels follow the reference's four in ``sink`` as 'CRF Overall Accuracy' ... 'CRF Mean IoU' (and in the returned
-        scores under "CRF").
-        With ``args.class_scores`` the samples carry that mask too; its argmax is the ground-truth class map, the
-        translation is decoded to classes through ``args.class_palette`` (segment_class.learn_palette; None: the built-in table)
-        and ONE confusion matrix per score is accumulated on the device over all samples and read back once.  After the scalars
-        above follow 'Class Overall Accuracy' ... 'Class Mean IoU', with ``args.boundary_px`` > 0 'Boundary Class Mean IoU' (the
-        pixels within that distance of a ground-truth class boundary), and with ``args.crf`` as well the four 'Class CRF ...'
-        scores of the CRF-refined map (metric.scores_class_fake_crf); the returned scores gain "Class", "Class Boundary" and
-        "Class CRF".
-        With ``args.image_scores`` every translation is also compared, as the 8-bit image ``save_images`` writes,
-        with the 8-bit label image ``convert_image_dtype_uint8(seg_image)`` (metric.scores_image_fake: the sums stay on the
-        device and are read back once); 'Image MAE', 'Image PSNR' and 'Image SSIM' follow the scalars above and the returned
-        scores gain "Image".  A cycle model also scores the reconstruction ``generator_BA(fake_A)`` against the 8-bit input,
-        under the same weights as the translation: 'Cycle MAE', 'Cycle PSNR', 'Cycle SSIM' and "Cycle".
-        With ``args.swd`` every translation also goes, as that 8-bit image, into the fakes of a sliced Wasserstein
-        distance of Laplacian-pyramid patches (metric.SWD, ``args.swd_patches`` descriptors per level and image); the reals are
-        the samples' own 8-bit label images, or, where ``swd_reals`` is given, the (H,W,3) images in [0,1] it yields (a callable
-        is called first), converted like everything else -- an unpaired set, of which as many are used as there are fakes.
-        'SWD <h>x<w>' per pyramid level, finest first, and 'SWD Mean' follow the scalars above; the returned scores gain "SWD".
-        A model built with ``ema_decay`` translates with the moving average of the generator's weights
-        (ema_weights) and logs 'EMA Decay', the decay its last applied update used, after all the scalars above."""
-        from . import metric as M
-        from .utils import convert_image_dtype_uint8, get_img, save_images
-        import os
-        gts, preds, outputs = [], [], []
-        crf = bool(getattr(args, "crf", False))
-        gts2, preds2 = [], []
-        class_scores = bool(getattr(args, "class_scores", False))
-        if class_scores:
-            n_class, class_palette = args.segment_class, getattr(args, "class_palette", None)
-            band_px = int(getattr(args, "boundary_px", 3))
-            far = int(getattr(args, "class_max_dist", -1))
-            decode = dict(max_dist2=far * far if far >= 0 else -1)
-            class_hist = {k: torch.zeros((n_class, n_class), dtype=torch.int64, device=self.device)
-                          for k, on in (("Class", True), ("Class Boundary", band_px > 0), ("Class CRF", crf)) if on}
-        image_scores = bool(getattr(args, "image_scores", False))
-        image_acc, cycle_acc = [], []
-        test_dir = getattr(args, "test_dir", None)
-        swd = None
-        if getattr(args, "swd", False):
-            if not hasattr(samples, "__len__"):     # the set-wide descriptor buffers are sized once
-                samples = list(samples)
-            swd = M.SWD(self.image_height, self.image_width, max(len(samples), 1), patches=int(getattr(args, "swd_patches", 128)),
-                        device=self.device)
-        with self._test_weights():                  # (the moving average, where the model keeps one)
-            for item in samples:
-                name, sample_image, seg_image = item[:3]
-                rescaled = convert_image_dtype_uint8(np.asarray(sample_image)[None])                 # :352-353
-                fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))                   # :357
-                if test_dir:
-                    os.makedirs(test_dir, exist_ok=True)
-                    save_images(fake_A, [1, 1], os.path.join(test_dir, os.path.basename(name)))      # :362-365
-                fake_img = get_img(fake_A, [1, 1])                                                   # :369
-                outputs.append(fake_img)
-                if image_scores:
-                    M.scores_image_fake(convert_image_dtype_uint8(np.asarray(seg_image)[None]).astype(np.uint8), fake_A, image_acc)
-                    if self.cycle:
-                        M.scores_image_fake(rescaled.astype(np.uint8), self.generator_BA(fake_A), cycle_acc)
-                if swd is not None:
-                    swd.add_fakes(fake_A)
-                    if swd_reals is None:
-                        swd.add_reals(convert_image_dtype_uint8(np.asarray(seg_image)[None]).astype(np.uint8))
-                lt, lp = M.scores_seg_fake(np.asarray(seg_image, dtype=np.float32)[None], torch.as_tensor(fake_img.astype(np.float32)))   # :373
-                preds += list(lp); gts += list(lt)
-                if crf:
-                    if len(item) < 4:
-                        raise ValueError("crf: test samples must carry the one-hot class mask (data.directory_test_samples over a "
-                                         "DatasetCache(with_class=True))")
-                    lt2, lp2 = M.scores_mask_sample_crf(np.asarray(item[3])[None], rescaled)          # :330,338 seg_mask_64
-                    preds2 += list(lp2); gts2 += list(lt2)
-                if class_scores:
-                    if len(item) < 4:
-                        raise ValueError("class_scores: test samples must carry the one-hot class mask (data.directory_test_samples "
-                                         "over a DatasetCache(with_class=True))")
-                    truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
-                    M.scores_class_fake(truth, fake_A, n_class, class_palette, hist=class_hist["Class"], **decode)
-                    if "Class Boundary" in class_hist:
-                        M.scores_class_fake(truth, fake_A, n_class, class_palette, band_radius=band_px, hist=class_hist["Class Boundary"], **decode)
-                    if crf:
-                        M.scores_class_fake_crf(truth, rescaled, fake_A, n_class, class_palette, hist=class_hist["Class CRF"], **decode)
-        score = M.scores(gts, preds, n_class=args.segment_class)                                 # :378
-        if sink is not None:                                                                     # :389-393
-            sink.scalar("Overall Accuracy", score["Overall Acc"], epoch)
-            sink.scalar("Mean Accuracy", score["Mean Acc"], epoch)
-            sink.scalar("Frequency Weighted Accuracy", score["FreqW Acc"], epoch)
-            sink.scalar("Mean IoU", score["Mean IoU"], epoch)
-        if crf:
-            score["CRF"] = crf_score = M.scores(gts2, preds2, n_class=args.segment_class)
-            if sink is not None:
-                sink.scalar("CRF Overall Accuracy", crf_score["Overall Acc"], epoch)
-                sink.scalar("CRF Mean Accuracy", crf_score["Mean Acc"], epoch)
-                sink.scalar("CRF Frequency Weighted Accuracy", crf_score["FreqW Acc"], epoch)
-                sink.scalar("CRF Mean IoU", crf_score["Mean IoU"], epoch)
-        if class_scores:
-            for key, h in class_hist.items():
-                score[key] = M.scores_from_hist(h)
-            if sink is not None:
-                self._class_scalars(sink, "Class ", score["Class"], epoch)
-                if "Class Boundary" in score:
-                    sink.scalar("Boundary Class Mean IoU", score["Class Boundary"]["Mean IoU"], epoch)
-                if "Class CRF" in score:
-                    self._class_scalars(sink, "Class CRF ", score["Class CRF"], epoch)
-        for key, acc in (("Image", image_acc), ("Cycle", cycle_acc)):
-            if acc:
-                score[key] = q = M.scores_from_quality(acc)
-                if sink is not None:
-                    sink.scalar(key + " MAE", q["MAE"], epoch)
-                    sink.scalar(key + " PSNR", q["PSNR"], epoch)
-                    sink.scalar(key + " SSIM", q["SSIM"], epoch)
-        if swd is not None and swd.count["fakes"]:
-            self._swd_add_reals(swd, swd_reals)
-            score["SWD"] = res = swd.result()
-            if sink is not None:
-                for key, value in M.swd_scalars(res):
-                    sink.scalar(key, value, epoch)
-        if self.ema_decay is not None and sink is not None:     # the decay the generator's last applied update used
-            sink.scalar("EMA Decay", float(self.generator.P._ema_state[0].item()), epoch)
+        """model.py:307-448 (the live part): every test sample -- ``samples`` yields (name, sample_image (H,W,3) in [0,1], seg_image (H,W,3)
+        in [0,1][, one-hot class mask (H,W,C)]); reading and resizing the files stays with the caller -- is translated, optionally saved under
+        ``args.test_dir``, and scored (evaluate.py) by the reference's FCN scores and by the scorers that ``args.crf`` / ``class_scores`` /
+        ``image_scores`` / ``swd`` name, which need their element of EVERY sample.  Returns (the stacked fakes as model.py:440-448, the scores)."""
+        optional = {"crf": E.CrfLabels(args.segment_class),
+                    "class_scores": E.ClassHists(args, self.device, int(getattr(args, "boundary_px", 3)), getattr(args, "crf", False)),
+                    "image_scores": E.ImageQuality(self.generator_BA if self.cycle else None), "swd": E.Swd(self, args, swd_reals)}
+        scorers = [E.SegLabels(args.segment_class)] + [sc for option, sc in optional.items() if getattr(args, option, False)]
+        def each(s):
+            if getattr(args, "test_dir", None):
+                os.makedirs(args.test_dir, exist_ok=True)
+                save_images(s.fake, [1, 1], os.path.join(args.test_dir, os.path.basename(s.name)))     # :362-365
+            return s.fake_img
+        outputs, results = E.run(self, samples, scorers, each, strict=True)
+        score = {k: v for res in results for k, v in res.items()}
+        if sink is not None:                                                                         # :389-393
+            decay = float(self.generator.P._ema_state[0].item()) if self.ema_decay is not None else None
+            for tag, value in E.scalars(score, decay):
+                sink.scalar(tag, value, epoch)
         return (np.concatenate(outputs, axis=0) if outputs else None), score
 
-    @staticmethod
-    def _swd_add_reals(swd, swd_reals):
-        """The unpaired reals of a test pass: (H,W,3) images in [0,1], as many as there are fakes."""
-        from .utils import convert_image_dtype_uint8
-        if swd_reals is None:
-            return
-        for img in (swd_reals() if callable(swd_reals) else swd_reals):
-            if swd.count["reals"] >= swd.count["fakes"]:
-                break
-            swd.add_reals(convert_image_dtype_uint8(np.asarray(img)[None]).astype(np.uint8))
-
-    @staticmethod
-    def _class_scalars(sink, prefix, s, epoch):
-        sink.scalar(prefix + "Overall Accuracy", s["Overall Acc"], epoch)
-        sink.scalar(prefix + "Mean Accuracy", s["Mean Acc"], epoch)
-        sink.scalar(prefix + "Frequency Weighted Accuracy", s["FreqW Acc"], epoch)
-        sink.scalar(prefix + "Mean IoU", s["Mean IoU"], epoch)
-
     def test(self, args, samples, log=print):
-        """model.py:535-567 (--phase test): load the latest checkpoint, translate every test sample and save the input and the
-        translation under ``args.test_dir``.  ``samples`` yields (name, sample_image (H,W,3) in [0,1]).  With
-        ``args.class_scores`` and samples that carry the one-hot class mask as their fourth element, the four class-level scores
-        of the translations are logged at the end; with ``args.image_scores`` and samples that carry their label
-        image as the third element, 'Image MAE / PSNR / SSIM' of the translations against it; with ``args.swd``
-        one line 'SWD <h>x<w>: ... SWD Mean: ...'  against ``args.swd_reals`` (images (H,W,3) in [0,1]) where that is
-        set, else against the label images of the samples that carry one.  A model built with ``ema_decay`` translates with the moving
-        average of the generator's weights, as the checkpoint holds it."""
-        from . import metric as M
-        from .utils import convert_image_dtype_uint8, save_images
-        import os
-        class_hist, image_acc = None, []
-        swd, swd_reals = None, getattr(args, "swd_reals", None)
-        if getattr(args, "swd", False):
-            if not hasattr(samples, "__len__"):
-                samples = list(samples)
-            swd = M.SWD(self.image_height, self.image_width, max(len(samples), 1), patches=int(getattr(args, "swd_patches", 128)),
-                        device=self.device)
+        """model.py:535-567 (--phase test): load the latest checkpoint, translate every test sample -- (name, sample_image (H,W,3) in [0,1][, label
+        image[, one-hot class mask]]) --, save the input and the translation under ``args.test_dir``; the scorers (evaluate.py) of ``class_scores``
+        ("Class" alone), ``image_scores`` and ``swd`` (``args.swd_reals`` where set) score the samples that carry what they need.  Returns the fakes."""
+        optional = {"class_scores": E.ClassHists(args, self.device), "image_scores": E.ImageQuality(),
+                    "swd": E.Swd(self, args, getattr(args, "swd_reals", None))}
+        scorers = [sc for option, sc in optional.items() if getattr(args, option, False)]
         log(" [*] Running Test ...")
         log(" [*] Load SUCCESS" if self.load(args.checkpoint_dir) else " [!] Load failed...")
         os.makedirs(args.test_dir, exist_ok=True)
-        out = []
-        with self._test_weights():                  # (the moving average, where the model keeps one)
-            for item in samples:
-                name, sample_image = item[0], np.asarray(item[1], dtype=np.float32)
-                log("Processing image: " + name)
-                rescaled = convert_image_dtype_uint8(sample_image[None])
-                fake_A = self.generator(torch.as_tensor(rescaled).to(self.device))
-                save_images(sample_image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(name)))
-                save_images(fake_A, [1, 1], os.path.join(args.test_dir, os.path.basename(name)))
-                out.append(fake_A)
-                if swd is not None:
-                    swd.add_fakes(fake_A)
-                    if swd_reals is None and len(item) >= 3:
-                        swd.add_reals(convert_image_dtype_uint8(np.asarray(item[2])[None]).astype(np.uint8))
-                if getattr(args, "image_scores", False) and len(item) >= 3:
-                    M.scores_image_fake(convert_image_dtype_uint8(np.asarray(item[2])[None]).astype(np.uint8), fake_A, image_acc)
-                if getattr(args, "class_scores", False) and len(item) >= 4:
-                    truth = torch.argmax(torch.as_tensor(np.asarray(item[3])).to(self.device), dim=-1).to(torch.uint8)[None]
-                    far = int(getattr(args, "class_max_dist", -1))
-                    class_hist = M.scores_class_fake(truth, fake_A, args.segment_class, getattr(args, "class_palette", None), hist=class_hist,
-                                                     max_dist2=far * far if far >= 0 else -1)
-        if class_hist is not None:
-            s = M.scores_from_hist(class_hist)
-            log("Class Overall Accuracy: %f Class Mean Accuracy: %f Class Frequency Weighted Accuracy: %f Class Mean IoU: %f"
-                % (s["Overall Acc"], s["Mean Acc"], s["FreqW Acc"], s["Mean IoU"]))
-        if image_acc:
-            q = M.scores_from_quality(image_acc)
-            log("Image MAE: %f Image PSNR: %f Image SSIM: %f" % (q["MAE"], q["PSNR"], q["SSIM"]))
-        if swd is not None and swd.count["fakes"]:
-            self._swd_add_reals(swd, swd_reals)
-            if swd.count["reals"]:
-                log(" ".join("%s: %f" % kv for kv in M.swd_scalars(swd.result())))
+        def each(s):
+            log("Processing image: " + s.name)
+            save_images(s.image[None], [1, 1], os.path.join(args.test_dir, "real_" + os.path.basename(s.name)))
+            save_images(s.fake, [1, 1], os.path.join(args.test_dir, os.path.basename(s.name)))
+            return s.fake
+        out, results = E.run(self, samples, scorers, each, strict=False)
+        for res in results:
+            log(" ".join("%s: %f" % tv for tv in E.scalars(res)))
         return out
 
     def train(self, args, batches, log=print, test_samples=None, sink=None):
