@@ -664,6 +664,25 @@ int sgg_diffaug_bwd(const void* dy, const float* params, const void* addend, voi
  *   > 2^35 (the vector index is a 32-bit counter word) or n_samples > 65535 (the grid's y extent).  n_samples == 0: SGG_OK, no launch. */
 int sgg_dropout(void* x, int64_t n_samples, int64_t elems_per_sample, int threshold, const int64_t* iterations, uint32_t seed,
                 int64_t sample_offset, int stream_id, int dtype, void* stream);
+/* ---- fixed 2x resampling in front of a resize-convolution layer and its adjoint.  NHWC, padded channels.
+ * sgg_upsample2x_fwd: x (N,H,W,Cp) -> y (N,2H,2W,Cp).  sgg_upsample2x_bwd: dy (N,2H,2W,Cp) -> dx (N,H,W,Cp) = U^T dy, the adjoint
+ *   of the same linear map; N, H, W are the LOW-resolution extents in both.  in and out must not overlap.
+ *   SGG_UPSAMPLE_NEAREST:  y[n,p,q,c] = x[n,p>>1,q>>1,c] -- a copy, output bits are input bits; adjoint: the sum of the 2x2 block,
+ *     ((d[2i][2j] + d[2i][2j+1]) + d[2i+1][2j]) + d[2i+1][2j+1].
+ *   SGG_UPSAMPLE_BILINEAR: half-pixel centres (tf.image.resize, torch align_corners=False).  Per axis of length n:
+ *     y[2i] = 0.25 x[max(i-1,0)] + 0.75 x[i], y[2i+1] = 0.75 x[i] + 0.25 x[min(i+1,n-1)]; the 2-D operator is the tensor product
+ *     (4 taps per output, weights 9/16, 3/16, 3/16, 1/16).  Adjoint per axis: dx[i] = sum_{k=-1..2} w_k dy[clamp(2i+k, 0, 2n-1)],
+ *     w = (0.25, 0.75, 0.75, 0.25) -- the clamped taps are the border terms; 16 taps per result in 2-D.
+ *   Arithmetic: f32.  acc = w_0 * v_0, then acc = acc + w_t * v_t over the taps in row-major order of their source offsets (a
+ *   clamped tap keeps its place and weight), every product and sum rounded to f32, never contracted; w_t = row weight * column
+ *   weight, exact.  One rounding to the storage type (bf16: to nearest even).  Gathers: a thread computes whole results -- no
+ *   atomics, no workspace, one launch, bitwise reproducible, capturable.
+ * Before any launch -- SGG_EINVAL: a NULL pointer, a negative extent, Cp % 8 != 0, a base that is not 16-byte aligned, an unknown
+ *   mode or dtype (SGG_F32 | SGG_BF16); SGG_EUNSUPPORTED: N * H * W * Cp / 8 > 2^31 - 1 (the work-item index is 32-bit).  A zero
+ *   extent: SGG_OK, no launch. */
+typedef enum { SGG_UPSAMPLE_NEAREST = 0, SGG_UPSAMPLE_BILINEAR = 1 } sgg_upsample_mode;
+int sgg_upsample2x_fwd(const void* x, void* y, int N, int H, int W, int Cp, int mode, int dtype, void* stream);
+int sgg_upsample2x_bwd(const void* dy, void* dx, int N, int H, int W, int Cp, int mode, int dtype, void* stream);
 /* ---- sliced Wasserstein distance of Laplacian-pyramid patches (Karras et al. 2018, section 5; the semantics of
  * PGGAN's metrics/sliced_wasserstein.py [3P-recall]): an unpaired realism score of two image sets.  The sort between
  * sgg_swd_project and sgg_swd_distance is the caller's.

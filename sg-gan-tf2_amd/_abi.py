@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libsggan.so")      # the package reads no enviro
 SGG_F32, SGG_BF16, SGG_U8 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT = 0, 1
+UPSAMPLE_NEAREST, UPSAMPLE_BILINEAR = 0, 1         # sgg_upsample_mode
 CPAD = 8
 # enum sgg_route (include/sggan.h): the kernel a plain call launches; ROUTE_SPLITK is OR-ed in when the GEMM planner splits K
 ROUTE_NAMES = ("REG", "HALO3", "S2HALO", "S2N", "N7", "HALO_NARROW_IN", "HALO_FWD", "HALO_DGRAD_NARROW",
@@ -167,6 +168,8 @@ SIGNATURES = {
     "sgg_diffaug_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_diffaug_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_dropout": (_i, [_vp, _i64, _i64, _i, _vp, C.c_uint32, _i64, _i, _i, _vp]),
+    "sgg_upsample2x_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "sgg_upsample2x_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sgg_swd_pyramid_elems":(_sz, [_i, _i, _i]),
     "sgg_swd_pyramid_workspace": (_sz, [_i, _i, _i, _i]),
     "sgg_swd_project_workspace": (_sz, [_i64]),

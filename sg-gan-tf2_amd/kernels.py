@@ -1097,6 +1097,38 @@ def dropout_(x, rate, iterations, seed, sample_offset, stream_id):
     return x
 
 
+# ----------------------------------------------------------------------------- 2x resampling of the resize-convolution layers (csrc/upsample.hip)
+UPSAMPLE_THREADS, UPSAMPLE_CHUNK, UPSAMPLE_GRID_BLOCKS = 256, 256, 1024     # UP_THREADS, UP_CHUNK (low-resolution vectors of 8), UP_GRID_BLOCKS
+UPSAMPLE_MODES = {"nearest": A.UPSAMPLE_NEAREST, "bilinear": A.UPSAMPLE_BILINEAR}
+
+
+def upsample_mode(mode) -> int:
+    try:
+        return UPSAMPLE_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"upsample2x mode must be one of {', '.join(UPSAMPLE_MODES)}, got {mode!r}")
+
+
+def upsample2x(x, mode, out=None):
+    """sgg_upsample2x_fwd: x internal (N,H,W,Cp) -> (N,2H,2W,Cp), ``mode`` 'nearest' (a copy) or 'bilinear' (half-pixel centres)."""
+    m = upsample_mode(mode)
+    N, H, W, Cp = x.shape
+    out = _out(out, (N, 2 * H, 2 * W, Cp), x.dtype, x.device)
+    A.check(A.lib().sgg_upsample2x_fwd(_p(x), _p(out), N, H, W, Cp, m, dt(x), _s()), "upsample2x")
+    return out
+
+
+def upsample2x_bwd(dy, mode, out=None):
+    """sgg_upsample2x_bwd: the adjoint of upsample2x for the gradient dy (N,2H,2W,Cp) of its output -> (N,H,W,Cp)."""
+    m = upsample_mode(mode)
+    N, H2, W2, Cp = dy.shape
+    if H2 % 2 or W2 % 2:
+        raise ValueError(f"upsample2x_bwd: dy {tuple(dy.shape)} is no output of upsample2x (odd height or width)")
+    out = _out(out, (N, H2 // 2, W2 // 2, Cp), dy.dtype, dy.device)
+    A.check(A.lib().sgg_upsample2x_bwd(_p(dy), _p(out), N, H2 // 2, W2 // 2, Cp, m, dt(dy), _s()), "upsample2x_bwd")
+    return out
+
+
 # ----------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
 SWD_K = 147                     # values of a descriptor: a 7x7 patch of three channels, (channel, y, x)
 SWD_CHUNK = 256                  # descriptor rows per partial sum of the statistics (SW_CHUNK, csrc/swd.hip)

@@ -116,6 +116,11 @@ def build_parser():
            "generator's step counter, the layer and the global sample index, never stored, so it works under --graph, with data "
            "parallelism and after --continue_train; the test passes stay in inference mode.  Refused with --generator resnet: that "
            "network has no dropout layers")
+    a("--upsample", dest="upsample", choices=("deconv", "nearest", "bilinear"), default=argparse.SUPPRESS,
+      help="how generator_resnet's two doubling layers d1 / d2 reach the next resolution (DESIGN.md 29): 'deconv' (default) -- the "
+           "reference's stride-2 transposed 3x3 convs; 'nearest' | 'bilinear' -- a fixed 2x resampling followed by a 3x3 stride-1 "
+           "SAME conv, the resize-convolution of Odena et al. 2016 against checkerboard artifacts (4x the layer's multiply-adds).  "
+           "Same parameter count; a checkpoint loads only into a model of the same --upsample.  Refused with --generator unet")
     a("--class_scores", dest="class_scores", action="store_true", default=argparse.SUPPRESS,
       help="test pass: decode every translation to class labels through the palette learned from the test set's own (colour label, "
            "class map) pairs and score it against the class map: 'Class Overall Accuracy' ... 'Class Mean IoU' scalars, "

@@ -20,7 +20,7 @@ from . import _abi as A
 from . import evaluate as E
 from . import kernels as K
 from .graph import StepProgram
-from .module import Adam, check_d_norm, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet, GeneratorUNetPair
+from .module import Adam, check_d_norm, check_upsample, Discriminator, DiscriminatorPair, Generator, GeneratorPair, GeneratorUNet, GeneratorUNetPair
 from .utils import ImagePool, save_images, StaticImagePool
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32,
@@ -38,7 +38,7 @@ def default_args(**over):
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
              crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
              diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0, d_norm="instance",
-             dropout=None)
+             dropout=None, upsample="deconv")
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -91,6 +91,14 @@ class sggan(object):
         # launches: graph replay and checkpoints carry it, and data-parallel ranks, which hold identical W and u, compute
         # identical sigma without exchanging anything.  The generators never see it.
         self.d_norm = check_d_norm(g("d_norm", "instance"))
+        # upsample ("deconv" is the reference's network): "nearest" / "bilinear" build generator_resnet's two
+        # doubling layers as a fixed 2x resampling + a 3x3 stride-1 SAME conv (Odena et al. 2016) -- same parameter names and
+        # sizes, d1_w / d2_w in the Conv2D layout.  The resampling has no parameters and no state: every other option, graph
+        # replay, checkpoints and data parallelism see an ordinary conv unit with one launch in front and one behind.
+        self.upsample = check_upsample(g("upsample", "deconv") or "deconv")
+        if self.upsample != "deconv" and self.arch != "resnet":
+            raise ValueError("--upsample: generator_unet has no stride-2 layer to replace (all of its convs are stride 1: the option "
+                             "belongs to generator_resnet's d1 / d2: --generator resnet / use_resnet=True)")
         self.dtype = _DTYPES[g("dtype", "bf16")]
         self.device = torch.device(g("device", "cuda"))
         if self.device.type != "cuda":       # refused here, before any network (and so any buffer) is built
@@ -102,7 +110,7 @@ class sggan(object):
         def make_generator(in_c, out_c, seed):                  # :56 generator_resnet / :58 generator_unet
             kw = dict(gf_dim=g("ngf", 64), in_c=in_c, out_c=out_c, dtype=self.dtype, device=self.device, seed=seed)
             if self.arch == "resnet":
-                return Generator(n_blocks=g("n_blocks", 9), **kw)
+                return Generator(n_blocks=g("n_blocks", 9), upsample=self.upsample, **kw)
             return GeneratorUNet(**kw) if self.dropout is None else GeneratorUNet(dropout=self.dropout, **kw)
         self.generator = make_generator(self.input_c_dim, self.output_c_dim, seed)
         self.beta1 = g("beta1", 0.5)
@@ -864,6 +872,10 @@ class sggan(object):
             if _spectral_state(net) is not None:    # a spectrally normalised discriminator: its kind and its power-iteration vectors
                 sd[key]["d_norm"], sd[key]["u"] = "spectral", _spectral_state(net).cpu()
         sd["G"]["arch"] = self.arch             # generator architecture tag (a checkpoint without one is a ResNet checkpoint)
+        mine = getattr(self, "upsample", "deconv")
+        if mine != "deconv":                    # how d1 / d2 double the resolution (a checkpoint without the tag: transposed convs)
+            for key in names[0::2]:
+                sd[key]["upsample"] = mine
         return sd
 
     def load_state_dict(self, sd):
@@ -872,7 +884,12 @@ class sggan(object):
         if arch != self.arch:
             raise ValueError(f"checkpoint holds a {arch} generator, this model is built with a {self.arch} generator "
                              f"(--generator {self.arch}); load it into a model built with --generator {arch}")
-        for key in names[1::2]:                 # (before anything is copied)
+        for key in names[0::2]:                 # (before anything is copied)
+            kind, mine = sd[key].get("upsample", "deconv"), getattr(self, "upsample", "deconv")
+            if kind != mine:
+                raise ValueError(f"checkpoint holds a generator whose d1 / d2 are built with --upsample {kind}, this model is built "
+                                 f"with --upsample {mine}; load it into a model built with --upsample {kind}")
+        for key in names[1::2]:
             kind = sd[key].get("d_norm", "instance")
             mine = getattr(self, "d_norm", "instance")
             if kind != mine:

@@ -211,8 +211,21 @@ def _layer_specs(name, shape, out_ch, norm=True):
     return L + [(name + "_g", (out_ch,)), (name + "_beta", (out_ch,))] if norm else L
 
 
-def generator_param_specs(gf_dim=64, in_c=3, out_c=3, n_blocks=9):
-    """(name, shape) in Keras ``trainable_variables`` creation order of generator_resnet (module.py:219-269)."""
+UPSAMPLES = ("deconv", "nearest", "bilinear")
+
+
+def check_upsample(upsample):
+    """How generator_resnet's d1 / d2 double the resolution: 'deconv' (the reference's stride-2 transposed convs) or a fixed
+    'nearest' / 'bilinear' 2x resampling in front of a stride-1 conv."""
+    if upsample not in UPSAMPLES:
+        raise ValueError(f"upsample must be one of {', '.join(UPSAMPLES)}, got {upsample!r}")
+    return upsample
+
+
+def generator_param_specs(gf_dim=64, in_c=3, out_c=3, n_blocks=9, upsample="deconv"):
+    """(name, shape) in Keras ``trainable_variables`` creation order of generator_resnet (module.py:219-269).  upsample other
+    than "deconv": d1 / d2 are Conv2D kernels (kh,kw,in,out) -- the element counts, and with them every offset, are unchanged."""
+    resize = check_upsample(upsample) != "deconv"
     L = []
     L += _layer_specs("c1", (7, 7, in_c, gf_dim), gf_dim)
     L += _layer_specs("c2", (3, 3, gf_dim, gf_dim * 2), gf_dim * 2)
@@ -220,8 +233,12 @@ def generator_param_specs(gf_dim=64, in_c=3, out_c=3, n_blocks=9):
     for i in range(1, n_blocks + 1):
         L += _layer_specs(f"r{i}a", (3, 3, gf_dim * 4, gf_dim * 4), gf_dim * 4)
         L += _layer_specs(f"r{i}b", (3, 3, gf_dim * 4, gf_dim * 4), gf_dim * 4)
-    L += _layer_specs("d1", (3, 3, gf_dim * 2, gf_dim * 4), gf_dim * 2)     # Conv2DTranspose kernel: (kh,kw,out,in)
-    L += _layer_specs("d2", (3, 3, gf_dim, gf_dim * 2), gf_dim)
+    if resize:
+        L += _layer_specs("d1", (3, 3, gf_dim * 4, gf_dim * 2), gf_dim * 2)     # Conv2D kernel behind the 2x resampling: (kh,kw,in,out)
+        L += _layer_specs("d2", (3, 3, gf_dim * 2, gf_dim), gf_dim)
+    else:
+        L += _layer_specs("d1", (3, 3, gf_dim * 2, gf_dim * 4), gf_dim * 2)     # Conv2DTranspose kernel: (kh,kw,out,in)
+        L += _layer_specs("d2", (3, 3, gf_dim, gf_dim * 2), gf_dim)
     L += _layer_specs("out", (7, 7, gf_dim, out_c), out_c, norm=False)
     return L
 
@@ -637,7 +654,13 @@ class _BlockInput:
 # each layer's launches alike by construction.
 class _ResNetWalk:
     """generator_resnet (module.py:219-269) over ``head`` (three stem units), ``blocks`` ((a, b) unit pairs of the residual
-    blocks) and ``tail`` (two transposed units + the output unit); ``checkpoint_blocks`` selects activation checkpointing."""
+    blocks) and ``tail`` (two transposed units + the output unit); ``checkpoint_blocks`` selects activation checkpointing.
+    ``upsample`` other than "deconv" (DESIGN.md 29): the two doubling units are stride-1 SAME convs and the walk puts the fixed 2x
+    resampling K.upsample2x in front of each -- one launch on whatever batch the walk carries, so a lockstep pair's stacked batch
+    takes one for both networks -- and its adjoint K.upsample2x_bwd behind each one's data gradient.  The unit's record holds the
+    resampled tensor (its conv's input: the weight gradient reads it), which nothing else keeps alive."""
+
+    upsample = "deconv"
 
     def conv_units(self):
         return self.head + [u for pair in self.blocks for u in pair] + self.tail
@@ -657,6 +680,8 @@ class _ResNetWalk:
             h, rb = ub.forward(y, residual=h)                 # IN(conv(y)) + x   (:216-217)
             tape.append(_BlockInput(hin) if self.checkpoint_blocks else (ra, rb))
         for u in self.tail:
+            if self.upsample != "deconv" and u is not self.tail[-1]:
+                h = K.upsample2x(h, self.upsample)
             h, r = u.forward(h, out=out if u is self.tail[-1] else None)
             tape.append(r)
         return h, tape
@@ -679,6 +704,8 @@ class _ResNetWalk:
         d = dy
         for u, r in zip(reversed(self.tail), reversed(tape[len(tape) - nt:])):
             d = u.backward(r, d, True, param_grads, gbuf)
+            if self.upsample != "deconv" and u is not self.tail[-1]:
+                d = K.upsample2x_bwd(d, self.upsample)
             done(u.name)
         # residual blocks: each data gradient also makes the first pass of the norm backward that consumes it (the
         # norm of the conv before it in forward order), so that norm skips its statistics pass over the tensor
@@ -710,17 +737,24 @@ class _ResNetWalk:
 class Generator(_ResNetWalk, _Net):
     """generator_resnet (module.py:219-269): c7s1-64, d128, d256, 9 x R256, u128, u64, c7s1-3 + tanh."""
 
-    def __init__(self, gf_dim=64, in_c=3, out_c=3, n_blocks=9, dtype=torch.bfloat16, device="cuda", eps=1e-3, seed=19):
-        super().__init__(generator_param_specs(gf_dim, in_c, out_c, n_blocks), dtype, device, eps, seed)
-        self.in_c, self.out_c, self.n_blocks = in_c, out_c, n_blocks
+    def __init__(self, gf_dim=64, in_c=3, out_c=3, n_blocks=9, dtype=torch.bfloat16, device="cuda", eps=1e-3, seed=19,
+                 upsample="deconv"):
+        """upsample="nearest" | "bilinear" (DESIGN.md 29): u128 and u64 become the 2x resampling + a 3x3 stride-1 SAME conv +
+        IN + ReLU instead of the stride-2 transposed conv + IN + ReLU."""
+        super().__init__(generator_param_specs(gf_dim, in_c, out_c, n_blocks, upsample), dtype, device, eps, seed)
+        self.in_c, self.out_c, self.n_blocks, self.upsample = in_c, out_c, n_blocks, upsample
         U = lambda *a, **k: _ConvUnit(self, *a, **k)
         self.c1 = U("c1", "conv", reflect=3, act=A.ACT_RELU)                       # :230-234
         self.c2 = U("c2", "conv", stride=2, padding="SAME", act=A.ACT_RELU)        # :236-238
         self.c3 = U("c3", "conv", stride=2, padding="SAME", act=A.ACT_RELU)        # :240-242
         self.blocks = [(U(f"r{i}a", "conv", reflect=1, act=A.ACT_RELU),            # residule_block :208-217
                         U(f"r{i}b", "conv", reflect=1, act=A.ACT_NONE)) for i in range(1, n_blocks + 1)]
-        self.d1 = U("d1", "deconv", stride=2, act=A.ACT_RELU)                      # :254-256
-        self.d2 = U("d2", "deconv", stride=2, act=A.ACT_RELU)                      # :258-260
+        if upsample == "deconv":
+            self.d1 = U("d1", "deconv", stride=2, act=A.ACT_RELU)                  # :254-256
+            self.d2 = U("d2", "deconv", stride=2, act=A.ACT_RELU)                  # :258-260
+        else:                                                                      # (the walk resamples in front of each)
+            self.d1 = U("d1", "conv", padding="SAME", act=A.ACT_RELU)
+            self.d2 = U("d2", "conv", padding="SAME", act=A.ACT_RELU)
         self.out = U("out", "conv", reflect=3, norm=False, act=A.ACT_TANH)         # :262-265
         self.head, self.tail = [self.c1, self.c2, self.c3], [self.d1, self.d2, self.out]
 
@@ -1153,8 +1187,8 @@ class GeneratorPair(_ResNetWalk):
     one ResNet walk over lockstep units, on stacked tensors."""
 
     def __init__(self, ga, gb):
-        assert ga.n_blocks == gb.n_blocks
-        self.a, self.b = ga, gb
+        assert (ga.n_blocks, ga.upsample) == (gb.n_blocks, gb.upsample)
+        self.a, self.b, self.upsample = ga, gb, ga.upsample
         self.head, self.tail = _pair_units(ga.head, gb.head), _pair_units(ga.tail, gb.tail)
         self.blocks = [tuple(_pair_units(xa, xb)) for xa, xb in zip(ga.blocks, gb.blocks)]
 

@@ -178,6 +178,21 @@ class _SsimLossFn(torch.autograd.Function):
         return dx[..., :ctx.Cr] * dl, None, None
 
 
+class _Upsample2xFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mode):
+        Cr = x.shape[-1]
+        xp = _padc(x.detach(), K.cpad(Cr)).contiguous()
+        ctx.mode, ctx.Cr, ctx.dtype = mode, Cr, xp.dtype
+        y = K.upsample2x(xp, mode)
+        return y[..., :Cr] if y.shape[-1] != Cr else y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _padc(dy.to(ctx.dtype), K.cpad(ctx.Cr)).contiguous()
+        return K.upsample2x_bwd(dy, ctx.mode)[..., :ctx.Cr], None
+
+
 _ACTS = {None: A.ACT_NONE, "none": A.ACT_NONE, "relu": A.ACT_RELU, "lrelu": A.ACT_LRELU, "tanh": A.ACT_TANH}
 
 
@@ -225,3 +240,13 @@ def ssim_loss(x, target, data_range=1.0):
     if x.shape != target.shape or x.dim() != 4 or x.shape[-1] > A.CPAD:
         raise ValueError(f"ssim_loss: x {tuple(x.shape)} and target {tuple(target.shape)} must be equal (N,H,W,C) with C <= {A.CPAD}")
     return _SsimLossFn.apply(x, target, float(data_range))
+
+
+def upsample2x(x, mode="nearest"):
+    """The fixed 2x resampling of the resize-convolution layers: x (N,H,W,C) float32 or bfloat16 -> (N,2H,2W,C).
+    mode 'nearest' (tf.keras.layers.UpSampling2D()) or 'bilinear' (half-pixel centres: UpSampling2D(interpolation="bilinear"),
+    torch's align_corners=False).  The gradient w.r.t. x is the adjoint of the same linear map (sgg_upsample2x_bwd)."""
+    K.upsample_mode(mode)
+    if x.dim() != 4:
+        raise ValueError(f"upsample2x: x {tuple(x.shape)} must be (N,H,W,C)")
+    return _Upsample2xFn.apply(x, mode)
