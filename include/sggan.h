@@ -398,6 +398,33 @@ int sgg_gradloss(const void* in, const void* target, const float* weight, int N,
 size_t sgg_ssim_loss_workspace(int N, int H, int W, int C_real);
 int sgg_ssim_loss(const void* target, const void* x, int N, int H, int W, int C_real, int Cpad, float data_range, float weight,
                   float gscale, float* loss, void* dx, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* feature-matching loss (csrc/featmatch.hip; Wang et al. 2018): L pairs of activations in ONE call.
+ *   pairs: a HOST array of L entries, 1 <= L <= SGG_FM_MAX_PAIRS, read during the call only; real, fake, grad are device tensors
+ *   (P, Cpad) in dtype (SGG_F32 | SGG_BF16), 16-byte aligned, Cpad % 8 == 0, 1 <= C_real <= Cpad, padded channels zero in both
+ *   inputs.  real is a constant.  With count_i = P_i * C_real_i:
+ *     term      = (1/L) * sum_i (1/count_i) * sum_{p, c < C_real_i} |fake_i - real_i|      -> *term (f32, always overwritten)
+ *     *loss (+)= weight * term                                      (accumulate bit 0: the old value is added)
+ *     grad_i    = (float)(weight / (L * count_i)) * sign(fake_i - real_i), sign(0) = 0 stored as +0, +0 in padded channels;
+ *                 one rounding to dtype; always overwritten.
+ *   d = (double)fake - (double)real is exact; |d| is added in double in a fixed order (featmatch.hip's header: lane-strided,
+ *   a butterfly over the wave, the waves in order, the chunks of a layer in index order, the layers in order); term and the
+ *   loss contribution are each one rounding of a double to f32.  Two launches whatever L is; the table travels in the kernel
+ *   arguments: no copy, no atomics, no allocation, no host sync, bitwise reproducible, capturable.
+ *   ws: sgg_feature_match_workspace(pairs, L, dtype) bytes (pointers are not read; 0: the arguments are refused), 8-byte aligned.
+ * Before any launch, in this order -- SGG_EINVAL: NULL loss, term or pairs, L outside 1..SGG_FM_MAX_PAIRS, an unknown dtype, an
+ *   entry with P <= 0, Cpad <= 0, Cpad % 8 != 0, C_real outside [1, Cpad], a NULL or misaligned pointer; SGG_EUNSUPPORTED: a layer of
+ *   more than 2^31 - 1 sixteen-byte vectors; SGG_EWORKSPACE: ws NULL, misaligned or short. */
+#define SGG_FM_MAX_PAIRS 8
+typedef struct {
+    const void* real;
+    const void* fake;
+    void* grad;
+    int64_t P;
+    int32_t C_real, Cpad;
+} sgg_fm_pair;
+size_t sgg_feature_match_workspace(const sgg_fm_pair* pairs, int L, int dtype);
+int sgg_feature_match(const sgg_fm_pair* pairs, int L, float weight, float* loss, float* term, int accumulate, int dtype,
+                      void* ws, size_t ws_bytes, void* stream);
 
 /* ---- optimizer: tf.keras.optimizers.Adam.apply_gradients ---- model.py:199-200,205-207
  * Keras form, over one flat f32 buffer:  m=b1*m+(1-b1)*g; v=b2*v+(1-b2)*g^2;

@@ -50,6 +50,12 @@ class SpectralItem(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w", "g", "u", "v", "sigma", "inv_sigma")] + [("rows", C.c_int32), ("K", C.c_int32)]
 
 
+class FmPair(C.Structure):
+    """struct sgg_fm_pair (include/sggan.h)."""
+    _fields_ = [("real", C.c_void_p), ("fake", C.c_void_p), ("grad", C.c_void_p), ("P", C.c_int64), ("C_real", C.c_int32), ("Cpad", C.c_int32)]
+
+
+FM_MAX_PAIRS = 8                                   # SGG_FM_MAX_PAIRS
 SPECTRAL_BAND, SPECTRAL_MAX_K = 32, 1024           # SGG_SPECTRAL_BAND, SGG_SPECTRAL_MAX_K
 
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -136,6 +142,8 @@ SIGNATURES = {
     "sgg_gradloss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "sgg_ssim_loss_workspace": (_sz, [_i, _i, _i, _i]),
     "sgg_ssim_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "sgg_feature_match_workspace": (_sz, [_vp, _i, _i]),
+    "sgg_feature_match": (_i, [_vp, _i, _f, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "sgg_adam": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _f, _f, _f, _f, _vp]),
     "sgg_adam_iter": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _vp]),
     "sgg_adam_sched": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _f, _vp]),

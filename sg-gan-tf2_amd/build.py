@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsggan.so")
-SOURCES = ["conv.hip", "conv_halo3.hip", "conv_wgrad.hip", "norm.hip", "misc.hip", "adam.hip", "resample.hip", "warp.hip", "crf.hip", "evalseg.hip", "imgqual.hip", "diffaug.hip", "dropout.hip", "swd.hip", "ssimloss.hip", "spectral.hip", "upsample.hip"]
+SOURCES = ["conv.hip", "conv_halo3.hip", "conv_wgrad.hip", "norm.hip", "misc.hip", "adam.hip", "resample.hip", "warp.hip", "crf.hip", "evalseg.hip", "imgqual.hip", "diffaug.hip", "dropout.hip", "swd.hip", "ssimloss.hip", "spectral.hip", "upsample.hip", "featmatch.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-Wno-inline-asm"]
 
 

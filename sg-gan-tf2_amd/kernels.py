@@ -1129,6 +1129,76 @@ def upsample2x_bwd(dy, mode, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- feature-matching loss (csrc/featmatch.hip)
+FEATMATCH_THREADS, FEATMATCH_CHUNK = 256, 4096     # FM_THREADS, FM_CHUNK (16-byte vectors per block)
+
+
+def _fm_check(reals, fakes, c_reals):
+    L = len(fakes)
+    if not 1 <= L <= A.FM_MAX_PAIRS or len(reals) != L or len(c_reals) != L:
+        raise ValueError(f"feature_match: 1..{A.FM_MAX_PAIRS} pairs with one C_real each, got {len(reals)} reals, {L} fakes, {len(c_reals)} C_real")
+    for i, (r, f, c) in enumerate(zip(reals, fakes, c_reals)):
+        if tuple(r.shape) != tuple(f.shape) or r.dtype != f.dtype or f.dtype != fakes[0].dtype:
+            raise ValueError(f"feature_match: pair {i}: real {tuple(r.shape)} {r.dtype} against fake {tuple(f.shape)} {f.dtype} "
+                             f"(all pairs in {fakes[0].dtype})")
+        if f.dim() < 2 or f.numel() == 0 or f.shape[-1] % A.CPAD or not 1 <= int(c) <= f.shape[-1]:
+            raise ValueError(f"feature_match: pair {i}: {tuple(f.shape)} with C_real {c}: channels padded to a multiple of {A.CPAD}, "
+                             "1 <= C_real <= Cpad, no empty tensor")
+    return L
+
+
+def feature_match(reals, fakes, c_reals, loss, term, weight, accumulate_loss=False, out=None):
+    """sgg_feature_match: ``term`` = the mean over the L pairs of mean |fake_i - real_i| over the real channels,
+    ``loss`` (+)= weight * term, both 1-element f32 device tensors; returns [grad_i] = weight / (L * count_i) * sign(fake_i - real_i)
+    in the storage type (the reals are constants; ``out``: the caller's buffers for them).  Two launches for any L; the pair table
+    travels in the kernel arguments."""
+    L = _fm_check(reals, fakes, c_reals)
+    grads = [torch.empty_like(f) for f in fakes] if out is None else list(out)
+    if len(grads) != L or any(g.shape != f.shape or g.dtype != f.dtype for g, f in zip(grads, fakes)):
+        raise ValueError("feature_match: out must hold one buffer per pair, shaped and typed like its fake")
+    if any(s.dtype != torch.float32 or s.numel() != 1 for s in (loss, term)):
+        raise ValueError("feature_match: loss and term are 1-element float32 tensors")
+    for t in list(reals) + list(fakes) + grads + [loss, term]:          # (before any address is taken: the kernel walks flat memory)
+        if not (t.is_cuda and t.is_contiguous()):
+            raise ValueError("feature_match: device-resident contiguous tensors required")
+    pairs = (A.FmPair * L)(*[A.FmPair(r.data_ptr(), f.data_ptr(), g.data_ptr(), f.numel() // f.shape[-1], int(c), f.shape[-1])
+                             for r, f, g, c in zip(reals, fakes, grads, c_reals)])
+    d = dt(fakes[0])
+    ws = workspace(int(A.lib().sgg_feature_match_workspace(pairs, L, d)), fakes[0].device)
+    A.check(A.lib().sgg_feature_match(pairs, L, float(weight), _p(loss), _p(term), int(bool(accumulate_loss)), d, _p(ws), ws.numel(), _s()),
+            "feature_match")
+    return grads
+
+
+def feature_match_ref(reals, fakes, c_reals, weight, loss=None, bf16=False):
+    """The rule of ``feature_match`` in float64 NumPy (logging, tests):
+
+        count_i = (elements of pair i) / Cpad_i * C_real_i;   m_i = sum over c < C_real_i of |fake_i - real_i| / count_i
+        term = (m_0 + m_1 + ...) / L;   loss' = float32(weight * term) (+ loss, added in float32)
+        grad_i = float32(weight / (L * count_i)) * sign(fake_i - real_i), 0 in padded channels, rounded to bfloat16 when ``bf16``
+
+    ``weight`` enters as the f32 value the kernel receives; the sums are float64 in NumPy's order, not the kernel's
+    (its chunk order is emulated by the tests).  Returns (float32 term, float32 loss, [float32 grad_i])."""
+    f = np.float32
+    w = float(f(weight))
+    L = len(fakes)
+    means, grads = [], []
+    for r, x, c in zip(reals, fakes, c_reals):
+        r, x = np.asarray(r, dtype=np.float64), np.asarray(x, dtype=np.float64)
+        d = (x - r)[..., :int(c)]
+        count = d.size
+        means.append(float(np.abs(d).sum()) / count)
+        g = np.zeros(x.shape, dtype=np.float32)
+        g[..., :int(c)] = f(w / (L * count)) * np.sign(d).astype(np.float32)
+        grads.append(torch.from_numpy(g).to(torch.bfloat16).to(torch.float32).numpy() if bf16 else g)
+    term = 0.0
+    for m in means:
+        term += m
+    term /= L
+    out = f(w * term)
+    return f(term), (out if loss is None else f(f(loss) + out)), grads
+
+
 # ----------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
 SWD_K = 147                     # values of a descriptor: a 7x7 patch of three channels, (channel, y, x)
 SWD_CHUNK = 256                  # descriptor rows per partial sum of the statistics (SW_CHUNK, csrc/swd.hip)

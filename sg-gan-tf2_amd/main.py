@@ -102,6 +102,13 @@ def build_parser():
     a("--ssim_data_range", dest="ssim_data_range", type=float, default=argparse.SUPPRESS,
       help="--ssim_lambda: the span of the image values that fixes SSIM's constants C1 = (0.01 R)^2, C2 = (0.03 R)^2 "
            "(default 1: the step's images live in [0,1])")
+    a("--fm_lambda", dest="fm_lambda", type=float, default=argparse.SUPPRESS,
+      help="paired (reference-mode) step: add X * the feature-matching term of pix2pixHD (Wang et al. 2018) to the generator's loss "
+           "(default 0 = off): the mean over the discriminator's seven intermediate activations of mean |D_k(fake) - D_k(label "
+           "image)|, from one call on the activations the discriminator pass already holds; the discriminator's own gradient "
+           "never sees it (DESIGN.md 30).  Works under --graph, with data parallelism, both generators, --d_norm spectral, "
+           "--ssim_lambda, --dropout, --upsample, the guard flags, --ema_decay, --augment and --lr_decay.  Refused with --cycle "
+           "(no pixel-aligned real) and with --diffaug (independent draws for reals and fakes)")
     a("--d_norm", dest="d_norm", choices=("instance", "spectral"), default=argparse.SUPPRESS,
       help="normalisation of the discriminators (default instance, the reference's network).  spectral (Miyato et al. 2018): no "
            "discriminator layer has an instance norm -- it would cancel any scale of the kernel in front of it -- and every "

@@ -38,7 +38,7 @@ def default_args(**over):
              checkpoint_blocks=False, use_pool=False, pool_static=False, fuse_in_stats_deconv=False, fuse_in_stats_stem=False,
              crf=False, lr_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, diffaug=None,
              diffaug_brightness=0.25, swd=False, swd_patches=128, ssim_lambda=0.0, ssim_data_range=1.0, d_norm="instance",
-             dropout=None, upsample="deconv")
+             dropout=None, upsample="deconv", fm_lambda=0.0)
     a.update(over)
     return SimpleNamespace(**a)
 
@@ -99,6 +99,21 @@ class sggan(object):
         if self.upsample != "deconv" and self.arch != "resnet":
             raise ValueError("--upsample: generator_unet has no stride-2 layer to replace (all of its convs are stride 1: the option "
                              "belongs to generator_resnet's d1 / d2: --generator resnet / use_resnet=True)")
+        # fm_lambda (off by default): the paired step's generator loss also gets fm_lambda * the feature-matching
+        # term of pix2pixHD -- the mean over D's seven intermediate activations of mean |D_k(fake) - D_k(seg)| -- from ONE
+        # K.feature_match call on the tape D's pass already recorded; its seven gradients join the generator-gradient walk through D
+        # in the data-gradient stores (feature_addends).  D's own gradient never sees the term, and it keeps no state: graph
+        # replay, checkpoints and data parallelism (a per-rank mean, averaged like L1) need nothing.  0: no launch, no buffer.
+        fm = g("fm_lambda", 0.0)
+        self.fm_lambda = float(fm or 0.0)
+        if not (math.isfinite(self.fm_lambda) and self.fm_lambda >= 0.0):
+            raise ValueError(f"fm_lambda must be finite and >= 0, got {fm!r}")
+        if self.fm_lambda and self.cycle:
+            raise ValueError("--fm_lambda with --cycle: the cycle step's fakes have no pixel-aligned real, so there is no per-sample "
+                             "feature target; the term belongs to the paired (reference-mode) step")
+        if self.fm_lambda and K.diffaug_policy_bits(g("diffaug", None)):
+            raise ValueError("--fm_lambda with --diffaug: reals and fakes take independent draws, so their discriminator features "
+                             "stop corresponding; train with one of the two")
         self.dtype = _DTYPES[g("dtype", "bf16")]
         self.device = torch.device(g("device", "cuda"))
         if self.device.type != "cuda":       # refused here, before any network (and so any buffer) is built
@@ -128,6 +143,7 @@ class sggan(object):
         self.real_A = self.seg_A = self.mask_A = self.fake_A = None
         self._loss = torch.zeros(2, dtype=torch.float32, device=self.device)    # [gen_loss, disc_loss] on device
         self.gen_loss, self.disc_loss = self._loss[0:1], self._loss[1:2]
+        self.fm_loss = torch.zeros(1, dtype=torch.float32, device=self.device) if self.fm_lambda else None   # the term itself
         self._dp = None
         self._world = 1
         self.dataset_dir = g("dataset_dir", "city")
@@ -525,11 +541,16 @@ class sggan(object):
             D.backward(tDr, d_real_d, want_dx=False, param_grads=True)
             D.backward(tDf, d_fake_d, want_dx=False, param_grads=True)
         hD = self._allreduce(D)
+        fm_grads = None
+        if self.fm_lambda:      # + fm_lambda * mean_k mean |D_k(fake) - D_k(seg)|: the generator's loss only, the reals constants
+            f_real, f_fake = (D.features(tDq, 0, N), D.features(tDq, N, 2 * N)) if stack else (D.features(tDr), D.features(tDf))
+            fm_grads = K.feature_match(f_real, f_fake, [u.cout for u in D.units], gl, self.fm_loss, self.fm_lambda, accumulate_loss=True)
         # gen_tape.gradient(gen_loss, G vars)    (:196): through D's data path, then G
         if aug:         # ... and back through the transform's adjoint, which takes over the join
             dfake = K.diffaug_bwd(D.backward(tDf, d_fake_g, want_dx=True, param_grads=False), par[N:], self.output_c_dim, addend=dfake_l1)
         else:
-            dfake = D.backward(tDf, d_fake_g, want_dx=True, param_grads=False, addend=dfake_l1)   # (the join rides on h0's data-gradient store)
+            dfake = D.backward(tDf, d_fake_g, want_dx=True, param_grads=False, addend=dfake_l1,    # (the join rides on h0's data-gradient store,
+                               feature_addends=fm_grads)                                          #  the feature gradients on h1's .. h4's)
         hook, (hG,) = self._bucketed_allreduce((G,))
         G.backward(tG, dfake, want_dx=False, param_grads=True, on_unit_done=hook)
 
@@ -1017,7 +1038,7 @@ class sggan(object):
         history, epoch = [], 0
         try:
             for epoch in range(args.epoch):
-                self.gen_loss_metric = self.disc_loss_metric = 0.0
+                self.gen_loss_metric = self.disc_loss_metric = self.fm_loss_metric = 0.0
                 self._metric_n = 0
                 data = batches(epoch)
                 if not hasattr(data, "__len__"):       # a sized source (data.DirectoryBatches) refills its buffers per step: keep it lazy
@@ -1032,7 +1053,12 @@ class sggan(object):
                     self._metric_n += 1
                     self.gen_loss_metric += (gl - self.gen_loss_metric) / self._metric_n
                     self.disc_loss_metric += (dl - self.disc_loss_metric) / self._metric_n
-                    log("Epoch: [%2d] [%4d/%4d] time: %4.4f Gen_Loss: %f Disc_Loss: %f " % (epoch, idx, len(data), time.time() - start, gl, dl))
+                    line = "Epoch: [%2d] [%4d/%4d] time: %4.4f Gen_Loss: %f Disc_Loss: %f " % (epoch, idx, len(data), time.time() - start, gl, dl)
+                    if self.fm_lambda:                 # the term itself (unweighted), read beside the two losses
+                        fm = float(self.fm_loss.item())
+                        self.fm_loss_metric += (fm - self.fm_loss_metric) / self._metric_n
+                        line += "fm_loss: %f " % fm
+                    log(line)
                 # epoch end (model.py:263-268): the test pass + image summary, then the two running-mean loss scalars
                 if test_samples is not None:
                     extra = {"swd_reals": args.swd_reals} if getattr(args, "swd", False) and getattr(args, "swd_reals", None) is not None else {}
@@ -1043,6 +1069,8 @@ class sggan(object):
                 if sink is not None:
                     sink.scalar("Generator Loss", self.gen_loss_metric, epoch)
                     sink.scalar("Discriminator Loss", self.disc_loss_metric, epoch)
+                    if self.fm_lambda:
+                        sink.scalar("Feature Matching Loss", self.fm_loss_metric, epoch)
                     if self.lr_decay:              # the rate the generator's last update of this epoch applied
                         last = max(self.g_optim.iterations.item() - 1, 0)
                         sink.scalar("Learning Rate", float(K.scheduled_lr(self.g_optim.learning_rate, last, *self._lr_sched_host)), epoch)

@@ -884,15 +884,27 @@ class _DiscriminatorWalk:
         tape.append((mask, tuple(h.shape)))
         return out, tape
 
-    def backward(self, tape, dlogits, want_dx=False, param_grads=True, gbuf=None, addend=None):
-        """addend: added to the image gradient in the first unit's data-gradient store (as in the generators' walks)."""
+    def backward(self, tape, dlogits, want_dx=False, param_grads=True, gbuf=None, addend=None, feature_addends=None):
+        """addend: added to the image gradient in the first unit's data-gradient store (as in the generators' walks).
+        feature_addends: one tensor per entry of ``features(tape)``; entry k, the gradient of a loss on feature k,
+        joins the walk's gradient of that feature where it is made -- in the data-gradient store of unit k + 1, its consumer,
+        exactly as ``addend`` joins the image gradient in h0's.  None: the walk as it always was, call for call."""
         *recs, (mask, h4_shape) = tape
         d = K.mask_reduce_bwd(dlogits.contiguous(), mask, h4_shape, self.dtype, self.segment_class)
         units = self.conv_units()
+        joins = [addend] + (list(feature_addends) if feature_addends is not None else [None] * (len(units) - 1))
+        assert len(joins) == len(units), f"feature_addends: {len(units) - 1} tensors, one per feature"
         for u, r in zip(reversed(units), reversed(recs)):
             first = u is units[0]
-            d = u.backward(r, d, want_dx or not first, param_grads, gbuf, addend=addend if first else None)
+            d = u.backward(r, d, want_dx or not first, param_grads, gbuf, addend=joins.pop())
         return d
+
+    def features(self, tape, lo=None, hi=None):
+        """The intermediate activations of a pass: the outputs of h0 .. h33 -- post-activation, each already
+        materialised as the recorded input of the unit behind it (h1 .. h33, h4) -- of images [lo, hi), as views, sliced like
+        ``slice_tape``.  h4's output, the logit map, is not a feature."""
+        *recs, _ = tape
+        return [r[1][lo:hi] for r in recs[1:]]
 
     def slice_tape(self, tape, lo, hi):
         """The forward records of images [lo, hi) of a pass, as views (a backward pass through part of the batch: the step sends

@@ -178,6 +178,24 @@ class _SsimLossFn(torch.autograd.Function):
         return dx[..., :ctx.Cr] * dl, None, None
 
 
+class _FeatureMatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, n, *tensors):
+        fakes, reals = tensors[:n], tensors[n:]
+        crs = [f.shape[-1] for f in fakes]
+        fp = [_padc(f.detach().to(torch.float32), K.cpad(c)).contiguous() for f, c in zip(fakes, crs)]
+        rp = [_padc(r.detach().to(torch.float32), K.cpad(c)).contiguous() for r, c in zip(reals, crs)]
+        loss, term = (torch.empty(1, dtype=torch.float32, device=fp[0].device) for _ in range(2))
+        grads = K.feature_match(rp, fp, crs, loss, term, 1.0)        # the gradients are the forward's by-product: kept for backward
+        ctx.crs = crs
+        ctx.save_for_backward(*grads)
+        return term[0]
+
+    @staticmethod
+    def backward(ctx, dl):
+        return (None,) + tuple(g[..., :c] * dl for g, c in zip(ctx.saved_tensors, ctx.crs)) + (None,) * len(ctx.crs)
+
+
 class _Upsample2xFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mode):
@@ -240,6 +258,17 @@ def ssim_loss(x, target, data_range=1.0):
     if x.shape != target.shape or x.dim() != 4 or x.shape[-1] > A.CPAD:
         raise ValueError(f"ssim_loss: x {tuple(x.shape)} and target {tuple(target.shape)} must be equal (N,H,W,C) with C <= {A.CPAD}")
     return _SsimLossFn.apply(x, target, float(data_range))
+
+
+def feature_match(fakes, reals):
+    """The feature-matching term (Wang et al. 2018) as a scalar: the mean over the pairs of mean |fake_i - real_i|,
+    for 1 to 8 pairs of (..., C_i) float32 tensors of equal shapes.  The reals are constants; the gradient goes to ``fakes`` only
+    (sign(fake - real) / (L * numel_i), 0 where they are equal), computed by the same call (sgg_feature_match)."""
+    fakes, reals = list(fakes), list(reals)
+    if not 1 <= len(fakes) <= A.FM_MAX_PAIRS or len(reals) != len(fakes) or any(f.shape != r.shape or f.dim() < 2 for f, r in zip(fakes, reals)):
+        raise ValueError(f"feature_match: 1..{A.FM_MAX_PAIRS} pairs of equally shaped (..., C) tensors, got "
+                         f"{[tuple(f.shape) for f in fakes]} against {[tuple(r.shape) for r in reals]}")
+    return _FeatureMatchFn.apply(len(fakes), *fakes, *reals)
 
 
 def upsample2x(x, mode="nearest"):
