@@ -23,6 +23,13 @@ class GradExchange:
         src = dist.get_global_rank(self.group, src_rank_in_group)
         dist.broadcast(flat_params, src=src, group=self.group)
 
+    def broadcast_object(self, obj, src_rank_in_group=0):
+        """Rank 0's small picklable host object (the replicas' draw keys), returned on every rank."""
+        src = dist.get_global_rank(self.group, src_rank_in_group)
+        box = [obj if self.rank == src_rank_in_group else None]
+        dist.broadcast_object_list(box, src=src, group=self.group)
+        return box[0]
+
     def allreduce_async(self, flat_grad):
         """Sum one network's gradient bucket over ranks; returns a handle whose wait() orders the current stream."""
         return dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group, async_op=True)

@@ -88,8 +88,8 @@ class sggan(object):
         # norms and runs every one of their convs on W / sigma(W) -- one power iteration per discriminator per training step
         # (Discriminator.spectral_step, first thing in the step bodies), the gradient transform directly before their Adam
         # launch (_apply_gradients).  The whole state is one small vector per layer on the device, advanced by the step's own
-        # launches: graph replay and checkpoints carry it, and data-parallel ranks, which hold identical W and u, compute
-        # identical sigma without exchanging anything.  The generators never see it.
+        # launches: graph replay and checkpoints carry it, and data-parallel ranks, which hold identical W and u (rank 0's:
+        # enable_data_parallel), compute identical sigma without exchanging anything.  The generators never see it.
         self.d_norm = check_d_norm(g("d_norm", "instance"))
         # upsample ("deconv" is the reference's network): "nearest" / "bilinear" build generator_resnet's two
         # doubling layers as a fixed 2x resampling + a 3x3 stride-1 SAME conv (Odena et al. 2016) -- same parameter names and
@@ -206,7 +206,8 @@ class sggan(object):
         # ema_decay (off by default): the generators' updates also keep an exponential moving average of their
         # parameters, in the update's own launches -- the decay ramp follows the device step counter and a skipped update
         # leaves the average alone -- and the test passes run on the average (ema_weights).  Data parallel: nothing to
-        # exchange, every rank applies the same update to the same average.
+        # exchange per step, every rank applies the same update to the same average -- the same because enable_data_parallel
+        # broadcasts rank 0's average with the rest of the replicated state.
         ema = g("ema_decay", None)
         self.ema_decay = None if ema is None else float(ema)
         if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:
@@ -256,13 +257,41 @@ class sggan(object):
     # ------------------------------------------------------------------ data parallel (new capability)
     def enable_data_parallel(self, process_group=None):
         """Average gradients over ranks with one all-reduce per network, launched as soon as that
-        network's backward has been queued so it overlaps with the rest of the step (dp.GradExchange)."""
+        network's backward has been queued so it overlaps with the rest of the step (dp.GradExchange).
+
+        Every claim the options make about data parallelism ("ranks hold identical W and u", "every rank applies the same update
+        to the same average", "the draws of the single-device run") rests on the replicas being identical, and this call is what
+        makes them so: every rank takes rank 0's replicated state -- all that ``state_dict`` writes: parameters, Adam slots and step
+        counter, the guard's counters, the weight average, the spectral u -- and rank 0's draw keys (the networks' seeds, which
+        key the dropout masks and the seeded start of u, and the augmentation's seed).  However the ranks were built, seeded or
+        resumed, they leave this call equal bit for bit; what a rank draws then differs by its sample offset alone."""
         from .dp import GradExchange
         self._dp = GradExchange(process_group)
         self._world = self._dp.world
-        for net in self.networks():                             # identical replicas: broadcast rank 0's parameters
-            self._dp.broadcast_(net.P.flat)
-            net.P.version += 1
+        nets = self.networks()
+        # host side first: the draw keys, and which networks carry a guard record on rank 0 (a checkpoint's counters allocate it
+        # at load, a fresh model at its first guarded step), so that every rank enters the same collectives below
+        keys = self._dp.broadcast_object({"seeds": [n.seed for n in nets], "diffaug": self._diffaug_seed,
+                                          "guard": [n.P._guard is not None for n in nets]})
+        self._diffaug_seed = int(keys["diffaug"])
+        for net, seed, guard in zip(nets, keys["seeds"], keys["guard"]):
+            P = net.P
+            net.adopt_seed(seed)
+            state = [P.flat, P.m, P.v, P._adam_state]
+            if guard:
+                state.append(P.guard_buffers()[0])
+            elif P._guard is not None:                          # (rank 0 has counted nothing)
+                P._guard.zero_()
+            if P.ema is not None:
+                state += [P.ema, P._ema_state]
+            u = _spectral_state(net)
+            if u is not None:
+                state.append(u)
+            for t in state:
+                self._dp.broadcast_(t)
+            P.version += 1
+            if u is not None and self._world > 1:               # u may have been replaced: sigma is computed anew
+                net._sn.seen = None
         self._program = None                                    # a recorded step has no collectives in it: record again
         return self
 

@@ -574,6 +574,10 @@ class _Net:
     def conv_units(self):
         return ()
 
+    def adopt_seed(self, seed):
+        """Take over another replica's seed, the key of this network's draws (sggan.enable_data_parallel)."""
+        self.seed = int(seed)
+
     def repack_all(self, dtype):
         """Pack the GEMM operands of every conv layer from the current parameters with ONE launch (all of them go stale
         together at each optimizer step); buffers and the device-side item table are built once per dtype."""
@@ -952,19 +956,30 @@ class Discriminator(_DiscriminatorWalk, _Net):
         mats = [tuple(int(d) for d in (np.prod(P.index[u.name + "_w"][2][:-1]), P.index[u.name + "_w"][2][-1])) for u in self.conv_units()]
         pad4 = lambda n: (n + 3) // 4 * 4
         uo, vo = np.cumsum([0] + [pad4(k) for _, k in mats]), np.cumsum([0] + [pad4(r) for r, _ in mats])
-        gen = torch.Generator(device="cpu").manual_seed(int(seed if seed is not None else 0) + 7919)
-        host = torch.zeros(int(uo[-1]), dtype=torch.float32)
-        for (_, k), o in zip(mats, uo):
-            d = torch.randn(k, generator=gen, dtype=torch.float64)
-            host[o:o + k] = (d / d.norm()).to(torch.float32)
         sn = self._sn = SimpleNamespace(mats=mats, uo=uo, vo=vo)
-        sn.u0 = host                                                             # (the seeded start: a checkpoint without u resumes from it)
+        sn.u0 = host = self._seeded_u(seed)                                      # (the seeded start: a checkpoint without u resumes from it)
         sn.u = host.to(dev)
         sn.v = torch.zeros(int(vo[-1]), dtype=torch.float32, device=dev)
         sn.sigma = torch.ones(len(mats), dtype=torch.float32, device=dev)
         sn.inv_sigma = torch.ones(len(mats), dtype=torch.float32, device=dev)
         sn.table = K.SpectralTable(self._spectral_entries(P.grad), dev)
         sn.seen = None               # P.loaded at the time sigma was last computed (None: never)
+
+    def _seeded_u(self, seed):
+        """The seeded start of the u vectors, flat on the host: a function of the seed and the layers' widths alone."""
+        sn = self._sn
+        gen = torch.Generator(device="cpu").manual_seed(int(seed if seed is not None else 0) + 7919)
+        host = torch.zeros(int(sn.uo[-1]), dtype=torch.float32)
+        for (_, k), o in zip(sn.mats, sn.uo):
+            d = torch.randn(k, generator=gen, dtype=torch.float64)
+            host[o:o + k] = (d / d.norm()).to(torch.float32)
+        return host
+
+    def adopt_seed(self, seed):
+        """... and, with it, the seeded start of u.  The vectors in use are not touched."""
+        super().adopt_seed(seed)
+        if self._sn is not None:
+            self._sn.u0 = self._seeded_u(seed)
 
     def _spectral_entries(self, gbuf):
         sn, P = self._sn, self.P

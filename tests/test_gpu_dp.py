@@ -3,13 +3,12 @@
 
 * world size 1 over RCCL ("nccl"): async all-reduce + wait() + grad_scale through the real step, eager and as HIP-graph
   segments with the collectives between them -- must be bit-identical to the model without data parallelism.
-* world size 2 (two processes sharing the one GPU; gloo moves the CUDA buckets): each rank steps on its half of the
-  batch; the averaged-gradient step must equal the single-process step on the concatenated batch,
+* world size 2 (two processes sharing the one GPU, started by tests/dp_harness.py; gloo moves the CUDA buckets): each rank steps
+  on its half of the batch; the averaged-gradient step must equal the single-process step on the concatenated batch,
   and the two replicas must stay bit-identical.
 """
 import os
 import socket
-import sys
 import warnings
 
 import numpy as np
@@ -81,50 +80,27 @@ def test_dp_world1_rccl_is_bit_identical_to_plain_step(cycle):
         dist.destroy_process_group()
 
 
-def _worker(rank, world, port, graph, out):
-    try:
-        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        sys.path.insert(0, ROOT)
-        import torch.distributed as dist
-        import sggan_amd as sg
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        m = sg.sggan(sg.default_args(ngf=16, ndf=16, n_blocks=2, dtype="f32", cycle=True, seed=19 + 7 * rank, graph=graph))
-        m.enable_data_parallel()                      # broadcasts rank 0's parameters: replicas start identical
-        a, b = _inputs(4, 5), _inputs(4, 6)
-        _set(m, a, b, slice(2 * rank, 2 * rank + 2))
-        m.train_step()
-        gl, dl = m.losses()
-        grads = [(n.P.grad / world).cpu().numpy() for n in m.networks()]       # buckets hold the SUM over ranks
-        m.train_step()                                                          # a second step: replicas must not drift apart
-        flat = torch.cat([n.P.flat for n in m.networks()]).cpu()
-        out.put((rank, flat.numpy(), grads, gl, dl, None))
-        dist.destroy_process_group()
-    except Exception as e:                              # surfaced by the parent
-        import traceback
-        out.put((rank, None, None, 0.0, 0.0, traceback.format_exc()))
+def _worker(rank, world, graph):
+    """One rank of the world-2 test (tests/dp_harness.py starts it in a fresh process, the process group initialised)."""
+    import sggan_amd as sg
+    m = sg.sggan(sg.default_args(ngf=16, ndf=16, n_blocks=2, dtype="f32", cycle=True, seed=19 + 7 * rank, graph=graph))
+    m.enable_data_parallel()                      # broadcasts rank 0's state: replicas start identical
+    a, b = _inputs(4, 5), _inputs(4, 6)
+    _set(m, a, b, slice(2 * rank, 2 * rank + 2))
+    m.train_step()
+    gl, dl = m.losses()
+    grads = [(n.P.grad / world).cpu().numpy() for n in m.networks()]       # buckets hold the SUM over ranks
+    m.train_step()                                                          # a second step: replicas must not drift apart
+    flat = torch.cat([n.P.flat for n in m.networks()]).cpu()
+    return {1: flat.numpy(), 2: grads, 3: gl, 4: dl}
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
 def test_dp_world2_train_step_equals_concatenated_batch(graph):
-    import torch.multiprocessing as mp
     import sggan_amd as sg
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, graph, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = {}
-    for _ in range(2):
-        r = q.get(timeout=300)
-        res[r[0]] = r
-    for p in procs:
-        p.join(60)
-    for r in res.values():
-        if r[5] is not None and "gloo" in r[5].lower() and ("cuda" in r[5].lower() or "not supported" in r[5].lower()):
-            pytest.skip("this PyTorch build's gloo backend cannot move CUDA tensors: " + r[5].splitlines()[-1])
-        assert r[5] is None, r[5]
+    from tests import dp_harness
+    res = dict(enumerate(dp_harness.launch(_worker, [graph, graph])))
+    print("transport:", res[0]["transport"])
     assert np.array_equal(res[0][1], res[1][1])                     # replicas bit-identical after two steps
     assert all(np.array_equal(a, b) for a, b in zip(res[0][2], res[1][2]))
     # single process, concatenated batch, same initial parameters (rank 0's seed): the averaged gradients of step 1
@@ -134,9 +110,16 @@ def test_dp_world2_train_step_equals_concatenated_batch(graph):
     errs = []
     for name, net, g_dp in zip(("G_AB", "D_A", "G_BA", "D_B"), m.networks(), res[0][2]):
         g = net.P.grad.cpu().numpy()
-        # relative L2: the sign() terms of the cycle / gradient-sensitive losses make single elements piecewise
-        # constant in the fakes, and the pixel-split / split-K partitions (hence the f32 summation order) depend on
-        # the per-rank batch size; D's tail runs InstanceNorm over 5x5 maps with rstd up to 31.6
+        # relative L2.  What this bound holds is the comparison of two f32 runs with each other, not the kernels' error: against
+        # float64 with every ReLU / LeakyReLU kink and every sign() of the L1 / gradient-sensitive terms taken the device's way,
+        # the exchanged buffers of a world-2 step are within 1.5e-5 of the sum of the ranks' oracle gradients in every tensor
+        # (tests/test_gpu_dp_options.py, bound 2e-4).  Here nothing aligns those decisions: the pixel-split / split-K partitions
+        # (hence the f32 summation order) depend on the per-rank batch size, the two runs' fakes differ in their last bits, and
+        # every sign() argument or pre-activation that lands on the other side of zero moves its element's gradient by a whole
+        # step (2 lambda / count for a sign); D's tail runs InstanceNorm over 5x5 maps with rstd up to 31.6.  Measured on an
+        # MI355X: 2.4e-3 (G_AB), 7e-4 (G_BA), 8e-4 (D_B), 1.3e-4 (D_A) -- the count of flipped decisions is a property of this
+        # seed's images, not derivable, so the bound stays at about twice the largest; a wrong mask, offset or clip factor is
+        # tests/test_gpu_dp_options.py's to find, at its bounds
         errs.append((name, float(np.linalg.norm(g_dp - g) / np.linalg.norm(g))))
     print("DP(2 ranks) vs concatenated batch, relative L2 error of the averaged gradients:", errs)
     assert all(e < 5e-3 for _, e in errs), errs
